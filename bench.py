@@ -3,7 +3,7 @@
 kernel and of the PQ-distance stage (K2) alone, and the CPU baseline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sift1b_shape|sift1m|sift10m|deep100m_shape|small|tiny]
-                    [--graph host|device|auto] [--pull -1|0|1] [--batches B] [--no-legs] [--legs k2,sift1m,...]
+                    [--graph host|device|auto] [--pull -1|0|1] [--batches B] [--no-legs] [--legs k2,sift1m,...] [--dump-outputs DIR]
 
 One process per GPU.  `--gpus N` IS the rank count: under a launcher (torchrun sets RANK / LOCAL_RANK / WORLD_SIZE) WORLD_SIZE must equal N;
 without one, N > 1 makes this process start its N ranks itself (tools/bench_legs/launch.py: fresh children before anything touches the GPU,
@@ -85,6 +85,34 @@ def build_everything(rank, world):
     _ = binding
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, ctx):
+    """--dump-outputs: what the caller of the timed path holds after the LAST timed step of the primary configuration, as DIR/<name>.npy --
+    `ids` [Q][k] (the gathered batch where an N > 1 step ends in the all-gather, else this rank's block; the u64 ids are stored as float64,
+    exact below 2**53) and `dists` [k][Q] float32 (rank 0's own block, in the layout bang_query returns).  The workloads are seeded, so two
+    builds run with the same arguments on machines of the same memory sizes (a *_shape workload's N is scaled to them: config.workload)
+    can be compared file for file.  Past 64 MB in all, a fixed sample of the queries is written instead (the same rows every run, listed in
+    `query_rows`)."""
+    gathered = (ctx.world > 1 or getattr(ctx, "force_gather", False)) and not ctx.weak
+    ids = getattr(ctx, "batch_ids", None) if gathered else None
+    ids = np.asarray(res["ids"] if ids is None else ids).astype(np.float64)
+    dists = None if res["dists"] is None else np.asarray(res["dists"], dtype=np.float32)
+    out = {"ids": ids, "dists": dists}
+    per_query = ids[0].nbytes + (dists[:, 0].nbytes if dists is not None else 0)
+    budget = DUMP_CAP_BYTES - 4096                            # (the .npy headers)
+    if ids.shape[0] * per_query > budget:
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], budget // (per_query + 8), replace=False))   # (+ its query_rows entry)
+        out = {"ids": ids[rows], "dists": None if dists is None else dists[:, rows[rows < dists.shape[1]]],
+               "query_rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        if a is not None:
+            np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+    log(f"[bench] outputs of the last timed step written to {out_dir}: " + ", ".join(f"{n} {a.dtype} {list(a.shape)}" for n, a in out.items() if a is not None))
+
+
 # ---------------------------------------------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -122,7 +150,11 @@ def main():
     ap.add_argument("--no-events", action="store_true", help="do not stamp the launches of the timed steps")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from the committed PMC passes (profiles/) instead of two rocprofv3 passes of this run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the primary configuration's last timed step returned as DIR/<name>.npy (see dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N is the rank count, whoever starts the ranks (tools/bench_legs/launch.py).  Without a launcher and N > 1 this process starts the N
     # ranks itself -- before it or anything it imported has touched the GPU --, relays rank 0's line and exits with their status; with a launcher
@@ -195,6 +227,8 @@ def main():
                       stream=(args.pull != 0 and not args.resident_graph), reserve_rows=(args.pull != 0), Q=args.queries,
                       shape_n=args.shape_n, batches=args.batches, lanes=lanes, threads=threads, keep=True, host_codes=args.host_codes)
     res, agg, L, graph = prim["res"], prim["res"]["agg"], prim["L"], prim["graph"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, ctx)
     ix = prim["wl"]["ix"]
     ids_primary = res["ids"]
     m_primary, D_primary, dtype_primary = ix.m, ix.D, ix.dtype

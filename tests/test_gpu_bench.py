@@ -75,3 +75,22 @@ def test_bench_shards_and_walker_legs_on_the_primary_engine(libbang):
     w = c["at_sift1b_shape_walker"]
     assert c["walker_qps"] > 0 and c["walker_N"] == 4000000 and w["ids_equal_pulled_run"] is True and w["result_properties_ok"] is True, w
     assert "walker threads read the 256-byte adjacency rows" in w["host_loop"]
+
+
+def test_bench_dump_outputs_are_the_same_from_run_to_run(libbang, tmp_path):
+    """--steps sets the number of timed steps, ms_per_step is their mean, and --dump-outputs writes what the last one returned: the same
+    arrays from two runs with the same arguments (seeded inputs), whose first 64 queries' ids are the oracle's."""
+    import numpy as np
+    base = [sys.executable, "bench.py", "--workload", "tiny", "--L", "46", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-legs",
+            "--no-live-traffic", "--dump-outputs"]
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run(base + [str(tmp_path / run)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and len(d["config"]["step_ms"]) == 3 and d["config"]["parity_vs_oracle_first_64"] is True
+        assert d["ms_per_step"] == pytest.approx(sum(d["config"]["step_ms"]) / 3, abs=0.02)
+        got.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("ids", "dists")})
+    a, b = got
+    assert a["ids"].dtype == np.float64 and a["ids"].shape == (1000, 10) and a["dists"].dtype == np.float32 and a["dists"].shape == (10, 1000)
+    assert np.array_equal(a["ids"], b["ids"]) and np.array_equal(a["dists"].view(np.uint32), b["dists"].view(np.uint32))

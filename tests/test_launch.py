@@ -1,6 +1,7 @@
 """bench.py --gpus N is the rank count (tools/bench_legs/launch.py): the checks that need no GPU, and the mechanics of the self-launch on a
 stand-in script (environment of the ranks, rank 0 owns stdout, status relay, a dead rank takes the others along)."""
 import os
+import re
 import subprocess
 import sys
 import textwrap
@@ -65,9 +66,10 @@ def test_self_launch_starts_n_ranks_with_their_environment(tmp_path):
     assert r.returncode == 0, r.stderr
     out = r.stdout.strip().splitlines()
     assert len(out) == 1 and out[0].startswith("rank 0 of 4 port ")          # rank 0 owns stdout ...
-    err = [l for l in r.stderr.splitlines() if l.startswith("rank ")]
-    assert sorted(l.split()[1] for l in err) == ["1", "2", "3"]               # ... the others' output goes to stderr
-    assert len({l.split()[-1] for l in err + out}) == 1                       # one rendezvous port for the job
+    # (the ranks share the one stderr pipe with whatever else writes to it: a line may follow another writer's text that lacks a newline)
+    err = re.findall(r"rank (\d+) of 4 port (\d+)\n", r.stderr)
+    assert sorted(rk for rk, _ in err) == ["1", "2", "3"], r.stderr[-3000:]   # ... the others' output goes to stderr
+    assert {p for _, p in err} == {out[0].split()[-1]}                        # one rendezvous port for the job
 
 
 def test_self_launch_relays_a_failing_rank_and_ends_the_others(tmp_path):
