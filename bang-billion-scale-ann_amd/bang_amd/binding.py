@@ -13,6 +13,7 @@ _LIB = os.environ.get("BANG_AMD_LIB") or os.path.join(_PKG, "lib", "libbang.so")
 U8, I8, F32 = 0, 1, 2
 DIST_L2, DIST_MIPS = 0, 1
 GRAPH_HOST, GRAPH_DEVICE, GRAPH_AUTO = 0, 1, 2
+DISTANCE_PQ, DISTANCE_EXACT = 0, 1       # option "distance": PQ distances + re-rank / exact distances, results from the worklist
 DTYPE_CODE = {"uint8": U8, "int8": I8, "float": F32}
 NP_DTYPE = {"uint8": np.uint8, "int8": np.int8, "float": np.float32}
 

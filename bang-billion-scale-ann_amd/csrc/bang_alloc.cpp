@@ -95,6 +95,28 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       e->pq_nhi = (w_rag > w_pad) ? e->pq_nhi_avail : 0;
     }
   }
+  // distance = 1: the exact-distance search kernel (bang_search_exact.hip) -- graph entries in HBM, self-paced, one launch per batch.  What it
+  // cannot run is refused: there is no PQ fallback
+  e->search_exact = false;
+  if (e->distance == 1) {
+    if (!dev_graph) {
+      bang_set_error("option distance = 1 (exact) needs the graph and vectors in HBM (graph = device; this index was placed in host RAM)");
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (e->search_opt == 0 || e->persistent == 0) {
+      bang_set_error("option distance = 1 (exact) runs on the query-resident search kernel only (search = %d, persistent = %d)", e->search_opt, e->persistent);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (e->distfn != BANG_DIST_L2) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
+    if (!bang_search_can_rerank(e->dtype, e->D, e->entry_len, 0)) {                 // (the layouts of the fused re-rank: the same arithmetic)
+      bang_set_error("option distance = 1 (exact): unsupported vector layout (dtype %d, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0 with D / 16 "
+                     "a power of two, float vectors D %% 4 == 0; D <= 256", e->dtype, e->D, (unsigned long long)e->entry_len);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    e->search_exact = true;
+    e->search_v2 = false;
+    e->pq_nhi = 0;
+  }
   // graph in host RAM: the host-paced form of the same kernel, where the walker can write device memory (BAR mode)
   e->search_host = false;
   if (!dev_graph && !e->search_v2 && persist_want && e->use_flag && e->stage_mode_eff == 2 && e->search_opt != 0 && e->psz != 0) {
@@ -194,7 +216,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   int nl = e->lanes_opt;
   if (nl <= 0) nl = dev_graph ? 1 : std::max(1, std::min(4, Q / 512));   // measured best on a 16-CPU-quota MI355X box
   nl = std::min(nl, Q);
-  if (e->search_v2 || e->search_host) nl = 1;            // the search kernel's waves are the unit of overlap, not lanes
+  if (e->search_v2 || e->search_host || e->search_exact) nl = 1;   // the search kernel's waves are the unit of overlap, not lanes
   if (e->search_host && e->threads_opt <= 0) e->threads_eff = std::max(1, std::min(12, usable_cpus() - 2));
   else if (e->threads_opt <= 0) e->threads_eff = (dev_graph || e->search_v2) ? 1 : std::max(1, std::min(4, (usable_cpus() - 2) / std::max(1, nl)));   // leave 2 CPUs for the caller + HIP runtime threads: a cgroup that exceeds its quota gets throttled for the rest of the period
   else e->threads_eff = e->threads_opt;
@@ -235,7 +257,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
         HIP_TRY(hipHostGetDevicePointer((void**)&ln.qmap_dev[b], ln.qmap_host[b], 0));
       }
     }
-    if (e->search_v2 || e->search_host) {
+    if (e->search_v2 || e->search_host || e->search_exact) {
       BANG_TRY(dmalloc(&ln.d_pcnt, 16));
       HIP_TRY(hipMemset(ln.d_pcnt, 0, 64));
     }
@@ -262,8 +284,8 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     else if (!dev_graph) fprintf(stderr, "[bang] walker threads not pinned\n");
   }
   if (env_flag("BANG_DEBUG"))
-    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d fp_direct=%d vec_on_device=%d\n", Q, nl,
-            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->fp_direct, (int)e->vec_on_device);
+    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d fp_direct=%d vec_on_device=%d\n", Q, nl,
+            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->fp_direct, (int)e->vec_on_device);
   start_threads(e);
   return BANG_OK;
 }

@@ -217,6 +217,8 @@ struct bang_engine {
                                        // -1 = auto (1 where the pivot table leaves LDS for at least 4 waves' worklists)
   bool search_v2 = false;              // resolved at bang_alloc: graph in HBM, self-paced form
   bool search_host = false;            // resolved at bang_alloc: graph in host RAM, the host-paced form of the same kernel (BAR mode)
+  int distance = 0;                    // option "distance": 0 = PQ distances + re-rank (BANG_Base), 1 = exact distances, results from the worklist
+  bool search_exact = false;           // resolved at bang_alloc: distance = 1 -- the exact-distance search kernel (bang_search_exact.hip)
   uint32_t sv_G = 0, sv_W = 0, sv_C = 1;   // its grid for the running query: workgroups, waves per workgroup, query contexts per wave
   uint32_t sv_GS = 8, sv_NG = 0;           // waves per pacing group; pacing groups = workgroups x groups per workgroup x contexts
   uint32_t* d_srows = nullptr;         // fine-grained device memory [groups*16][64]: adjacency ids per slot, written through the BAR

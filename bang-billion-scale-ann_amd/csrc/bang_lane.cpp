@@ -117,6 +117,9 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   // K6 + K7 inside the search launch (8-bit vectors, self-paced form): no launch behind it
   const bool fused_rerank = e->search_v2 && e->fuse_rerank != 0 && (dev_graph || e->vec_on_device) &&
                             bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : vb, dim_adjust) != 0;
+  // distance = 1: the exact-distance kernel writes the results itself, as the fused re-rank does (no launch behind it)
+  const bool results_in_launch = fused_rerank || e->search_exact;
+  if (e->search_exact && dim_adjust != 0) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
   const bool whole = ln.q0 == 0 && (int)ln.nq == Q && (int)ln.nq == e->Qcur;
   const size_t mailbox_max = (size_t)env_long("BANG_MAILBOX_BYTES", BANG_RESULT_MAILBOX_BYTES);
   uint64_t* d_ids_user = e->pool.d_ids_user;
@@ -125,12 +128,14 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   const bool mailbox = !to_device && whole && e->res_off_iters <= mailbox_max;
   // ... and with the re-rank fused into the search launch the kernel writes ids, distances, iteration counts and its abort word straight
   // into that pinned mirror (posted PCIe writes, a query at a time as the queries finish): nothing is copied behind the launch
-  const bool results_direct = mailbox && fused_rerank && e->h_results_dev != nullptr && env_long("BANG_RESULTS_DIRECT", 1) != 0;
+  const bool results_direct = mailbox && results_in_launch && e->h_results_dev != nullptr && env_long("BANG_RESULTS_DIRECT", 1) != 0;
   // queries H2D (:612) + K1 (:623)
   uint8_t* dq = (uint8_t*)e->d_queries + (size_t)ln.q0 * qbytes;
   LANE_HIP(hipMemcpyAsync(dq, (const uint8_t*)h_queries + (size_t)ln.q0 * qbytes, (size_t)ln.nq * qbytes,
                           hipMemcpyHostToDevice, ln.s_main));
-  if (e->psz)
+  if (e->search_exact) {
+    // (exact distances: the raw queries are all the kernel needs -- no centring, no K1)
+  } else if (e->psz)
     BANG_TRY(bang_k_center_queries(dq, e->dtype, e->d_centroid, e->d_chunk_off, (float*)p.d_qc, ln.nq, e->D, e->m,
                                    e->mp, e->psz, dim_adjust, ln.s_main));
   else
@@ -155,7 +160,37 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   uint32_t pw_stats[2] = {0, 0};
   uint32_t* h_abort = (uint32_t*)(e->h_results + e->res_bytes - BANG_MAX_LANES * 4) + ln.index;   // (one word per lane behind the results)
   *h_abort = 0;
-  if (e->search_v2) {
+  if (e->search_exact) {
+    // distance = 1: ONE launch of the exact-distance search kernel; it writes the results itself
+    LANE_HIP(hipMemsetAsync(ln.d_pcnt, 0, 64, ln.s_main));
+    bang_search_params sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.Q = ln.nq; sp.R = e->R; sp.m = e->m; sp.L = (uint32_t)e->L; sp.medoid = (uint32_t)e->medoid; sp.cap_iter = cap_iter;
+    sp.d_seed = e->d_seed; sp.d_graph = e->d_graph; sp.entry_len = e->entry_len; sp.vec_bytes = (uint32_t)vb;
+    sp.d_bloom = p.d_bloom; sp.d_cand_ids = p.d_cand_ids; sp.d_cand_cnt = p.d_cand_cnt; sp.d_qstats = p.d_qstats;
+    sp.d_qiters = e->d_qiters + ln.q0; sp.d_next_query = ln.d_pcnt; sp.d_abort = ln.d_pcnt + 1; sp.n_nodes = e->N;
+    sp.rr_queries = e->d_queries;
+    sp.rr_dtype = (uint32_t)e->dtype; sp.rr_D = e->D; sp.rr_k = (uint32_t)e->k; sp.rr_q0 = ln.q0; sp.rr_Q_total = (uint32_t)Q;
+    sp.rr_ids_out = e->d_ids_out; sp.rr_dists_out = e->d_dists_out;
+    if (to_device && whole) {                                         // bang_query_dev_e: straight into the caller's device buffers
+      sp.rr_ids_out = d_ids_user;
+      if (d_dists_user) sp.rr_dists_out = d_dists_user;
+    }
+    if (results_direct) {                                             // straight into the pinned mirror
+      sp.rr_ids_out = (uint64_t*)e->h_results_dev; sp.rr_dists_out = (float*)(e->h_results_dev + e->res_off_dists);
+      sp.d_qiters = (uint32_t*)(e->h_results_dev + e->res_off_iters) + ln.q0;
+      sp.d_abort = (uint32_t*)(e->h_results_dev + e->res_bytes - BANG_MAX_LANES * 4) + ln.index;
+    }
+    sp.d_ktime = ktime_slot(e, ln);
+    sp.max_wgs = (uint32_t)std::max(0L, env_long("BANG_SEARCH_MAX_WGS", 0));          // experiment / test knobs
+    sp.max_waves = (uint32_t)std::max(0L, env_long("BANG_SEARCH_MAX_WAVES", 0));
+    e->rerank_fused = false;
+    ENQ_BEGIN();
+    BANG_TRY(bang_k_search_exact(&sp, ln.s_main));
+    ENQ_END();
+    ++ln.front_launches;
+    iter = cap_iter;                                                         // refined from the per-query counts below
+  } else if (e->search_v2) {
     // graph resident in HBM: ONE launch of the query-resident search kernel; no host involvement until the re-rank
     LANE_HIP(hipMemsetAsync(ln.d_pcnt, 0, 64, ln.s_main));
     bang_search_params sp;
@@ -373,7 +408,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     LANE_HIP(hipEventRecord(ln.ev_fp, ln.s_fp));
     LANE_HIP(hipStreamWaitEvent(ln.s_main, ln.ev_fp, 0));
   }
-  if (!fused_rerank) {
+  if (!results_in_launch) {
     if (dev_graph)
       BANG_TRY(bang_k_rerank_range(e->d_graph, e->entry_len, e->d_medoid_vec, e->d_queries, e->dtype, e->d_cand_ids,
                                    nullptr, e->d_cand_cnt, e->cand_stride, ln.q0, ln.nq, (uint32_t)Q, e->D,
@@ -396,10 +431,10 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   // A copy into the caller's pageable arrays is staged by the runtime and costs ~20 us before the first byte moves, per copy.  The
   // results come back whole in ONE asynchronous copy into the pinned mirror and are handed out with memcpy (measured: 70 -> 17 us for
   // a 1 250-query shard, 92-107 -> 73-82 us for the 10 K batch); only a very large batch keeps the direct, runtime-pipelined copies.
-  if ((e->search_host || e->search_v2) && !results_direct) LANE_HIP(hipMemcpyAsync(h_abort, ln.d_pcnt + 1, 4, hipMemcpyDeviceToHost, ln.s_main));
-  const bool iters = e->search_v2 || e->search_host;
+  if ((e->search_host || e->search_v2 || e->search_exact) && !results_direct) LANE_HIP(hipMemcpyAsync(h_abort, ln.d_pcnt + 1, 4, hipMemcpyDeviceToHost, ln.s_main));
+  const bool iters = e->search_v2 || e->search_host || e->search_exact;
   if (to_device) {
-    const bool in_place = fused_rerank && whole;                // (the fused re-rank wrote into the caller's buffers)
+    const bool in_place = results_in_launch && whole;           // (the fused re-rank / the exact kernel wrote into the caller's buffers)
     if (!in_place)
       LANE_HIP(hipMemcpyAsync(d_ids_user + (size_t)ln.q0 * e->k, e->d_ids_out + (size_t)ln.q0 * e->k, (size_t)ln.nq * e->k * sizeof(uint64_t),
                               hipMemcpyDeviceToDevice, ln.s_main));

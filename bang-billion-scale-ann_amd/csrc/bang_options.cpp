@@ -51,6 +51,10 @@ static const OptionDef kOptions[] = {
      "host graph loaded in pull mode: 1 = the C++ walker threads serve the adjacency rows to the host-paced search kernel (the reference's data flow, "
      "bang_search.cu:771-813) -- reading the same 256-byte pull rows the kernel would pull itself, so no resident graph image is needed; 0 = the kernel pulls (default)"},
     {"search", "BANG_SEARCH", &bang_engine::search_opt, -1, 1, INT, BEFORE_ALLOC, "1 = the query-resident search kernel (bang_k_search), 0 = the per-iteration kernels, -1 = auto"},
+    {"distance", "BANG_DISTANCE", &bang_engine::distance, 0, 1, INT, BEFORE_ALLOC,
+     "0 = PQ distances in the walk + exact re-rank (default), 1 = exact distances in the walk, results = the first k worklist entries (no re-rank; "
+     "the reference's BANG_Exactdistance).  1 needs graph = device, search != 0, persistent != 0, L2 distance and the vector layouts of fuse_rerank: "
+     "8-bit D % 16 == 0 with D / 16 a power of two, float D % 4 == 0, D <= 256 (environment: pq | exact)"},
     {"stage_zero_copy", "BANG_STAGE_ZC", &bang_engine::stage_zero_copy, -1, 2, INT, BEFORE_ALLOC,
      "walker forms, where staged adjacency rows travel: 0 = H2D copy per iteration, 1 = kernels read mapped pinned memory, 2 = CPU stores through the PCIe BAR, -1 = auto"},
     {"numa", "BANG_NUMA", &bang_engine::numa_opt, -1, 1, INT, BEFORE_ALLOC, "1 = pin walker threads to the GPU's NUMA node, one physical core each; 0 / -1 = leave them to the scheduler"},
@@ -132,6 +136,8 @@ void apply_env_defaults(bang_engine* e) {
     long x;
     if (o.field == &bang_engine::graph_mode && !isdigit((unsigned char)*v) && *v != '-')
       x = strcmp(v, "device") == 0 ? BANG_GRAPH_DEVICE : strcmp(v, "auto") == 0 ? BANG_GRAPH_AUTO : BANG_GRAPH_HOST;
+    else if (o.field == &bang_engine::distance && !isdigit((unsigned char)*v) && *v != '-')
+      x = strcmp(v, "exact") == 0 ? 1 : 0;
     else
       x = atol(v);
     store(e, o, std::min(o.hi, std::max(o.lo, x)));

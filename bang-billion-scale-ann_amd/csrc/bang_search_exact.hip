@@ -1,0 +1,419 @@
+// bang_search_exact.hip -- the EXACT-DISTANCE search kernel (option distance = 1): the BANG_Base search loop of bang_search.hip with every
+// neighbour's distance the exact L2 against its full-precision vector instead of a PQ estimate (the reference's BANG_Exactdistance variant,
+// BANG_Exactdistance/parANN.cu:1139-1179), and the results the first k entries of the worklist as the loop leaves it (:1275) -- no re-rank.
+// DESIGN.md section 2 lists the two changes (CANON 10, 11); everything else -- filter, eager parent, merge, per-query activity, the L + 49 cap --
+// is the loop bang_search.hip runs, and the sort / merge / parent code is the same device code (bang_worklist.h, bang_device.h).
+//
+//  * Query-resident, self-paced: a wave owns one query from its first iteration to its last (worklist + survivors in LDS, the query in
+//    registers), then pulls the next unstarted query from *d_next_query.  Graph and vectors resident in HBM (d_graph = graph entries
+//    [vec][u32 degree][u32 id x R]); the vector of node x is the first D elements of its entry.
+//  * Distances.  8-bit vectors: G = D / 16 adjacent lanes per survivor, one 16-byte piece each, and the v_dot4 identity
+//    sum (a - b)^2 = sum a^2 - 2 sum a b + sum b^2 on integers below 2^24 -- exact, so its float image is what orc_exact_dist's ascending
+//    fmaf chain gives (the arithmetic of wave_rerank8).  Float vectors: one lane per survivor runs the ascending fmaf chain over its
+//    vector, four 16-byte loads in flight (the arithmetic of wave_rerank_f32).  The query sits in registers in both cases.
+//  * Filter (CANON 3): every id of the row is probed against the filter state at entry -- both words in one round trip, read past L1 --
+//    and only then are the survivors' bits set, with ATOMIC ORs into the query's private words.  The claim table of bang_search.hip
+//    (plain stores, same-word lanes merged in LDS) is an optimisation for a kernel whose iteration is bound by requests past L2; here an
+//    evaluation already costs 2-6 lines of vector, the atomics are one request per bit and need no LDS, and the next iteration's probes
+//    wait for them (s_waitcnt vmcnt(0) ahead of the probes, behind the adjacency row they need anyway).
+//  * No pivot table: LDS holds 2L + L/4 + 144 words per wave and the launch is bound by VGPRs.  bang_search_exact_geometry reads the
+//    instance's register count and gives every CU as many waves as its registers (512 per SIMD lane, allocated in granules of 8) and
+//    160 KB of LDS hold, at most 32; small batches are spread over all CUs.
+//  * An adjacency id >= n_nodes is never followed: the row counts as empty and *d_abort = 2 (the batch ends with an error).
+//
+// Reference line numbers: the reference's BANG_Base/bang_search.cu unless a file is named.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stddef.h>
+
+#include "bang_c.h"
+#include "bang_internal.h"
+#include "bang_device.h"
+#include "bang_worklist.h"
+
+#define EXACT_SCRATCH_WORDS 144u     // sd/ti [72] + td/compaction [72] (the survivors' distances, then the sort)
+#define EXACT_MAX_LDS (160u * 1024u)
+
+struct ExactArgs {
+  bang_search_params p;
+  uint32_t wave_words;               // LDS words per wave: worklist + scratch
+  uint32_t wl_words;                 // LDS words of the worklist (2L + ceil(L/4), rounded to 4)
+};
+
+static __host__ __device__ inline uint32_t exact_wl_words(uint32_t L) { return (2u * L + (L + 3u) / 4u + 3u) & ~3u; }
+
+template <bool SIGNED>
+__device__ __forceinline__ int xdot4(uint32_t a, uint32_t b, int c) {
+  if (SIGNED) return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
+  return (int)__builtin_amdgcn_udot4(a, b, (uint32_t)c, false);
+}
+
+// exact distances of the n survivors (ids in LDS: sid[0, n)) -> dist[0, n) in LDS, 8-bit vectors.  qw: this lane's 16-byte piece of the
+// query (piece lane % G), qq: the sum of its squares.  Every lane of the wave executes (the G lanes of a survivor reduce by xor-shuffles).
+template <bool SIGNED>
+__device__ __forceinline__ void exact_dist8(const uint8_t GAS* graph, uint64_t entry_len, uint32_t G, const uint32_t* sid, uint32_t n,
+                                            float* dist, u32x4a qw, int qq, int lane) {
+  constexpr int U = 4;                                            // vector fetches in flight per lane
+  const uint32_t per = 64u / G;                                   // survivors per wave instruction
+  const uint32_t sub = (uint32_t)lane & (G - 1u), slot = (uint32_t)lane / G;
+  for (uint32_t i0 = 0; i0 < n; i0 += per * U) {                  // (uniform)
+    u32x4a v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t i = i0 + (uint32_t)u * per + slot;
+      const uint32_t id = sid[i < n ? i : 0u];
+      v[u] = *(const u32x4a GAS*)(graph + (uint64_t)id * entry_len + 16u * sub);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t i = i0 + (uint32_t)u * per + slot;
+      int vv = xdot4<SIGNED>(v[u].x, v[u].x, xdot4<SIGNED>(v[u].y, v[u].y, xdot4<SIGNED>(v[u].z, v[u].z, xdot4<SIGNED>(v[u].w, v[u].w, qq))));
+      const int vq = xdot4<SIGNED>(v[u].x, qw.x, xdot4<SIGNED>(v[u].y, qw.y, xdot4<SIGNED>(v[u].z, qw.z, xdot4<SIGNED>(v[u].w, qw.w, 0))));
+      vv -= 2 * vq;
+      for (uint32_t off = 1; off < G; off <<= 1) vv += __shfl_xor(vv, (int)off);
+      if (i < n && sub == 0u) dist[i] = (float)vv;
+    }
+  }
+}
+
+// the same for float vectors: lane i evaluates survivor i0 + i, the ascending fmaf chain over the D dimensions (D % 4 == 0, <= 256);
+// qr[t]: lane l holds query element 64 t + l, read with v_readlane (the dimension index is uniform)
+__device__ __forceinline__ void exact_dist_f32(const uint8_t GAS* graph, uint64_t entry_len, uint32_t D, const uint32_t* sid, uint32_t n,
+                                               float* dist, const float (&qr)[4], int lane) {
+  constexpr int RF = 4;                                           // 16-byte loads in flight per lane
+  for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform)
+    const uint32_t i = i0 + (uint32_t)lane;
+    const uint32_t id = sid[i < n ? i : 0u];
+    const uint8_t GAS* v = graph + (uint64_t)id * entry_len;
+    float acc = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t jt = (uint32_t)t * 64u;
+      if (jt >= D) break;                                         // (uniform)
+      const uint32_t dt = D - jt < 64u ? D - jt : 64u;
+      for (uint32_t jl = 0; jl < dt; jl += 4u * RF) {             // (uniform)
+        u32x4a w[RF];
+#pragma unroll
+        for (int u = 0; u < RF; ++u) {
+          const uint32_t j = jl + 4u * (uint32_t)u;
+          w[u] = *(const u32x4a GAS*)(v + 4u * (jt + (j < dt ? j : 0u)));
+        }
+#pragma unroll
+        for (int u = 0; u < RF; ++u) {
+          const uint32_t j = jl + 4u * (uint32_t)u;
+          if (j < dt) {                                           // (uniform)
+            const uint32_t ww[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+              const float qv = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qr[t]), (int)(j + (uint32_t)d)));
+              const float diff = __uint_as_float(ww[d]) - qv;     // parANN.cu:1139-1179 / orc_exact_dist: vector - query
+              acc = __builtin_fmaf(diff, diff, acc);              // ascending dimension
+            }
+          }
+        }
+      }
+    }
+    if (i < n) dist[i] = acc;
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(1024) void search_exact_kernel(const ExactArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t xlds[];
+  const bang_search_params& p = a.p;
+  const int lane = lane_id();
+  const uint32_t wave = uni(threadIdx.x >> 6);
+  const uint32_t nwaves = blockDim.x >> 6;
+  const uint32_t L = p.L, medoid = p.medoid, cap_iter = p.cap_iter, R = p.R, n_nodes = p.n_nodes;
+  const uint32_t cand_stride = L + BANG_EXTRA_ITERS;
+  const uint8_t GAS* graph = (const uint8_t GAS*)p.d_graph;
+  const uint64_t entry_len = p.entry_len;
+  uint32_t* wbase = xlds + (size_t)wave * a.wave_words;
+  uint32_t* scratch = wbase + a.wl_words;
+  WaveLds s;
+  s.wd = (float*)wbase; s.wi = wbase + L; s.wv = (uint8_t*)(wbase + 2 * L);
+  s.sd = (float*)scratch; s.ti = scratch; s.td = (float*)(scratch + 72);
+  float* sdist = (float*)scratch;                 // the survivors' distances (dead before the sort writes sd)
+  uint32_t* sc = scratch + 72;                    // the survivors' ids, in input order (== td: dead before the sort)
+  if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+  const uint32_t total_waves = gridDim.x * nwaves;
+  const uint32_t gw = blockIdx.x * nwaves + wave;
+
+  for (bool first_q = true;; first_q = false) {
+    // ---------------- the next query: the first one by position, then from the hand-out counter
+    uint32_t q;
+    if (first_q) q = gw;
+    else {
+      uint32_t t = 0;
+      if (lane == 0) t = __hip_atomic_fetch_add(p.d_next_query, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      q = total_waves + uni(t);
+    }
+    if (q >= p.Q) break;
+    const size_t qabs = (size_t)p.rr_q0 + q;
+    uint32_t GAS* bloom = (uint32_t GAS*)p.d_bloom + (size_t)q * BANG_BF_WORDS;
+
+    // the raw query, in registers
+    const uint32_t D = p.rr_D;
+    u32x4a qw = {0u, 0u, 0u, 0u};
+    int qq = 0;
+    uint32_t G = 1;
+    float qr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (DT == BANG_F32) {
+      const float GAS* qsrc = (const float GAS*)p.rr_queries + qabs * D;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { const uint32_t j = (uint32_t)t * 64u + (uint32_t)lane; qr[t] = qsrc[j < D ? j : 0u]; }
+    } else {
+      G = D >> 4;
+      qw = *(const u32x4a GAS*)((const uint8_t GAS*)p.rr_queries + qabs * D + 16u * ((uint32_t)lane & (G - 1u)));
+      qq = xdot4<DT == BANG_I8>(qw.x, qw.x, xdot4<DT == BANG_I8>(qw.y, qw.y, xdot4<DT == BANG_I8>(qw.z, qw.z, xdot4<DT == BANG_I8>(qw.w, qw.w, 0))));
+    }
+
+    // ---------------- per-query state (bang_init :440-489): candidate log = [MEDOID], seed list [MEDOID, adj(MEDOID)...]
+    uint32_t iter = 1, w_n = 0, cc = 1, mark = 0x01010101u, evals = 0, fetched = 0;
+    WlHead head;
+    head.found = false; head.idx = 0; head.id = 0; head.d = 0.0f; head.tail = 0.0f;
+    if (lane == 0) p.d_cand_ids[(size_t)q * cand_stride] = medoid;
+    uint32_t cnt_in = p.d_seed[0], x0 = p.d_seed[1 + lane], x1 = p.d_seed[65];
+    bool have_row = true;
+
+    for (;;) {
+      const bool first = (iter == 1);
+      // ---------------- K5: filter (neighbor_filtering_new :1140-1165) ----------------
+      uint32_t ci = have_row ? uni(cnt_in) : 0u;
+      {
+        const uint32_t cap = R + (first ? 1u : 0u);
+        if (ci > cap) ci = cap;
+      }
+      if (n_nodes != 0u && (__ballot((uint32_t)lane < ci && x0 >= n_nodes) != 0ull || (ci > 64u && uni(x1) >= n_nodes))) {
+        if (lane == 0 && p.d_abort) *p.d_abort = 2u;
+        ci = 0;
+      }
+      fetched += ci;
+      const bool v0 = (uint32_t)lane < ci;
+      const bool v1 = ci > 64;                                    // the 65th id exists in the seed list only (uniform)
+      const uint32_t h0a = hash1(x0), h0b = hash2(x0);
+      uint32_t h1a = 0, h1b = 0, w0a = 0, w0b = 0, w1a = 0, w1b = 0;
+      // CANON 3: every id is tested against the filter state at entry; the previous iteration's atomic ORs have completed
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (v0) { w0a = ld_bypass_l1(&bloom[h0a >> 5]); w0b = ld_bypass_l1(&bloom[h0b >> 5]); }
+      if (v1) {
+        h1a = hash1(x1); h1b = hash2(x1);
+        if (lane == 0) { w1a = ld_bypass_l1(&bloom[h1a >> 5]); w1b = ld_bypass_l1(&bloom[h1b >> 5]); }
+      }
+      const bool pass0 = v0 && !(((w0a >> (h0a & 31)) & 1u) && ((w0b >> (h0b & 31)) & 1u));
+      const bool pass1 = v1 && (lane == 0) && !(((w1a >> (h1a & 31)) & 1u) && ((w1b >> (h1b & 31)) & 1u));
+      const uint64_t m0 = __ballot(pass0);
+      const uint64_t m1 = __ballot(pass1);
+      const uint32_t n0 = (uint32_t)__popcll(m0);
+      const uint32_t n = n0 + (uint32_t)__popcll(m1);
+      // ... then every survivor's two bits are set (:1159-1160)
+      if (pass0) {
+        (void)__hip_atomic_fetch_or(&bloom[h0a >> 5], 1u << (h0a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_or(&bloom[h0b >> 5], 1u << (h0b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (pass1) {
+        (void)__hip_atomic_fetch_or(&bloom[h1a >> 5], 1u << (h1a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_or(&bloom[h1b >> 5], 1u << (h1b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      // ordered compaction through LDS: survivors keep input order (CANON; the reference emits in atomicAdd order :1161)
+      if (pass0) sc[lanes_below(m0)] = x0;
+      if (pass1) sc[n0] = x1;
+      wave_sync();
+      const uint32_t sid0 = ((uint32_t)lane < n) ? sc[lane] : 0u;
+      const uint32_t sid1 = (lane == 0 && n > 64) ? sc[64] : 0u;
+      evals += n;
+
+      // ---------------- exact distances (CANON 10: replaces K2) ----------------
+      if (n > 0) {
+        if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, sc, n, sdist, qr, lane);
+        else exact_dist8<DT == BANG_I8>(graph, entry_len, G, sc, n, sdist, qw, qq, lane);
+      }
+      wave_sync();
+      const float d0 = ((uint32_t)lane < n) ? sdist[lane] : BIG_DIST;
+      const float d1 = (lane == 0 && n > 64) ? sdist[64] : BIG_DIST;
+      wave_sync();
+
+      // ---------------- K4: parent (compute_parent1 :1464-1521 / compute_parent2 :1384-1459), as bang_search.hip ----------------
+      uint32_t parent = 0;
+      bool found = false;
+      {
+        const bool elig = (uint32_t)lane < n && sid0 != medoid && d0 < BIG_DIST;
+        // (squared distances are non-negative: their bit patterns order like the floats; {bits, lane}: first minimum wins)
+        uint32_t khi = elig ? __float_as_uint(d0) : 0xFFFFFFFFu, klo = (uint32_t)lane;
+        wave_min_key(khi, klo);
+        uint32_t bi = (khi != 0xFFFFFFFFu) ? klo : 0xFFFFu;
+        float bd = (khi != 0xFFFFFFFFu) ? __uint_as_float(khi) : BIG_DIST;
+        uint32_t bid = (uint32_t)__builtin_amdgcn_readlane((int)sid0, (int)(klo & 63u));
+        if (n > 64) {                                             // element 64 can only win with a strictly smaller distance
+          const float e_d = __shfl(d1, 0);
+          const uint32_t e_id = (uint32_t)__shfl((int)sid1, 0);
+          if (e_id != medoid && e_d < BIG_DIST && (bi == 0xFFFFu || e_d < bd)) { bd = e_d; bi = 64; bid = e_id; }
+        }
+        const bool have_best = (bi != 0xFFFFu);
+        if (!have_best) bd = BIG_DIST;
+        bool from_best = false;
+        if (first) {
+          if (have_best) { found = true; parent = bid; from_best = true; }
+        } else {
+          if (head.found) {                                       // first unvisited entry :1425-1439
+            found = true;
+            if (bd < head.d) { parent = bid; from_best = true; }
+            else { parent = head.id; if (lane == 0) s.wv[head.idx] = 1; }
+          } else if (w_n > 0) {                                   // corner case :1442-1446
+            if (bd < head.tail) { found = true; parent = bid; from_best = true; }
+          }
+        }
+        parent = uni(parent);
+        if (found) {
+          if (from_best) mark = parent;
+          ++cc;
+        }
+      }
+
+      // ---------------- hand the parent over: its adjacency row is requested now and travels during the sort/merge
+      const bool want_row = found && iter < cap_iter;
+      if (want_row) {
+        const uint32_t GAS* nrow = (const uint32_t GAS*)(graph + (uint64_t)parent * entry_len + p.vec_bytes);
+        cnt_in = nrow[0];
+        x0 = nrow[1 + ((uint32_t)lane < R ? (uint32_t)lane : 0u)];
+      }
+      if (found && lane == 0) p.d_cand_ids[(size_t)q * cand_stride + cc - 1u] = parent;      // :1451-1458
+
+      // ---------------- K3a + K3b: sort the survivors, merge them into the worklist (not at the cap: CANON 6) ----------------
+      if (n > 0 && iter < cap_iter) w_n = sort_and_merge(s, n, d0, sid0, d1, sid1, iter, w_n, L, medoid, mark, head.tail, lane);
+
+      // a query is active while it has a parent or unmerged survivors (CANON 4); the loop ends at the cap (:950-956)
+      if ((!found && n == 0) || iter == cap_iter) break;
+      ++iter;
+      have_row = found;
+      head = worklist_head(s, w_n, lane);
+    }
+
+    // ---------------- the query is finished: counters, then the results straight from the worklist (CANON 11: replaces K6 + K7)
+    if (lane == 0) {
+      p.d_cand_cnt[q] = cc;
+      if (p.d_qstats) { p.d_qstats[(size_t)q * 2] = evals; p.d_qstats[(size_t)q * 2 + 1] = fetched; }
+      if (p.d_qiters) p.d_qiters[q] = iter;
+    }
+    const uint32_t k = p.rr_k, Qt = p.rr_Q_total;
+    uint64_t GAS* ids_out = (uint64_t GAS*)p.rr_ids_out;
+    float GAS* dists_out = (float GAS*)p.rr_dists_out;
+    for (uint32_t r = (uint32_t)lane; r < k; r += WAVE) {
+      const bool have = r < w_n;                                  // a short worklist is padded (CANON 8)
+      ids_out[qabs * k + r] = have ? (uint64_t)s.wi[r] : ~0ull;                     // [Q][k] u64
+      dists_out[(size_t)r * Qt + qabs] = have ? s.wd[r] : BIG_DIST;                 // [rank][Q]
+    }
+    wave_sync();                                                  // (the worklist is read before the next query overwrites it)
+  }
+  if (p.d_ktime) {
+    __syncthreads();
+    if (threadIdx.x == 0) p.d_ktime[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// launcher
+// ---------------------------------------------------------------------------------------------------------------------
+static const void* exact_instance(int dtype) {
+  if (dtype == BANG_U8) return (const void*)search_exact_kernel<BANG_U8>;
+  if (dtype == BANG_I8) return (const void*)search_exact_kernel<BANG_I8>;
+  if (dtype == BANG_F32) return (const void*)search_exact_kernel<BANG_F32>;
+  return nullptr;
+}
+
+static uint32_t exact_wave_bytes(uint32_t L) { return (exact_wl_words(L) + EXACT_SCRATCH_WORDS) * 4u; }
+
+// Vector layouts the kernel evaluates: those of the fused re-rank (bang_search_can_rerank) -- 8-bit: D % 16 == 0, D / 16 a power of two;
+// float: D % 4 == 0; D <= 256; a 4-byte-aligned entry stride; no MIPS padding.
+static int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry_len, uint32_t L) {
+  if (L == 0 || L > BANG_MAX_L) return 0;
+  return bang_search_can_rerank(dtype, D, entry_len, 0);
+}
+
+// Waves per CU: what the instance's registers allow (512 per SIMD lane, allocated in granules of 8, four SIMDs, at most 8 waves per SIMD),
+// what 160 KB of LDS hold (2L + L/4 + 144 words per wave), at most 32.  The three instances compile to 97-98 VGPRs and no scratch (the merge
+// of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves per SIMD, 16 per CU -- one workgroup of
+// 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  A batch of fewer than 16 queries per CU is spread over all CUs with fewer
+// waves each (a wave's iteration is latency bound, as in bang_search_geometry).
+extern "C" int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups,
+                                          uint32_t* waves) {
+  if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
+  const void* k = exact_instance(dtype);
+  if (!k || L == 0 || L > BANG_MAX_L) { bang_set_error("distance = 1: bad dtype / L"); return BANG_ERR_ARG; }
+  static int regs[3][BANG_MAX_DEVICES] = {};                     // per instance and device, read once
+  const int dev = current_device();
+  if (regs[dtype][dev] == 0) {
+    hipFuncAttributes at;
+    HIP_TRY(hipFuncGetAttributes(&at, k));
+    regs[dtype][dev] = at.numRegs > 0 ? at.numRegs : 128;
+  }
+  const uint32_t vg = (uint32_t)regs[dtype][dev];
+  const uint32_t alloc = (vg + 7u) & ~7u;
+  uint32_t per_simd = 512u / alloc;
+  if (per_simd > 8u) per_simd = 8u;
+  uint32_t per_cu = 4u * per_simd;
+  const uint32_t by_lds = EXACT_MAX_LDS / exact_wave_bytes(L);
+  if (by_lds < per_cu) per_cu = by_lds;
+  if (per_cu > 32u) per_cu = 32u;
+  if (per_cu == 0) { bang_set_error("distance = 1: one wave's worklist does not fit LDS at L=%u", L); return BANG_ERR_UNSUPPORTED; }
+  uint32_t W = per_cu < 16u ? per_cu : 16u;
+  const uint32_t wgs_per_cu = per_cu / W;
+  if (max_waves && max_waves < W) W = max_waves;
+  const uint32_t cus = (uint32_t)num_cus();
+  uint32_t grid_n;
+  if (Q <= cus * W) {                                             // fewer queries than a wave-full per CU: all CUs, fewer waves each
+    grid_n = Q < cus ? Q : cus;
+    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
+    const uint32_t share = (Q + grid_n - 1) / grid_n;
+    if (share < W) W = share;
+  } else {
+    const uint32_t want = (Q + W - 1) / W;
+    grid_n = cus * wgs_per_cu;
+    if (want < grid_n) grid_n = want;
+    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
+  }
+  *workgroups = grid_n;
+  *waves = W;
+  return BANG_OK;
+}
+
+extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (p->Q == 0) return BANG_OK;
+  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("distance = 1: bad R/L"); return BANG_ERR_ARG; }
+  if (!p->d_graph || p->row_layout != 0) { bang_set_error("distance = 1: the exact-distance kernel needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
+  if (!p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt || !p->d_next_query || !p->rr_queries || !p->rr_ids_out || !p->rr_dists_out) {
+    bang_set_error("distance = 1: null buffer"); return BANG_ERR_ARG;
+  }
+  if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("distance = 1: bad iteration cap"); return BANG_ERR_ARG; }
+  if (p->rr_k == 0 || p->rr_k > p->L || p->rr_Q_total < p->rr_q0 + p->Q) { bang_set_error("distance = 1: bad k / result rows"); return BANG_ERR_ARG; }
+  if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len, p->L) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
+      (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
+    bang_set_error("distance = 1: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0 with D / 16 a power "
+                   "of two, float vectors D %% 4 == 0; D <= 256", p->rr_dtype, p->rr_D, (unsigned long long)p->entry_len);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  uint32_t grid_n = 0, waves = 0;
+  const int rc = bang_search_exact_geometry((int)p->rr_dtype, p->L, p->Q, p->max_wgs, p->max_waves, &grid_n, &waves);
+  if (rc != BANG_OK) return rc;
+  ExactArgs a;
+  a.p = *p;
+  a.wl_words = exact_wl_words(p->L);
+  a.wave_words = a.wl_words + EXACT_SCRATCH_WORDS;
+  const size_t lds = (size_t)waves * a.wave_words * 4u;
+  const void* k = exact_instance((int)p->rr_dtype);
+  static bool attr_done[3][BANG_MAX_DEVICES] = {};
+  const int dev = current_device();
+  if (!attr_done[p->rr_dtype][dev]) {
+    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_MAX_LDS));
+    attr_done[p->rr_dtype][dev] = true;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(grid_n), block(waves * WAVE);
+  if (p->rr_dtype == BANG_F32) hipLaunchKernelGGL(search_exact_kernel<BANG_F32>, grid, block, lds, st, a);
+  else if (p->rr_dtype == BANG_I8) hipLaunchKernelGGL(search_exact_kernel<BANG_I8>, grid, block, lds, st, a);
+  else hipLaunchKernelGGL(search_exact_kernel<BANG_U8>, grid, block, lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return BANG_OK;
+}

@@ -440,6 +440,20 @@ int bang_k_rerank(const void* d_vec_base, uint64_t vec_stride, const void* d_med
                   uint32_t cand_stride, uint32_t Q, uint32_t D, uint32_t k, uint32_t dim_adjust,
                   uint64_t* d_ids_out, float* d_dists_out, void* stream);
 
+/* EXACT-DISTANCE search kernel (csrc/bang_search_exact.hip; engine option "distance" = 1; the reference's BANG_Exactdistance,
+ * BANG_Exactdistance/parANN.cu:1139-1179, :1275): the loop of bang_k_search with every neighbour's distance the exact L2 against its full-precision
+ * vector -- the first vec_bytes of its graph entry in d_graph (row_layout 0; graph in HBM only) -- and no re-rank: each query's results are the
+ * first min(k, worklist length) worklist entries when its loop ends (padded with UINT64_MAX / 3.402823E+38f), written to rr_ids_out [rr_Q_total][k]
+ * (u64) / rr_dists_out [k][rr_Q_total] at row rr_q0 + q.  Uses Q, R, L, medoid, cap_iter, max_wgs, max_waves, d_seed, d_graph, entry_len,
+ * vec_bytes, d_bloom (zeroed), d_cand_ids / d_cand_cnt (the expanded nodes, [0] = MEDOID), d_qstats, d_qiters, d_next_query (zeroed), d_abort,
+ * d_ktime, n_nodes and rr_queries (raw queries), rr_dtype, rr_D, rr_k, rr_q0, rr_Q_total, rr_ids_out, rr_dists_out; the PQ fields and rr_vec_* are
+ * ignored.  Vector layouts: those of the fused re-rank (bang_search_can_rerank with rr_vec_stride = entry_len); others are BANG_ERR_UNSUPPORTED. */
+int bang_k_search_exact(const bang_search_params* p, void* stream);
+/* grid of a bang_k_search_exact launch over Q queries for vectors of dtype at worklist length L: workgroups and waves per workgroup (as many
+ * waves per CU as the instance's registers and LDS allow, <= 16 per workgroup; max_wgs / max_waves: caps if nonzero; a batch of fewer than a
+ * workgroup-full of queries per CU is spread over all CUs) */
+int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+
 #ifdef __cplusplus
 }
 #endif
