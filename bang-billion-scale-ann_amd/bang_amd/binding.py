@@ -14,6 +14,7 @@ U8, I8, F32 = 0, 1, 2
 DIST_L2, DIST_MIPS = 0, 1
 GRAPH_HOST, GRAPH_DEVICE, GRAPH_AUTO = 0, 1, 2
 DISTANCE_PQ, DISTANCE_EXACT = 0, 1       # option "distance": PQ distances + re-rank / exact distances, results from the worklist
+SEMANTICS_BASE, SEMANTICS_INMEMORY = 0, 1   # option "semantics": the walk of BANG_Base / of BANG_Inmemory (parent after the merge, cap L + 119)
 DTYPE_CODE = {"uint8": U8, "int8": I8, "float": F32}
 NP_DTYPE = {"uint8": np.uint8, "int8": np.int8, "float": np.float32}
 
@@ -325,9 +326,10 @@ class Engine:
         _check(lib().bang_get_query_counters(self._h, _vp(cols[2]), _vp(cols[3]), _vp(cols[1]), _vp(cols[0])), "bang_get_query_counters")
         return np.stack(cols, axis=1).astype(np.int64)
 
-    def candidate_log(self, Q: int, L: int):
-        """(ids [Q][L + 50] u32, counts [Q]): the nodes every query of the last batch expanded, in expansion order."""
-        ids = np.zeros((Q, L + EXTRA_ITERS), np.uint32)
+    def candidate_log(self, Q: int, L: int, extra: int = EXTRA_ITERS):
+        """(ids [Q][L + extra] u32, counts [Q]): the nodes every query of the last batch expanded, in expansion order.
+        extra: 50, or 120 under option semantics = 1 (its candidate log has L + 120 entries)."""
+        ids = np.zeros((Q, L + extra), np.uint32)
         cnt = np.zeros(Q, np.uint32)
         _check(lib().bang_get_candidate_log(self._h, _vp(ids), C.c_uint32(ids.shape[1]), _vp(cnt), C.c_uint32(Q)), "bang_get_candidate_log")
         return ids, cnt

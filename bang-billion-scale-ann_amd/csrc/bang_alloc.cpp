@@ -53,7 +53,7 @@ void free_batch(bang_engine* e) {
 
 int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validated the pull rows)
   const size_t L = (size_t)e->L, nq = (size_t)Q;
-  const size_t rows = L + BANG_EXTRA_ITERS;                                  // uMAX_PARENTS_PERQUERY :370
+  const size_t rows = L + (e->semantics == 1 ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS);   // uMAX_PARENTS_PERQUERY :370 (BANG_Inmemory/parANN.cu:30)
   const size_t vb = vec_bytes(e);
   const bool dev_graph = (e->graph_mode == BANG_GRAPH_DEVICE);
   const size_t slots_cap = std::max<size_t>(nq, 8 * 16 * KT_WGS);   // rows / parent words: one per query, or one per context slot of the search kernel
@@ -116,6 +116,32 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     e->search_exact = true;
     e->search_v2 = false;
     e->pq_nhi = 0;
+  }
+  // semantics = 1: the BANG_Inmemory walk on the self-paced search kernel (bang_k_search_inmem).  What it cannot run is refused: there is no
+  // fallback to the BANG_Base walk
+  e->search_inmem = false;
+  if (e->semantics == 1) {
+    if (!dev_graph) {
+      bang_set_error("option semantics = 1 (inmemory) needs the graph and vectors in HBM (graph = device; this index was placed in host RAM)");
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (e->search_opt == 0 || e->persistent == 0) {
+      bang_set_error("option semantics = 1 (inmemory) runs on the query-resident search kernel only (search = %d, persistent = %d)", e->search_opt, e->persistent);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (e->distance != 0) { bang_set_error("option semantics = 1 (inmemory) is not available with distance = 1 (exact)"); return BANG_ERR_UNSUPPORTED; }
+    if (e->distfn != BANG_DIST_L2) { bang_set_error("option semantics = 1 (inmemory) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
+    if (e->psz == 0) { bang_set_error("option semantics = 1 (inmemory) needs the LDS-resident pivot table (the LUT path, pq = 1, has no such kernel)"); return BANG_ERR_UNSUPPORTED; }
+    if (!e->search_v2) {
+      bang_set_error("option semantics = 1 (inmemory): the pivot table and one wave's worklist do not fit LDS at L = %d", e->L);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (!bang_search_inmem_has_instance(e->psz, e->mp, e->code_stride ? e->code_stride : e->m)) {
+      bang_set_error("option semantics = 1 (inmemory): no kernel instance for %u-chunk code rows that are not dword-aligned (code stride %u; option code_stride "
+                     "can pad them)", e->mp, e->code_stride ? e->code_stride : e->m);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    e->search_inmem = true;
   }
   // graph in host RAM: the host-paced form of the same kernel, where the walker can write device memory (BAR mode)
   e->search_host = false;
@@ -284,8 +310,8 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     else if (!dev_graph) fprintf(stderr, "[bang] walker threads not pinned\n");
   }
   if (env_flag("BANG_DEBUG"))
-    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d fp_direct=%d vec_on_device=%d\n", Q, nl,
-            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->fp_direct, (int)e->vec_on_device);
+    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d semantics=%d fp_direct=%d vec_on_device=%d\n", Q, nl,
+            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->search_inmem, (int)e->fp_direct, (int)e->vec_on_device);
   start_threads(e);
   return BANG_OK;
 }

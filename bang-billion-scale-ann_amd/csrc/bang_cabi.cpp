@@ -161,7 +161,7 @@ extern "C" int bang_alloc_e(bang_engine_t* e, int Q) {
   BANG_TRY(ensure_device(e));
   e->Qcap = Q;
   e->Qcur = 0;
-  e->cand_stride = (uint32_t)e->L + BANG_EXTRA_ITERS;
+  e->cand_stride = (uint32_t)e->L + (e->semantics == 1 ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS);     // (semantics = 1: L + 120)
   BANG_TRY(validate_pull_rows(e));       // a truncated / overwritten rows file is reported as such -- and never costs the HBM row cache below
   if (e->n_slices > 1) {                 // peer rows: the slice table (biased base addresses: own HBM, peers' HBM) goes to the device
     if (!e->d_slice_tab) BANG_TRY(dmalloc(&e->d_slice_tab, (size_t)BANG_MAX_ROW_SLICES));
@@ -406,7 +406,10 @@ extern "C" int bang_get_query_counters(bang_engine_t* e, uint32_t* dist_evals, u
 extern "C" int bang_get_candidate_log(bang_engine_t* e, uint32_t* ids, uint32_t stride, uint32_t* counts, uint32_t num_queries) {
   if (!e || !ids || !counts) return BANG_ERR_ARG;
   if (!e->allocated || e->Qcur <= 0) { bang_set_error("bang_get_candidate_log: no query has run on this allocation"); return BANG_ERR_ARG; }
-  if (stride < e->cand_stride) { bang_set_error("bang_get_candidate_log: stride %u < %u (L + 50)", stride, e->cand_stride); return BANG_ERR_ARG; }
+  if (stride < e->cand_stride) {
+    bang_set_error("bang_get_candidate_log: stride %u < %u (L + %d)", stride, e->cand_stride, e->search_inmem ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS);
+    return BANG_ERR_ARG;
+  }
   if (num_queries < (uint32_t)e->Qcur) { bang_set_error("bang_get_candidate_log: buffers hold %u queries, the last batch had %d", num_queries, e->Qcur); return BANG_ERR_ARG; }
   const size_t Q = (size_t)e->Qcur;
   HIP_TRY(hipMemcpy(counts, e->d_cand_cnt, Q * 4, hipMemcpyDeviceToHost));

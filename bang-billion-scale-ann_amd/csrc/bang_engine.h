@@ -219,6 +219,8 @@ struct bang_engine {
   bool search_host = false;            // resolved at bang_alloc: graph in host RAM, the host-paced form of the same kernel (BAR mode)
   int distance = 0;                    // option "distance": 0 = PQ distances + re-rank (BANG_Base), 1 = exact distances, results from the worklist
   bool search_exact = false;           // resolved at bang_alloc: distance = 1 -- the exact-distance search kernel (bang_search_exact.hip)
+  int semantics = 0;                   // option "semantics": 0 = BANG_Base's walk (default), 1 = BANG_Inmemory's (parent after the merge, cap L + 119)
+  bool search_inmem = false;           // resolved at bang_alloc: semantics = 1 -- search_v2 on bang_k_search_inmem; candidate log L + 120
   uint32_t sv_G = 0, sv_W = 0, sv_C = 1;   // its grid for the running query: workgroups, waves per workgroup, query contexts per wave
   uint32_t sv_GS = 8, sv_NG = 0;           // waves per pacing group; pacing groups = workgroups x groups per workgroup x contexts
   uint32_t* d_srows = nullptr;         // fine-grained device memory [groups*16][64]: adjacency ids per slot, written through the BAR
@@ -286,6 +288,9 @@ struct bang_engine {
   int walker_stall_ms = 0;             // test hook: the walker team sleeps this long at the start of the next host-paced query (one shot)
   bang_stats stats{};
 };
+
+// bang_search.hip, part 2 (semantics = 1): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride
+extern "C" int bang_search_inmem_has_instance(uint32_t psz, uint32_t mp, uint32_t code_stride);
 
 namespace bang {
 

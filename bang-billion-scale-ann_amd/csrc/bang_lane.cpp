@@ -76,7 +76,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   const size_t qdim = e->D - dim_adjust;
   const size_t qbytes = qdim * e->tsize;
   const size_t vb = vec_bytes(e);
-  const uint32_t cap_iter = (uint32_t)e->L + BANG_EXTRA_ITERS - 1;          // :950
+  const uint32_t cap_iter = (uint32_t)e->L + (e->search_inmem ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS) - 1;   // :950 (semantics = 1: L + 119)
   if (ln.kt_used) { (void)hipMemset(ln.d_ktime, 0, ln.kt_used * KT_WGS * 16); ln.kt_used = 0; }   // stats not collected
   if (e->h_fin.size() >= (size_t)ln.q0 + ln.nq) memset(e->h_fin.data() + ln.q0, 0, ln.nq);
   ln.h2d_bytes.store(0); ln.iterations = 0; ln.front_launches = 0; ln.walker_ms = 0; ln.sync_ms = 0; ln.enqueue_ms = 0;
@@ -119,6 +119,12 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
                             bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : vb, dim_adjust) != 0;
   // distance = 1: the exact-distance kernel writes the results itself, as the fused re-rank does (no launch behind it)
   const bool results_in_launch = fused_rerank || e->search_exact;
+  // semantics = 1: the separate re-rank launch holds at most BANG_MAX_L + 50 candidates per query, and the log may hold L + 120
+  if (e->search_inmem && !fused_rerank && e->cand_stride > BANG_MAX_L + BANG_EXTRA_ITERS) {
+    bang_set_error("option semantics = 1 (inmemory) at L = %d needs the fused re-rank (fuse_rerank != 0 and a vector layout it evaluates): the separate "
+                   "re-rank holds %d candidates per query", e->L, BANG_MAX_L + BANG_EXTRA_ITERS);
+    return BANG_ERR_UNSUPPORTED;
+  }
   if (e->search_exact && dim_adjust != 0) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
   const bool whole = ln.q0 == 0 && (int)ln.nq == Q && (int)ln.nq == e->Qcur;
   const size_t mailbox_max = (size_t)env_long("BANG_MAILBOX_BYTES", BANG_RESULT_MAILBOX_BYTES);
@@ -233,7 +239,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     const uint32_t Gd = (uint32_t)std::min<int>((int)ln.nq, bang_num_cus());
     if (kprof_d) { LANE_HIP(hipMalloc((void**)&d_prof, (size_t)Gd * 128)); LANE_HIP(hipMemsetAsync(d_prof, 0, (size_t)Gd * 128, ln.s_main)); sp.d_prof = d_prof; }
     ENQ_BEGIN();
-    BANG_TRY(bang_k_search(&sp, ln.s_main));
+    BANG_TRY(e->search_inmem ? bang_k_search_inmem(&sp, ln.s_main) : bang_k_search(&sp, ln.s_main));
     ENQ_END();
     ++ln.front_launches;
     if (d_prof) {

@@ -55,6 +55,10 @@ static const OptionDef kOptions[] = {
      "0 = PQ distances in the walk + exact re-rank (default), 1 = exact distances in the walk, results = the first k worklist entries (no re-rank; "
      "the reference's BANG_Exactdistance).  1 needs graph = device, search != 0, persistent != 0, L2 distance and the vector layouts of fuse_rerank: "
      "8-bit D % 16 == 0 with D / 16 a power of two, float D % 4 == 0, D <= 256 (environment: pq | exact)"},
+    {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
+     "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
+     "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "
+     "(pq = 0), L2 distance and distance = 0 (environment: base | inmemory)"},
     {"stage_zero_copy", "BANG_STAGE_ZC", &bang_engine::stage_zero_copy, -1, 2, INT, BEFORE_ALLOC,
      "walker forms, where staged adjacency rows travel: 0 = H2D copy per iteration, 1 = kernels read mapped pinned memory, 2 = CPU stores through the PCIe BAR, -1 = auto"},
     {"numa", "BANG_NUMA", &bang_engine::numa_opt, -1, 1, INT, BEFORE_ALLOC, "1 = pin walker threads to the GPU's NUMA node, one physical core each; 0 / -1 = leave them to the scheduler"},
@@ -138,6 +142,8 @@ void apply_env_defaults(bang_engine* e) {
       x = strcmp(v, "device") == 0 ? BANG_GRAPH_DEVICE : strcmp(v, "auto") == 0 ? BANG_GRAPH_AUTO : BANG_GRAPH_HOST;
     else if (o.field == &bang_engine::distance && !isdigit((unsigned char)*v) && *v != '-')
       x = strcmp(v, "exact") == 0 ? 1 : 0;
+    else if (o.field == &bang_engine::semantics && !isdigit((unsigned char)*v) && *v != '-')
+      x = strcmp(v, "inmemory") == 0 ? 1 : 0;
     else
       x = atol(v);
     store(e, o, std::min(o.hi, std::max(o.lo, x)));

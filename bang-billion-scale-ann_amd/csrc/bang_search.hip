@@ -52,6 +52,15 @@
 #include "bang_device.h"
 #include "bang_worklist.h"
 
+// BANG_SEARCH_INMEM (Makefile: bang_search_inmem.o / bang_search_inmem_b.o, BANG_SEARCH_PART 2 / 3): the same kernel under another name
+// (search_inmem_kernel), self-paced instances only, with the parent rule and the iteration cap of the reference's BANG_Inmemory variant
+// (option semantics = 1).  Everything that differs sits under #if BANG_SEARCH_INMEM: parts 0 and 1 compile
+// what they compiled before.
+#ifndef BANG_SEARCH_INMEM
+#define BANG_SEARCH_INMEM 0
+#endif
+#define BANG_INMEM_NO_MARK 0xFFFFFFFFu   // semantics = 1 merges with a mark no id equals: the reference variant has no d_mark step
+
 struct SearchArgs;
 // A kernel-argument field read WHERE IT IS USED (a scalar load from the kernarg segment through a pointer the optimiser cannot see through),
 // for arguments that are needed once per query (the seed list at its start, the counters and the re-rank at its end): read the ordinary way they are loop-invariant, get
@@ -304,6 +313,9 @@ __host__ __device__ constexpr uint32_t search_scratch_words(int ndw, bool host_p
   return search_coop(ndw, host_paced) ? ((ndw >= 16 && search_maxt(ndw, host_paced) >= 1024) ? 144u : 256u) : 144u;
 }
 
+#if BANG_SEARCH_INMEM
+#define search_kernel search_inmem_kernel          // (its own symbols: the instances of parts 0 and 1 keep their names)
+#endif
 template <int PSZ, int NDW, bool ALIGNED, int NHI, bool HOST, bool SPEC>
 __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const SearchArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -373,7 +385,12 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
   uint32_t* tbl = scratch;                         // filter claim table, 128 words (== sd + td: dead between the stages that use them)
   const uint32_t total_waves = gridDim.x * nwaves;
   const uint32_t gw = blockIdx.x * nwaves + wave;
+#if BANG_SEARCH_INMEM
+  const uint32_t cand_stride = L + BANG_INMEM_EXTRA_ITERS;     // candidate log of L + 120 entries
+  static_assert(!HOST && !SPEC, "semantics = 1: self-paced instances without the speculative row request");
+#else
   const uint32_t cand_stride = L + BANG_EXTRA_ITERS;
+#endif
   constexpr int SB = (NDW >= 18) ? 6 : 0;          // long rows (70 .. 128 chunks): consumed 6 code dwords (24 chunks) at a time
   constexpr bool EARLY_ROWS = !HOST;                           // code rows requested before the filter update (host-paced instances: behind it --
                                                                // 60-100 B of scratch per lane otherwise)
@@ -509,6 +526,9 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
       if (q < KARG(Q)) {
         active = true;
         w_n = 0; cc = 1; mark = 0x01010101u;           // cudaMemset(d_mark, 1, ...) :446 ; candidate log = [MEDOID] :452-464
+#if BANG_SEARCH_INMEM
+        mark = BANG_INMEM_NO_MARK;
+#endif
         evals = 0; fetched = 0; iter = 1;
         if (SUMM) { summ.clear(); probes_skipped = 0; }
         if (lane == 0) KARGP(uint32_t, d_cand_ids)[(size_t)q * cand_stride] = medoid;
@@ -530,6 +550,10 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
     uint32_t sl_ua = 0, sl_ub = 0;
     float d0 = BIG_DIST, d1 = BIG_DIST;
     bool found = false;
+#if BANG_SEARCH_INMEM
+    bool s0_mark = false;                             // the parent is the first sorted survivor: marked visited where the merge puts it
+    float s0_d = 0.0f;
+#endif
     const bool first = (iter == 1);
     if (active) {
       // ---------------- K5: filter (neighbor_filtering_new :1140-1165) ----------------
@@ -717,6 +741,25 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
       const bool have_best = (bi != 0xFFFFu);
       if (!have_best) bd = BIG_DIST;
       bool from_best = false;
+#if BANG_SEARCH_INMEM
+      // semantics = 1 (BANG_Inmemory/parANN.cu:1399-1418): the parent is the first unvisited worklist entry AFTER this
+      // iteration's merge.  Which entry that will be is known before the merge -- the first sorted survivor s0 or the first unvisited old entry h,
+      // whichever the merge puts first (new before equal old) -- so the next row is still requested here, ahead of the sort/merge.
+      if (first) {
+        // the merge takes the first min(n, L) sorted survivors and marks the medoid visited: the parent is the first non-medoid among them
+        uint32_t rk = (uint32_t)__popcll(__ballot((uint32_t)lane < n && (d0 < bd || (d0 == bd && (uint32_t)lane < bi))));
+        if (n > 64 && bi != 64u && __shfl(d1, 0) < bd) ++rk;
+        if (have_best && rk < L) { found = true; parent = bid; from_best = true; }
+      } else {
+        const bool s0_in = have_best && (bd < head.tail || w_n < L);          // s0 enters the worklist (orc_merge: nb >= 1)
+        if (head.found && !(s0_in && bd <= head.d)) { found = true; parent = head.id; if (lane == 0) s.wv[head.idx] = 1; }
+        else if (s0_in) { found = true; parent = bid; from_best = true; }
+      }
+      parent = uni(parent);
+      s0_mark = from_best;
+      s0_d = bd;
+      if (found) ++cc;
+#else
       if (first) {
         if (have_best) { found = true; parent = bid; from_best = true; }
       } else {
@@ -733,6 +776,7 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
         if (from_best) mark = parent;
         ++cc;                                                  // (the candidate-log store :1451-1458 is issued behind the row request: it is not on the chain)
       }
+#endif
     }
     IA_FRESH();                                                 // (the hand-over's arguments: IterArgs)
     const uint32_t cap_iter = IA32(IA_CAP_ITER);
@@ -816,9 +860,33 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
     if (active) {
       // ---------------- K3a + K3b: sort the survivors, merge them into the worklist ----------------
       LANE_FRESH();
+#if BANG_SEARCH_INMEM
+      if (n > 0 && iter < cap_iter && found) {
+        w_n = sort_and_merge(s, n, d0, sid0, d1, sid1, iter, w_n, L, medoid, mark, head.tail, lane);
+        if (s0_mark) {
+          // the parent s0 sits where the merge put it, marked by position (the reference marks that one entry, W.vis[i] = 1: a second copy
+          // of its id from the same row stays unvisited).  Iteration 1: the worklist is the sorted survivors and s0 the first non-medoid among
+          // them -- only medoid copies precede it, and they may TIE with it (the stable sort keeps the medoid, input position 0, first), so the
+          // slot is the first id that is not the medoid.  Later iterations: behind the entries closer than it and in front of the equal ones
+          // (new before equal old; no other survivor precedes s0)
+          uint32_t pos = 0;
+          for (uint32_t b = 0; b < w_n; b += WAVE) {
+            const uint32_t i = b + (uint32_t)lane;
+            const uint32_t ii = i < w_n ? i : 0u;
+            if (first) {
+              const uint64_t mk = __ballot(i < w_n && s.wi[ii] != medoid);
+              if (mk) { pos = b + (uint32_t)__builtin_ctzll(mk); break; }
+            } else pos += (uint32_t)__popcll(__ballot(i < w_n && s.wd[ii] < s0_d));
+          }
+          if (lane == 0) s.wv[pos] = 1;
+          wave_sync();
+        }
+      }
+#else
       if (n > 0 && iter < cap_iter) {
         w_n = sort_and_merge(s, n, d0, sid0, d1, sid1, iter, w_n, L, medoid, mark, head.tail, lane);
       }
+#endif
       PH(6);   // (publish +) sort/merge
 #ifdef BANG_SEARCH_PHASE_PROF
       if (wave == 0) ++ph_n;
@@ -826,7 +894,11 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
 
       // ---------------- next iteration of this query, or the query is finished
       // a query is active while it has a parent or unmerged survivors (CANON 4); the loop ends at the cap (:950-956)
+#if BANG_SEARCH_INMEM
+      if (!found || iter == cap_iter) {                       // no parent: the query ends (its survivors could not enter the worklist either)
+#else
       if ((!found && n == 0) || iter == cap_iter) {
+#endif
         if (lane == 0) {
           // (the once-per-query arguments are read where they are used: KARG)
           KARGP(uint32_t, d_cand_cnt)[q] = cc;
@@ -919,12 +991,20 @@ static int launch_inst(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, h
 #define BANG_SEARCH_PART 0
 #endif
 constexpr bool search_in_part1(int ndw, bool aligned, bool host_paced) { return ndw >= 24 || (ndw == 19 && !aligned) || (host_paced && ndw >= 16); }
+#if BANG_SEARCH_INMEM
+// semantics = 1: parts 2 (bang_search_inmem.o, iterative-ILP) and 3 (bang_search_inmem_b.o, the default scheduler) split the instances the way
+// parts 0 and 1 do
+#define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 3)
+#define bang_search_launch_part1 bang_search_inmem_launch_part3
+#else
+#define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 1)
+#endif
 extern "C" int bang_search_launch_part1(const SearchArgs* a, uint32_t grid, uint32_t block, size_t lds, void* stream);
 
 template <int PSZ, int NDW, bool ALIGNED, int NHI, bool HOST, bool SPEC>
 static int launch_part(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-  if constexpr (search_in_part1(NDW, ALIGNED, HOST) == (BANG_SEARCH_PART == 1)) return launch_inst<PSZ, NDW, ALIGNED, NHI, HOST, SPEC>(a, grid, block, lds, st);
-#if BANG_SEARCH_PART == 0
+  if constexpr (search_in_part1(NDW, ALIGNED, HOST) == BANG_SEARCH_SECOND_PART) return launch_inst<PSZ, NDW, ALIGNED, NHI, HOST, SPEC>(a, grid, block, lds, st);
+#if !BANG_SEARCH_SECOND_PART
   return bang_search_launch_part1(&a, grid.x, block.x, lds, (void*)st);
 #else
   bang_set_error("search-kernel instance psz=%u mp=%u is not part of this translation unit", a.p.psz, a.p.mp);
@@ -934,11 +1014,15 @@ static int launch_part(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, h
 
 template <int PSZ, int NDW, bool ALIGNED, int NHI>
 static int launch_hd(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
+#if BANG_SEARCH_INMEM
+  return launch_part<PSZ, NDW, ALIGNED, NHI, false, false>(a, grid, block, lds, st);     // (self-paced, no speculative row request)
+#else
   if constexpr (search_has_spec(NDW)) {
     if (a.p.d_graph && a.p.spec_rows == 1u) return launch_part<PSZ, NDW, ALIGNED, NHI, false, true>(a, grid, block, lds, st);
   }
   return a.p.d_graph ? launch_part<PSZ, NDW, ALIGNED, NHI, false, false>(a, grid, block, lds, st)
                      : launch_part<PSZ, NDW, ALIGNED, NHI, true, false>(a, grid, block, lds, st);
+#endif
 }
 
 template <int PSZ, int NDW>
@@ -954,6 +1038,12 @@ static int launch_al(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hip
     bang_set_error("no search-kernel instance for the exact-size pivot table psz=%u mp=%u nhi=%u", a.p.psz, a.p.mp, a.p.pq_nhi);
     return BANG_ERR_UNSUPPORTED;
   }
+#if BANG_SEARCH_INMEM
+  if constexpr (NDW >= 32) {          // 128-chunk rows that are not dword-aligned spill under every scheduler (56-72 B per lane): not built here
+    if (!al) { bang_set_error("semantics = 1: no search-kernel instance for %u-chunk code rows that are not dword-aligned", a.p.mp); return BANG_ERR_UNSUPPORTED; }
+    return launch_hd<PSZ, NDW, true, 0>(a, grid, block, lds, st);
+  } else
+#endif
   return al ? launch_hd<PSZ, NDW, true, 0>(a, grid, block, lds, st) : launch_hd<PSZ, NDW, false, 0>(a, grid, block, lds, st);
 }
 
@@ -981,7 +1071,7 @@ static int search_dispatch(const SearchArgs& a, dim3 grid, dim3 block, size_t ld
   }
 }
 
-#if BANG_SEARCH_PART == 1
+#if BANG_SEARCH_SECOND_PART
 extern "C" int bang_search_launch_part1(const SearchArgs* a, uint32_t grid, uint32_t block, size_t lds, void* stream) {
   return search_dispatch(*a, dim3(grid), dim3(block), lds, (hipStream_t)stream);
 }
@@ -989,6 +1079,97 @@ extern "C" int bang_search_launch_part1(const SearchArgs* a, uint32_t grid, uint
 
 #define SRCH_WG_SHARED_BYTES 2048u     // group-shared LDS behind the waves' regions (host-paced form): 128 words per pacing group, up to 4 groups
 #define SRCH_DEFAULT_GROUP_WAVES 8u
+
+// Argument checks, IterArgs, grid and launch policies of a search-kernel launch -- ONE copy for bang_k_search (parts 0 / 1) and
+// bang_k_search_inmem (parts 2 / 3, inmem: semantics = 1 -- self-paced only, cap up to L + 119, no speculative row request)
+static int search_setup(const bang_search_params* p, bool inmem, SearchArgs* out, dim3* grid, dim3* block, size_t* lds) {
+  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L || p->m == 0) { bang_set_error("bad R/L/m"); return BANG_ERR_ARG; }
+  if (p->psz == 0 || p->mp < p->m || (p->mp & 3u)) { bang_set_error("the search kernel needs the LDS-resident pivot layout"); return BANG_ERR_UNSUPPORTED; }
+  if (!p->d_codes || !p->d_pivots_packed || !p->d_qc || !p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt ||
+      !p->d_next_query) { bang_set_error("null buffer"); return BANG_ERR_ARG; }
+  if (!p->d_graph && (!p->d_rows || !p->d_ctl || !p->h_done || !p->h_parents || (p->ship_vectors && (!p->h_pub_q || !p->h_pub_c)))) {
+    bang_set_error("host-paced search kernel: null pacing buffer"); return BANG_ERR_ARG;
+  }
+  if (inmem && (!p->d_graph || p->row_layout != 0u)) { bang_set_error("semantics = 1: the graph entries must be in HBM (d_graph, row_layout 0)"); return BANG_ERR_UNSUPPORTED; }
+  if (p->pq_nhi && (p->psz != 2 || p->pq_nhi > p->mp)) { bang_set_error("bad pq_nhi"); return BANG_ERR_ARG; }
+  if (p->cap_iter == 0 || p->cap_iter > p->L + (inmem ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS) - 1) { bang_set_error("bad iteration cap"); return BANG_ERR_ARG; }
+  if (p->rr_queries) {
+    if (!p->d_graph) { bang_set_error("the fused re-rank belongs to the self-paced form"); return BANG_ERR_ARG; }
+    if (!p->rr_vec_base || !p->rr_ids_out || !p->rr_dists_out || p->rr_k == 0 || p->rr_Q_total < p->rr_q0 + p->Q ||
+        !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0) || (((uintptr_t)p->rr_vec_base) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
+      bang_set_error("fused re-rank: bad arguments / unsupported vector layout"); return BANG_ERR_ARG;
+    }
+  }
+  SearchArgs& a = *out;
+  a.p = *p;
+  a.lds_piv_floats = pivot_table_floats(p->psz, p->mp, p->pq_nhi);
+  __builtin_memset(&a.iter, 0, sizeof(a.iter));
+  a.iter.d_codes = p->d_codes; a.iter.n_nodes = p->n_nodes; a.iter.d_cand_ids = p->d_cand_ids; a.iter.d_graph = p->d_graph; a.iter.entry_len = p->entry_len;
+  a.iter.vec_bytes = p->vec_bytes; a.iter.row_layout = p->row_layout; a.iter.n_rows_hbm = p->n_rows_hbm; a.iter.n_slices = p->n_slices;
+  a.iter.d_rows_hbm = p->d_rows_hbm; a.iter.d_row_slices = p->d_row_slices; a.iter.slice_rows = p->slice_rows;
+  a.iter.d_bloom = p->d_bloom; a.iter.cap_iter = p->cap_iter;      // (summ_iters: below, once the policy is resolved)
+  uint32_t grid_n = 0, waves = 0, nctx = p->nctx, gs = p->group_waves;
+  const int rc = bang_search_geometry(p->psz, p->mp, p->pq_nhi, p->L, p->Q, p->max_wgs, p->max_waves, p->d_graph ? 0 : 1, &grid_n, &waves, &nctx, &gs);
+  if (rc != BANG_OK) return rc;
+  a.nctx = nctx;
+  a.gs = gs;
+  // The filter summary trades LDS-crossbar work on the chain of every iteration (12 ds_bpermute + two transposition passes) for
+  // memory requests.  A full chip is short of requests-in-flight: with it the 10 K SIFT1B-shape batch takes 8.36 instead of 9.09 ms, 5 000 /
+  // 2 500 queries 4.68 / 2.37 instead of 4.99 / 2.71.  A lightly loaded one is short of nothing but the chain: 1 250 queries (5 waves per CU)
+  // 1.70 ms without it against 1.77, 625 queries 1.43 against 1.53 (profiles/r04_summary_cutoff.md).  auto then: off up to 6 queries per CU.
+  // (with spec_rows on, re-measured: 1 250 queries 1.69 with / 1.63 without, 1 400: 1.73 / 1.72, 1 536 = 6 per CU: 1.74-1.78 / 1.73-1.74, 1 900: 1.94 / 1.99)
+  // (round 6, final kernel: 1 536 queries = 6 per CU 1.555 with / 1.585 without, 1 250 = 5 per CU 1.493 / 1.453: the cut-off is 5)
+  const bool light = (p->Q + grid_n - 1) / grid_n <= 5u;
+  if (a.p.summ_iters == 0u) a.p.summ_iters = light ? 1u : 0xFFFFFFFFu;
+  a.iter.summ_iters = a.p.summ_iters;
+  // wave priority around the request-issuing stretches of an iteration: on where wave slots are free (<= 10 queries per CU); BANG_SEARCH_PRIO = 0 / 1 forces it
+  { const char* e = getenv("BANG_SEARCH_PRIO"); a.iter.prio = (e && e[0] >= '0' && e[0] <= '3') ? (e[0] == '1' ? 3u : e[0] == '3' ? 1u : (uint32_t)(e[0] - '0')) : (((p->Q + grid_n - 1) / grid_n <= 10u) ? 3u : 0u); }   // (1 = both stretches, 2 = the hand-over's only, 3 = the top's only)
+  // spec_rows: one memory latency less on the chain of every iteration, the rows of the ids the filter drops fetched in vain.  Without / with,
+  // ms per batch (profiles/r05_spec_rows.md) -- rows pulled, N = 1e9 random graph: 10 000 queries 8.75 / 8.38, 5 000 4.72 / 4.61, 2 500 2.33 / 2.29, 1 250 1.74 / 1.63; N = 1e8 Vamana-style graph, pulled:
+  // 6.48 / 6.38, 1.77 / 1.77, 1.29 / 1.23; the same graph in HBM: 4.68 / 4.79, 1.44 / 1.41, 1.13 / 1.07.
+  // auto: on where the rows are pulled, and up to 8 queries per CU where the graph is in HBM
+  // (round 6, final kernel, structured 1e8-point graph in HBM, without / with: 10 000 queries 4.40 / 4.62 ms, 2 500: 1.32 / 1.345, 2 000: 1.18 / 1.13, 1 250: 1.05 / 1.02, 625: 0.94 / 0.91;
+  //  the shape-only DEEP100M index -- its filter drops next to nothing -- 7.16 / 7.05 at 10 000: the policy follows the structured graph, up to 8 queries per CU)
+  const bool spec_auto = p->row_layout != 0u || (p->Q + grid_n - 1) / grid_n <= 8u;
+  a.p.spec_rows = (!inmem && search_has_spec((int)(p->mp / 4u)) && p->d_graph && (p->spec_rows == 1u || (p->spec_rows == 0u && spec_auto))) ? 1u : 2u;
+  // (semantics = 1: no instances with the speculative row request -- off)
+  a.wl_words = search_wl_words(p->L);
+  a.wave_words = search_wave_words(p->L, nctx, (int)(p->mp / 4u), p->d_graph == nullptr);
+  *lds = (size_t)a.lds_piv_floats * 4 + (size_t)waves * a.wave_words * 4 + (p->d_graph ? 0u : SRCH_WG_SHARED_BYTES);
+  *grid = dim3(grid_n);
+  *block = dim3(waves * WAVE);
+  return BANG_OK;
+}
+
+#if BANG_SEARCH_INMEM
+
+// semantics = 1: the grid is that of the self-paced form of bang_k_search (the same LDS per wave: the candidate log is in HBM)
+extern "C" int bang_search_inmem_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
+                                          uint32_t* workgroups, uint32_t* waves) {
+  uint32_t nctx = 1, gs = 0;
+  return bang_search_geometry(psz, mp, nhi, L, Q, max_wgs, max_waves, 0, workgroups, waves, &nctx, &gs);
+}
+
+// engine-internal (bang_engine.h): does a semantics = 1 instance exist for this pivot layout and code-row stride?  (launch_al: not for 128-chunk
+// rows that are not dword-aligned)
+extern "C" int bang_search_inmem_has_instance(uint32_t psz, uint32_t mp, uint32_t code_stride) {
+  return (psz != 0 && mp / 4u >= 32u && (code_stride % 4u) != 0u) ? 0 : 1;
+}
+
+extern "C" int bang_k_search_inmem(const bang_search_params* p, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (p->Q == 0) return BANG_OK;
+  SearchArgs a;
+  dim3 grid, block;
+  size_t lds = 0;
+  const int rc = search_setup(p, true, &a, &grid, &block, &lds);
+  if (rc != BANG_OK) return rc;
+  // the fused re-rank works in the wave's LDS region: its n <= L + 120 candidate words fit (2L + L/4 + 144 words)
+  static_assert(BANG_INMEM_EXTRA_ITERS <= 144, "the fused re-rank's candidates fit the wave's LDS region");
+  return search_dispatch(a, grid, block, lds, (hipStream_t)stream);
+}
+
+#else
 
 // waves per workgroup that fit beside the pivot table with nctx query contexts each (0: not even one); the host-paced form also
 // keeps its pacing groups' shared words there
@@ -1053,59 +1234,13 @@ extern "C" int bang_search_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uin
 extern "C" int bang_k_search(const bang_search_params* p, void* stream) {
   if (!p) return BANG_ERR_ARG;
   if (p->Q == 0) return BANG_OK;
-  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L || p->m == 0) { bang_set_error("bad R/L/m"); return BANG_ERR_ARG; }
-  if (p->psz == 0 || p->mp < p->m || (p->mp & 3u)) { bang_set_error("the search kernel needs the LDS-resident pivot layout"); return BANG_ERR_UNSUPPORTED; }
-  if (!p->d_codes || !p->d_pivots_packed || !p->d_qc || !p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt ||
-      !p->d_next_query) { bang_set_error("null buffer"); return BANG_ERR_ARG; }
-  if (!p->d_graph && (!p->d_rows || !p->d_ctl || !p->h_done || !p->h_parents || (p->ship_vectors && (!p->h_pub_q || !p->h_pub_c)))) {
-    bang_set_error("host-paced search kernel: null pacing buffer"); return BANG_ERR_ARG;
-  }
-  if (p->pq_nhi && (p->psz != 2 || p->pq_nhi > p->mp)) { bang_set_error("bad pq_nhi"); return BANG_ERR_ARG; }
-  if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("bad iteration cap"); return BANG_ERR_ARG; }
-  if (p->rr_queries) {
-    if (!p->d_graph) { bang_set_error("the fused re-rank belongs to the self-paced form"); return BANG_ERR_ARG; }
-    if (!p->rr_vec_base || !p->rr_ids_out || !p->rr_dists_out || p->rr_k == 0 || p->rr_Q_total < p->rr_q0 + p->Q ||
-        !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0) || (((uintptr_t)p->rr_vec_base) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
-      bang_set_error("fused re-rank: bad arguments / unsupported vector layout"); return BANG_ERR_ARG;
-    }
-  }
   SearchArgs a;
-  a.p = *p;
-  a.lds_piv_floats = pivot_table_floats(p->psz, p->mp, p->pq_nhi);
-  __builtin_memset(&a.iter, 0, sizeof(a.iter));
-  a.iter.d_codes = p->d_codes; a.iter.n_nodes = p->n_nodes; a.iter.d_cand_ids = p->d_cand_ids; a.iter.d_graph = p->d_graph; a.iter.entry_len = p->entry_len;
-  a.iter.vec_bytes = p->vec_bytes; a.iter.row_layout = p->row_layout; a.iter.n_rows_hbm = p->n_rows_hbm; a.iter.n_slices = p->n_slices;
-  a.iter.d_rows_hbm = p->d_rows_hbm; a.iter.d_row_slices = p->d_row_slices; a.iter.slice_rows = p->slice_rows;
-  a.iter.d_bloom = p->d_bloom; a.iter.cap_iter = p->cap_iter;      // (summ_iters: below, once the policy is resolved)
-  uint32_t grid_n = 0, waves = 0, nctx = p->nctx, gs = p->group_waves;
-  const int rc = bang_search_geometry(p->psz, p->mp, p->pq_nhi, p->L, p->Q, p->max_wgs, p->max_waves, p->d_graph ? 0 : 1, &grid_n, &waves, &nctx, &gs);
+  dim3 grid, block;
+  size_t lds = 0;
+  const int rc = search_setup(p, false, &a, &grid, &block, &lds);
   if (rc != BANG_OK) return rc;
-  a.nctx = nctx;
-  a.gs = gs;
-  // The filter summary trades LDS-crossbar work on the chain of every iteration (12 ds_bpermute + two transposition passes) for
-  // memory requests.  A full chip is short of requests-in-flight: with it the 10 K SIFT1B-shape batch takes 8.36 instead of 9.09 ms, 5 000 /
-  // 2 500 queries 4.68 / 2.37 instead of 4.99 / 2.71.  A lightly loaded one is short of nothing but the chain: 1 250 queries (5 waves per CU)
-  // 1.70 ms without it against 1.77, 625 queries 1.43 against 1.53 (profiles/r04_summary_cutoff.md).  auto then: off up to 6 queries per CU.
-  // (with spec_rows on, re-measured: 1 250 queries 1.69 with / 1.63 without, 1 400: 1.73 / 1.72, 1 536 = 6 per CU: 1.74-1.78 / 1.73-1.74, 1 900: 1.94 / 1.99)
-  // (round 6, final kernel: 1 536 queries = 6 per CU 1.555 with / 1.585 without, 1 250 = 5 per CU 1.493 / 1.453: the cut-off is 5)
-  const bool light = (p->Q + grid_n - 1) / grid_n <= 5u;
-  if (a.p.summ_iters == 0u) a.p.summ_iters = light ? 1u : 0xFFFFFFFFu;
-  a.iter.summ_iters = a.p.summ_iters;
-  // wave priority around the request-issuing stretches of an iteration: on where wave slots are free (<= 10 queries per CU); BANG_SEARCH_PRIO = 0 / 1 forces it
-  { const char* e = getenv("BANG_SEARCH_PRIO"); a.iter.prio = (e && e[0] >= '0' && e[0] <= '3') ? (e[0] == '1' ? 3u : e[0] == '3' ? 1u : (uint32_t)(e[0] - '0')) : (((p->Q + grid_n - 1) / grid_n <= 10u) ? 3u : 0u); }   // (1 = both stretches, 2 = the hand-over's only, 3 = the top's only)
-  // spec_rows: one memory latency less on the chain of every iteration, the rows of the ids the filter drops fetched in vain.  Without / with,
-  // ms per batch (profiles/r05_spec_rows.md) -- rows pulled, N = 1e9 random graph: 10 000 queries 8.75 / 8.38, 5 000 4.72 / 4.61, 2 500 2.33 / 2.29, 1 250 1.74 / 1.63; N = 1e8 Vamana-style graph, pulled:
-  // 6.48 / 6.38, 1.77 / 1.77, 1.29 / 1.23; the same graph in HBM: 4.68 / 4.79, 1.44 / 1.41, 1.13 / 1.07.
-  // auto: on where the rows are pulled, and up to 8 queries per CU where the graph is in HBM
-  // (round 6, final kernel, structured 1e8-point graph in HBM, without / with: 10 000 queries 4.40 / 4.62 ms, 2 500: 1.32 / 1.345, 2 000: 1.18 / 1.13, 1 250: 1.05 / 1.02, 625: 0.94 / 0.91;
-  //  the shape-only DEEP100M index -- its filter drops next to nothing -- 7.16 / 7.05 at 10 000: the policy follows the structured graph, up to 8 queries per CU)
-  const bool spec_auto = p->row_layout != 0u || (p->Q + grid_n - 1) / grid_n <= 8u;
-  a.p.spec_rows = (search_has_spec((int)(p->mp / 4u)) && p->d_graph && (p->spec_rows == 1u || (p->spec_rows == 0u && spec_auto))) ? 1u : 2u;
-  a.wl_words = search_wl_words(p->L);
-  a.wave_words = search_wave_words(p->L, nctx, (int)(p->mp / 4u), p->d_graph == nullptr);
-  const size_t lds = (size_t)a.lds_piv_floats * 4 + (size_t)waves * a.wave_words * 4 + (p->d_graph ? 0u : SRCH_WG_SHARED_BYTES);
-  const dim3 grid(grid_n), block(waves * WAVE);
   hipStream_t st = (hipStream_t)stream;
   return search_dispatch(a, grid, block, lds, st);
 }
-#endif   // BANG_SEARCH_PART == 0
+#endif   // BANG_SEARCH_INMEM
+#endif   // parts 0 / 2

@@ -37,6 +37,7 @@ extern "C" {
 #define BANG_MAX_L 512          /* bang.h:20 */
 #define BANG_MAX_R 64           /* bang_search.cu:35 */
 #define BANG_EXTRA_ITERS 50     /* NAX_EXTRA_ITERATION, bang_search.cu:53 */
+#define BANG_INMEM_EXTRA_ITERS 120 /* semantics = 1: MAX_PARENTS_PERQUERY = L + 120, BANG_Inmemory/parANN.cu:30 (cap: iteration L + 119, :603-609) */
 #define BANG_BF_ENTRIES 399887u /* bang_search.cu:48 */
 #define BANG_BF_WORDS 12512u    /* bit-packed filter, u32 words per query (>= ceil(399887/32), 64-B multiple) */
 #define BANG_NO_PARENT 0xFFFFFFFFu   /* parents[q]: query is finished */
@@ -453,6 +454,16 @@ int bang_k_search_exact(const bang_search_params* p, void* stream);
  * waves per CU as the instance's registers and LDS allow, <= 16 per workgroup; max_wgs / max_waves: caps if nonzero; a batch of fewer than a
  * workgroup-full of queries per CU is spread over all CUs) */
 int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+
+/* BANG_INMEMORY SEMANTICS of the query-resident search kernel (csrc/bang_search.hip built as bang_search_inmem.o / bang_search_inmem_b.o; engine
+ * option "semantics" = 1; the reference's BANG_Inmemory, BANG_Inmemory/parANN.cu:1287-1420): the loop of bang_k_search with the parent taken AFTER
+ * the merge -- the first unvisited worklist entry, marked visited -- and an iteration cap of L + 119 (cap_iter <= L + BANG_INMEM_EXTRA_ITERS - 1; the
+ * candidate log d_cand_ids has a stride of L + BANG_INMEM_EXTRA_ITERS).  Graph entries in HBM only (d_graph, row_layout 0); spec_rows is ignored (off).
+ * Arguments otherwise as for bang_k_search's self-paced form, the fused re-rank (rr_*) included. */
+int bang_k_search_inmem(const bang_search_params* p, void* stream);
+/* grid of a bang_k_search_inmem launch: that of bang_search_geometry's self-paced form (host_paced = 0) */
+int bang_search_inmem_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
+                               uint32_t* workgroups, uint32_t* waves);
 
 #ifdef __cplusplus
 }
