@@ -108,9 +108,9 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       return BANG_ERR_UNSUPPORTED;
     }
     if (e->distfn != BANG_DIST_L2) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
-    if (!bang_search_can_rerank(e->dtype, e->D, e->entry_len, 0)) {                 // (the layouts of the fused re-rank: the same arithmetic)
-      bang_set_error("option distance = 1 (exact): unsupported vector layout (dtype %d, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0 with D / 16 "
-                     "a power of two, float vectors D %% 4 == 0; D <= 256", e->dtype, e->D, (unsigned long long)e->entry_len);
+    if (!bang_search_exact_supported(e->dtype, e->D, e->entry_len)) {
+      bang_set_error("option distance = 1 (exact): unsupported vector layout (dtype %d, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0, "
+                     "float vectors D %% 4 == 0; D <= %u; an entry stride divisible by 4", e->dtype, e->D, (unsigned long long)e->entry_len, BANG_EXACT_MAX_D);
       return BANG_ERR_UNSUPPORTED;
     }
     e->search_exact = true;

@@ -54,6 +54,12 @@ int bang_num_cus(void);
 // 1 if the fused kernel has an instance for the exact-size ("ragged") pivot table of this layout
 int bang_ragged_supported(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t m);
 
+
+// the wide-layout instances of the exact-distance search kernel (bang_search_exact.hip built with BANG_EXACT_WIDE as bang_search_exact_wide.o):
+// bang_k_search_exact hands them the layouts bang_search_can_rerank refuses, its arguments checked; the grid as bang_search_exact_geometry
+int bang_k_search_exact_wide(const bang_search_params* p, void* stream);
+int bang_search_exact_wide_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,8 +53,8 @@ static const OptionDef kOptions[] = {
     {"search", "BANG_SEARCH", &bang_engine::search_opt, -1, 1, INT, BEFORE_ALLOC, "1 = the query-resident search kernel (bang_k_search), 0 = the per-iteration kernels, -1 = auto"},
     {"distance", "BANG_DISTANCE", &bang_engine::distance, 0, 1, INT, BEFORE_ALLOC,
      "0 = PQ distances in the walk + exact re-rank (default), 1 = exact distances in the walk, results = the first k worklist entries (no re-rank; "
-     "the reference's BANG_Exactdistance).  1 needs graph = device, search != 0, persistent != 0, L2 distance and the vector layouts of fuse_rerank: "
-     "8-bit D % 16 == 0 with D / 16 a power of two, float D % 4 == 0, D <= 256 (environment: pq | exact)"},
+     "the reference's BANG_Exactdistance).  1 needs graph = device, search != 0, persistent != 0, L2 distance and a vector layout of "
+     "bang_search_exact_supported: 8-bit D % 16 == 0, float D % 4 == 0, D <= 1024 (environment: pq | exact)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

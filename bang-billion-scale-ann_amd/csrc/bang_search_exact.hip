@@ -20,6 +20,16 @@
 //    instance's register count and gives every CU as many waves as its registers (512 per SIMD lane, allocated in granules of 8) and
 //    160 KB of LDS hold, at most 32; small batches are spread over all CUs.
 //  * An adjacency id >= n_nodes is never followed: the row counts as empty and *d_abort = 2 (the batch ends with an error).
+//  * WIDE LAYOUTS (this file built a second time with -DBANG_EXACT_WIDE=1 as bang_search_exact_wide.o: the kernel renamed
+//    search_exact_wide_kernel, so that the three instances above stay the code they are).  D up to 1024; 8-bit vectors with any D / 16.
+//    The same loop; what changes is the distance stage (exact_dist_wide below): the survivors' rows are fetched COOPERATIVELY, 64 bytes
+//    of 16 rows per wave instruction (four adjacent lanes per row), staged through registers into a 4 KB LDS tile of the wave (64 rows x
+//    64 B, 16-byte slots XOR-swizzled so that the tile's ds_write_b128 and ds_read_b128 are free of bank conflicts), and lane i runs
+//    survivor i's chain out of the tile while the next tile's loads are in flight.  Tiles are consumed in ascending order, so the chain
+//    is orc_exact_dist's.  Float: the query in up to 16 registers.  8-bit: lane l holds the query's 16-byte piece l; a 16-dimension piece
+//    is added as an integer (v_dot4) while EVERY survivor's running sum stays <= 2^24 -- all partial sums of the chain are then integers
+//    a float holds, the chain rounds nowhere and its value is the integer -- and from the first piece that takes a survivor past 2^24 the
+//    wave continues with the float chain, dimension by dimension, from the integer it has (CANON 10).
 //
 // Reference line numbers: the reference's BANG_Base/bang_search.cu unless a file is named.
 
@@ -118,8 +128,125 @@ __device__ __forceinline__ void exact_dist_f32(const uint8_t GAS* graph, uint64_
   }
 }
 
+#ifdef BANG_EXACT_WIDE
+// ---------------------------------------------------------------------------------------------------------------------
+// wide layouts: rows fetched cooperatively through an LDS tile (one per wave: 64 rows x 64 bytes)
+// ---------------------------------------------------------------------------------------------------------------------
+#define EXACT_TILE_WORDS 1024u
+#define EXACT_QREGS 16               // float query registers: 64 dimensions each
+
+// word offset of 16-byte piece c (0..3) of row s (0..63) in the tile.  ds_read_b128 banks over 256 B (16 slots) in four 16-lane groups
+// {0-3,12-15,20-27} {4-11,16-19,28-31} {32-35,44-47,52-59} {36-43,48-51,60-63}: lane s reads slot 4 (s & 3) + (c ^ (s >> 2 & 3)), and
+// s >> 2 & 3 takes four values in every group -- 16 slots, no conflict.  ds_write_b128 banks over 128 B in groups of 8 adjacent lanes =
+// two adjacent rows x four pieces: 8 slots, no conflict.
+typedef uint32_t u32x4t __attribute__((ext_vector_type(4)));     // 16-byte aligned: the tile's slots (ds_write_b128 / ds_read_b128)
+__device__ __forceinline__ uint32_t tile_word(uint32_t s, uint32_t c) { return 16u * s + 4u * (c ^ ((s >> 2) & 3u)); }
+
+__device__ __forceinline__ int rdlane(int v, uint32_t l) { return __builtin_amdgcn_readlane(v, (int)l); }
+
+// exact distances of the n survivors (ids in LDS: sid[0, n)) -> dist[0, n) in LDS.  DT == BANG_F32: qr[t] holds query element 64 t + lane.
+// 8-bit: qw = the query's 16-byte piece `lane`, qq the sum of its squares.  Every lane of the wave executes.
 template <int DT>
-__global__ __launch_bounds__(1024) void search_exact_kernel(const ExactArgs a) {
+__device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64_t entry_len, uint32_t vec_bytes, uint32_t D, const uint32_t* sid,
+                                                uint32_t n, float* dist, uint32_t* tile, const float (&qr)[EXACT_QREGS], u32x4a qw, int qq, int lane) {
+  constexpr bool SG = (DT == BANG_I8);
+  const uint32_t T = (vec_bytes + 63u) >> 6;                      // 64-byte tiles per row
+  const uint32_t ls = (uint32_t)lane >> 2, lc = (uint32_t)lane & 3u;   // fetch: row ls + 16 u, piece lc
+  for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform; a second pass for the 65th id of the seed list only)
+    const uint32_t np = n - i0 < WAVE ? n - i0 : WAVE;
+    u32x4a st[4] = {};
+    auto fetch = [&](uint32_t t) {                                // tile t of up to 64 rows: four loads of 16 rows x 64 B
+      uint32_t o = 64u * t + 16u * lc;
+      if (o >= vec_bytes) o = 0;                                  // (behind the vector's end: a piece again, never used)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t i = 16u * (uint32_t)u + ls;                // (the ids are re-read from LDS per tile: four registers less across the chain)
+        if (16u * (uint32_t)u < np) st[u] = *(const u32x4a GAS*)(graph + (uint64_t)sid[i0 + (i < np ? i : 0u)] * entry_len + o);   // (uniform)
+      }
+    };
+    auto turn = [&](uint32_t t) {                                 // staged tile t -> LDS; tile t + 1 requested
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (16u * (uint32_t)u < np) *(u32x4t*)(tile + tile_word(16u * (uint32_t)u + ls, lc)) = (u32x4t){st[u].x, st[u].y, st[u].z, st[u].w};
+      wave_sync();
+      if (t + 1u < T) fetch(t + 1u);
+    };
+    auto piece = [&](int c) { return *(const u32x4t*)(tile + tile_word((uint32_t)lane, (uint32_t)c)); };   // this lane's row
+    fetch(0);
+    float acc = 0.0f;
+    if (DT == BANG_F32) {
+      for (uint32_t tq = 0; 64u * tq < D; ++tq) {                 // (uniform; qr[tq]: a register picked by index, s_set_gpr_idx)
+        const int qcur = (int)__float_as_uint(qr[tq]);
+        for (uint32_t tt = 0; tt < 4u; ++tt) {
+          const uint32_t t = 4u * tq + tt;
+          if (t >= T) break;                                      // (uniform)
+          turn(t);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            if (16u * t + 4u * (uint32_t)c < D) {                 // (uniform; D % 4 == 0)
+              const u32x4t w = piece(c);
+              const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+              for (int d = 0; d < 4; ++d) {
+                const float qv = __uint_as_float((uint32_t)rdlane(qcur, 16u * tt + 4u * (uint32_t)c + (uint32_t)d));
+                const float diff = __uint_as_float(ww[d]) - qv;   // parANN.cu:1139-1179 / orc_exact_dist: vector - query
+                acc = __builtin_fmaf(diff, diff, acc);            // ascending dimension
+              }
+            }
+          }
+        }
+      }
+    } else {
+      int sum = 0;                                                // the chain's value while it is an integer <= 2^24
+      bool chain = false;                                         // (uniform) the wave has left the integers
+      const uint32_t P = D >> 4;                                  // 16-byte pieces per vector
+      for (uint32_t t = 0; t < T; ++t) {
+        turn(t);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const uint32_t pc = 4u * t + (uint32_t)c;
+          if (pc < P) {                                           // (uniform)
+            const u32x4t w = piece(c);
+            const uint32_t qx = (uint32_t)rdlane((int)qw.x, pc), qy = (uint32_t)rdlane((int)qw.y, pc), qz = (uint32_t)rdlane((int)qw.z, pc),
+                           qv = (uint32_t)rdlane((int)qw.w, pc);
+            if (!chain) {
+              const int vv = xdot4<SG>(w.x, w.x, xdot4<SG>(w.y, w.y, xdot4<SG>(w.z, w.z, xdot4<SG>(w.w, w.w, rdlane(qq, pc)))));
+              const int vq = xdot4<SG>(w.x, qx, xdot4<SG>(w.y, qy, xdot4<SG>(w.z, qz, xdot4<SG>(w.w, qv, 0))));
+              const int next = sum + vv - 2 * vq;                 // < 2^31: 1024 x 255^2 = 66 585 600
+              if (__ballot((uint32_t)lane < np && next > (1 << 24)) == 0ull) { sum = next; continue; }
+              chain = true;
+              acc = (float)sum;
+            }
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w}, qs[4] = {qx, qy, qz, qv};
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+#pragma unroll
+              for (int b = 0; b < 4; ++b) {
+                const int vb = SG ? (int)(int8_t)(ww[d] >> (8 * b)) : (int)((ww[d] >> (8 * b)) & 255u);
+                const int qb = SG ? (int)(int8_t)(qs[d] >> (8 * b)) : (int)((qs[d] >> (8 * b)) & 255u);
+                const float diff = (float)(vb - qb);              // orc_exact_dist: the subtraction in int, then to float
+                acc = __builtin_fmaf(diff, diff, acc);
+              }
+            }
+          }
+        }
+      }
+      if (!chain) acc = (float)sum;
+    }
+    if ((uint32_t)lane < np) dist[i0 + (uint32_t)lane] = acc;
+  }
+}
+#define EXACT_KERNEL search_exact_wide_kernel
+// the float instance keeps 16 query registers across the whole loop and needs a few registers more than the 128 that 16 waves per CU leave a
+// wave: 12 waves per CU, no scratch (bang_search_exact_wide_geometry reads both figures off the instance)
+#define EXACT_MAX_THREADS(DT) ((DT) == BANG_F32 ? 768 : 1024)
+#else
+#define EXACT_KERNEL search_exact_kernel
+#define EXACT_MAX_THREADS(DT) 1024
+#endif
+
+template <int DT>
+__global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const ExactArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t xlds[];
   const bang_search_params& p = a.p;
   const int lane = lane_id();
@@ -157,6 +284,19 @@ __global__ __launch_bounds__(1024) void search_exact_kernel(const ExactArgs a) {
     const uint32_t D = p.rr_D;
     u32x4a qw = {0u, 0u, 0u, 0u};
     int qq = 0;
+#ifdef BANG_EXACT_WIDE
+    float qr[EXACT_QREGS];
+    if (DT == BANG_F32) {
+      const float GAS* qsrc = (const float GAS*)p.rr_queries + qabs * D;
+#pragma unroll
+      for (int t = 0; t < EXACT_QREGS; ++t) { const uint32_t j = (uint32_t)t * 64u + (uint32_t)lane; qr[t] = qsrc[j < D ? j : 0u]; }
+    } else {
+#pragma unroll
+      for (int t = 0; t < EXACT_QREGS; ++t) qr[t] = 0.0f;
+      qw = *(const u32x4a GAS*)((const uint8_t GAS*)p.rr_queries + qabs * D + 16u * ((uint32_t)lane < (D >> 4) ? (uint32_t)lane : 0u));
+      qq = xdot4<DT == BANG_I8>(qw.x, qw.x, xdot4<DT == BANG_I8>(qw.y, qw.y, xdot4<DT == BANG_I8>(qw.z, qw.z, xdot4<DT == BANG_I8>(qw.w, qw.w, 0))));
+    }
+#else
     uint32_t G = 1;
     float qr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (DT == BANG_F32) {
@@ -168,6 +308,7 @@ __global__ __launch_bounds__(1024) void search_exact_kernel(const ExactArgs a) {
       qw = *(const u32x4a GAS*)((const uint8_t GAS*)p.rr_queries + qabs * D + 16u * ((uint32_t)lane & (G - 1u)));
       qq = xdot4<DT == BANG_I8>(qw.x, qw.x, xdot4<DT == BANG_I8>(qw.y, qw.y, xdot4<DT == BANG_I8>(qw.z, qw.z, xdot4<DT == BANG_I8>(qw.w, qw.w, 0))));
     }
+#endif
 
     // ---------------- per-query state (bang_init :440-489): candidate log = [MEDOID], seed list [MEDOID, adj(MEDOID)...]
     uint32_t iter = 1, w_n = 0, cc = 1, mark = 0x01010101u, evals = 0, fetched = 0;
@@ -226,8 +367,12 @@ __global__ __launch_bounds__(1024) void search_exact_kernel(const ExactArgs a) {
 
       // ---------------- exact distances (CANON 10: replaces K2) ----------------
       if (n > 0) {
+#ifdef BANG_EXACT_WIDE
+        exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, scratch + EXACT_SCRATCH_WORDS, qr, qw, qq, lane);
+#else
         if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, sc, n, sdist, qr, lane);
         else exact_dist8<DT == BANG_I8>(graph, entry_len, G, sc, n, sdist, qw, qq, lane);
+#endif
       }
       wave_sync();
       const float d0 = ((uint32_t)lane < n) ? sdist[lane] : BIG_DIST;
@@ -315,37 +460,39 @@ __global__ __launch_bounds__(1024) void search_exact_kernel(const ExactArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------
 // launcher
 // ---------------------------------------------------------------------------------------------------------------------
+#ifdef BANG_EXACT_WIDE
+#define EXACT_EXTRA_WORDS EXACT_TILE_WORDS                        // the wave's row tile, behind its scratch
+#define EXACT_GEOMETRY bang_search_exact_wide_geometry
+#else
+#define EXACT_EXTRA_WORDS 0u
+#define EXACT_GEOMETRY bang_search_exact_geometry
+#endif
+
 static const void* exact_instance(int dtype) {
-  if (dtype == BANG_U8) return (const void*)search_exact_kernel<BANG_U8>;
-  if (dtype == BANG_I8) return (const void*)search_exact_kernel<BANG_I8>;
-  if (dtype == BANG_F32) return (const void*)search_exact_kernel<BANG_F32>;
+  if (dtype == BANG_U8) return (const void*)EXACT_KERNEL<BANG_U8>;
+  if (dtype == BANG_I8) return (const void*)EXACT_KERNEL<BANG_I8>;
+  if (dtype == BANG_F32) return (const void*)EXACT_KERNEL<BANG_F32>;
   return nullptr;
 }
 
-static uint32_t exact_wave_bytes(uint32_t L) { return (exact_wl_words(L) + EXACT_SCRATCH_WORDS) * 4u; }
-
-// Vector layouts the kernel evaluates: those of the fused re-rank (bang_search_can_rerank) -- 8-bit: D % 16 == 0, D / 16 a power of two;
-// float: D % 4 == 0; D <= 256; a 4-byte-aligned entry stride; no MIPS padding.
-static int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry_len, uint32_t L) {
-  if (L == 0 || L > BANG_MAX_L) return 0;
-  return bang_search_can_rerank(dtype, D, entry_len, 0);
-}
+static uint32_t exact_wave_bytes(uint32_t L) { return (exact_wl_words(L) + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS) * 4u; }
 
 // Waves per CU: what the instance's registers allow (512 per SIMD lane, allocated in granules of 8, four SIMDs, at most 8 waves per SIMD),
-// what 160 KB of LDS hold (2L + L/4 + 144 words per wave), at most 32.  The three instances compile to 97-98 VGPRs and no scratch (the merge
-// of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves per SIMD, 16 per CU -- one workgroup of
-// 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  A batch of fewer than 16 queries per CU is spread over all CUs with fewer
-// waves each (a wave's iteration is latency bound, as in bang_search_geometry).
-extern "C" int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups,
-                                          uint32_t* waves) {
+// what 160 KB of LDS hold (2L + L/4 + 144 words per wave; the wide instances 1024 more), at most 32.  The three narrow instances compile to
+// 97-98 VGPRs and no scratch (the merge of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves
+// per SIMD, 16 per CU -- one workgroup of 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  The wide instances (at most 128
+// VGPRs, no scratch: DESIGN.md section 4.6) run 16 waves per CU as well, up to L = 704.  A batch of fewer than 16 queries per CU is spread
+// over all CUs with fewer waves each (a wave's iteration is latency bound, as in bang_search_geometry).
+extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   const void* k = exact_instance(dtype);
   if (!k || L == 0 || L > BANG_MAX_L) { bang_set_error("distance = 1: bad dtype / L"); return BANG_ERR_ARG; }
-  static int regs[3][BANG_MAX_DEVICES] = {};                     // per instance and device, read once
+  static int regs[3][BANG_MAX_DEVICES] = {}, max_waves_wg[3][BANG_MAX_DEVICES] = {};   // per instance and device, read once
   const int dev = current_device();
   if (regs[dtype][dev] == 0) {
     hipFuncAttributes at;
     HIP_TRY(hipFuncGetAttributes(&at, k));
+    max_waves_wg[dtype][dev] = at.maxThreadsPerBlock >= WAVE ? at.maxThreadsPerBlock / WAVE : 16;
     regs[dtype][dev] = at.numRegs > 0 ? at.numRegs : 128;
   }
   const uint32_t vg = (uint32_t)regs[dtype][dev];
@@ -358,6 +505,7 @@ extern "C" int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uin
   if (per_cu > 32u) per_cu = 32u;
   if (per_cu == 0) { bang_set_error("distance = 1: one wave's worklist does not fit LDS at L=%u", L); return BANG_ERR_UNSUPPORTED; }
   uint32_t W = per_cu < 16u ? per_cu : 16u;
+  if (W > (uint32_t)max_waves_wg[dtype][dev]) W = (uint32_t)max_waves_wg[dtype][dev];     // (the instance's launch bound)
   const uint32_t wgs_per_cu = per_cu / W;
   if (max_waves && max_waves < W) W = max_waves;
   const uint32_t cus = (uint32_t)num_cus();
@@ -378,29 +526,15 @@ extern "C" int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uin
   return BANG_OK;
 }
 
-extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
-  if (!p) return BANG_ERR_ARG;
-  if (p->Q == 0) return BANG_OK;
-  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("distance = 1: bad R/L"); return BANG_ERR_ARG; }
-  if (!p->d_graph || p->row_layout != 0) { bang_set_error("distance = 1: the exact-distance kernel needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
-  if (!p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt || !p->d_next_query || !p->rr_queries || !p->rr_ids_out || !p->rr_dists_out) {
-    bang_set_error("distance = 1: null buffer"); return BANG_ERR_ARG;
-  }
-  if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("distance = 1: bad iteration cap"); return BANG_ERR_ARG; }
-  if (p->rr_k == 0 || p->rr_k > p->L || p->rr_Q_total < p->rr_q0 + p->Q) { bang_set_error("distance = 1: bad k / result rows"); return BANG_ERR_ARG; }
-  if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len, p->L) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
-      (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
-    bang_set_error("distance = 1: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0 with D / 16 a power "
-                   "of two, float vectors D %% 4 == 0; D <= 256", p->rr_dtype, p->rr_D, (unsigned long long)p->entry_len);
-    return BANG_ERR_UNSUPPORTED;
-  }
+// one launch of this translation unit's instances (the arguments are checked: bang_k_search_exact)
+static int exact_launch(const bang_search_params* p, void* stream) {
   uint32_t grid_n = 0, waves = 0;
-  const int rc = bang_search_exact_geometry((int)p->rr_dtype, p->L, p->Q, p->max_wgs, p->max_waves, &grid_n, &waves);
+  const int rc = EXACT_GEOMETRY((int)p->rr_dtype, p->L, p->Q, p->max_wgs, p->max_waves, &grid_n, &waves);
   if (rc != BANG_OK) return rc;
   ExactArgs a;
   a.p = *p;
   a.wl_words = exact_wl_words(p->L);
-  a.wave_words = a.wl_words + EXACT_SCRATCH_WORDS;
+  a.wave_words = a.wl_words + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS;
   const size_t lds = (size_t)waves * a.wave_words * 4u;
   const void* k = exact_instance((int)p->rr_dtype);
   static bool attr_done[3][BANG_MAX_DEVICES] = {};
@@ -411,9 +545,47 @@ extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
   }
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(grid_n), block(waves * WAVE);
-  if (p->rr_dtype == BANG_F32) hipLaunchKernelGGL(search_exact_kernel<BANG_F32>, grid, block, lds, st, a);
-  else if (p->rr_dtype == BANG_I8) hipLaunchKernelGGL(search_exact_kernel<BANG_I8>, grid, block, lds, st, a);
-  else hipLaunchKernelGGL(search_exact_kernel<BANG_U8>, grid, block, lds, st, a);
+  if (p->rr_dtype == BANG_F32) hipLaunchKernelGGL(EXACT_KERNEL<BANG_F32>, grid, block, lds, st, a);
+  else if (p->rr_dtype == BANG_I8) hipLaunchKernelGGL(EXACT_KERNEL<BANG_I8>, grid, block, lds, st, a);
+  else hipLaunchKernelGGL(EXACT_KERNEL<BANG_U8>, grid, block, lds, st, a);
   HIP_TRY(hipGetLastError());
   return BANG_OK;
 }
+
+#ifdef BANG_EXACT_WIDE
+// called by bang_k_search_exact with its arguments checked, for the layouts the narrow instances do not evaluate
+extern "C" int bang_k_search_exact_wide(const bang_search_params* p, void* stream) {
+  if (!p || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len)) return BANG_ERR_ARG;
+  return exact_launch(p, stream);
+}
+#else
+// Vector layouts the kernels evaluate.  8-bit: D % 16 == 0; float: D % 4 == 0; D <= 1024; a 4-byte-aligned entry stride; no MIPS padding.
+// Those of the fused re-rank (bang_search_can_rerank: D <= 256, 8-bit D / 16 a power of two) run on the narrow instances, the others on the
+// wide ones.
+extern "C" int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry_len) {
+  if (D == 0 || D > BANG_EXACT_MAX_D || (entry_len & 3u)) return 0;
+  if (dtype == BANG_F32) return D % 4u == 0 && entry_len >= 4ull * D;
+  if (dtype == BANG_U8 || dtype == BANG_I8) return D % 16u == 0 && entry_len >= D;
+  return 0;
+}
+
+extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (p->Q == 0) return BANG_OK;
+  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("distance = 1: bad R/L"); return BANG_ERR_ARG; }
+  if (!p->d_graph || p->row_layout != 0) { bang_set_error("distance = 1: the exact-distance kernel needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
+  if (!p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt || !p->d_next_query || !p->rr_queries || !p->rr_ids_out || !p->rr_dists_out) {
+    bang_set_error("distance = 1: null buffer"); return BANG_ERR_ARG;
+  }
+  if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("distance = 1: bad iteration cap"); return BANG_ERR_ARG; }
+  if (p->rr_k == 0 || p->rr_k > p->L || p->rr_Q_total < p->rr_q0 + p->Q) { bang_set_error("distance = 1: bad k / result rows"); return BANG_ERR_ARG; }
+  if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
+      (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
+    bang_set_error("distance = 1: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0, float vectors "
+                   "D %% 4 == 0; D <= %u; an entry stride divisible by 4", p->rr_dtype, p->rr_D, (unsigned long long)p->entry_len, BANG_EXACT_MAX_D);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->entry_len, 0)) return exact_launch(p, stream);
+  return bang_k_search_exact_wide(p, stream);
+}
+#endif

@@ -448,9 +448,12 @@ int bang_k_rerank(const void* d_vec_base, uint64_t vec_stride, const void* d_med
  * (u64) / rr_dists_out [k][rr_Q_total] at row rr_q0 + q.  Uses Q, R, L, medoid, cap_iter, max_wgs, max_waves, d_seed, d_graph, entry_len,
  * vec_bytes, d_bloom (zeroed), d_cand_ids / d_cand_cnt (the expanded nodes, [0] = MEDOID), d_qstats, d_qiters, d_next_query (zeroed), d_abort,
  * d_ktime, n_nodes and rr_queries (raw queries), rr_dtype, rr_D, rr_k, rr_q0, rr_Q_total, rr_ids_out, rr_dists_out; the PQ fields and rr_vec_* are
- * ignored.  Vector layouts: those of the fused re-rank (bang_search_can_rerank with rr_vec_stride = entry_len); others are BANG_ERR_UNSUPPORTED. */
+ * ignored.  Vector layouts: bang_search_exact_supported(rr_dtype, rr_D, entry_len); others are BANG_ERR_UNSUPPORTED.  The layouts of the fused re-rank
+ * (bang_search_can_rerank with rr_vec_stride = entry_len) run on the instances that share its arithmetic, the others -- D up to BANG_EXACT_MAX_D,
+ * 8-bit vectors with any D / 16 -- on the wide instances (rows fetched cooperatively through an LDS tile; 8-bit sums leave the integers at 2^24 and
+ * continue as orc_exact_dist's float chain).  Same bits as bang_k_rerank either way. */
 int bang_k_search_exact(const bang_search_params* p, void* stream);
-/* grid of a bang_k_search_exact launch over Q queries for vectors of dtype at worklist length L: workgroups and waves per workgroup (as many
+/* grid of a bang_k_search_exact launch (layouts of bang_search_can_rerank) over Q queries for vectors of dtype at worklist length L: workgroups and waves per workgroup (as many
  * waves per CU as the instance's registers and LDS allow, <= 16 per workgroup; max_wgs / max_waves: caps if nonzero; a batch of fewer than a
  * workgroup-full of queries per CU is spread over all CUs) */
 int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
@@ -464,6 +467,11 @@ int bang_k_search_inmem(const bang_search_params* p, void* stream);
 /* grid of a bang_k_search_inmem launch: that of bang_search_geometry's self-paced form (host_paced = 0) */
 int bang_search_inmem_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
                                uint32_t* workgroups, uint32_t* waves);
+
+/* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
+ * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
+#define BANG_EXACT_MAX_D 1024u
+int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry_len);
 
 #ifdef __cplusplus
 }
