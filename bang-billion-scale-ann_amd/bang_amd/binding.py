@@ -62,6 +62,7 @@ class SearchParams(C.Structure):
         ("n_nodes", C.c_uint32), ("summ_iters", C.c_uint32), ("spec_rows", C.c_uint32),
         ("rr_queries", C.c_void_p), ("rr_vec_base", C.c_void_p), ("rr_vec_stride", C.c_uint64), ("rr_ids_out", C.c_void_p), ("rr_dists_out", C.c_void_p),
         ("rr_dtype", C.c_uint32), ("rr_D", C.c_uint32), ("rr_k", C.c_uint32), ("rr_q0", C.c_uint32), ("rr_Q_total", C.c_uint32),
+        ("d_lut", C.c_void_p),               # bang_k_search_lut only (appended last)
     ]
 
 
@@ -520,6 +521,25 @@ class IterState:
         d_next = DeviceBuffer(64)
         sp.d_qiters, sp.d_next_query = d_iters.ptr, d_next.ptr
         _check(lib().bang_k_search(C.byref(sp), None), "bang_k_search")
+        sync()
+        return d_iters.download(np.uint32, (self.Q,))
+
+    def run_search_lut(self):
+        """The same on the LUT path (use_lut=True, device_graph=True): ONE launch of bang_k_search_lut behind K1.  Fills the candidate log;
+        returns the per-query iteration counts."""
+        assert self.d_graph is not None and self.psz == 0
+        ix = self.ix
+        sp = SearchParams()
+        sp.Q, sp.R, sp.m, sp.L, sp.medoid, sp.cap_iter = self.Q, ix.R, ix.m, self.L, ix.medoid, self.L + EXTRA_ITERS - 1
+        sp.d_seed, sp.d_codes, sp.d_lut = self.d_seed.ptr, self.d_codes.ptr, self.d_lut.ptr
+        sp.d_graph, sp.entry_len = self.d_graph.ptr, ix.entry_len
+        sp.vec_bytes = ix.D * np.dtype(NP_DTYPE[ix.dtype]).itemsize
+        sp.n_nodes = ix.N
+        sp.d_bloom, sp.d_cand_ids, sp.d_cand_cnt, sp.d_qstats = self.d_bloom.ptr, self.d_cand_ids.ptr, self.d_cand_cnt.ptr, self.d_qstats.ptr
+        d_iters = DeviceBuffer(self.Q * 4)
+        d_next = DeviceBuffer(64)
+        sp.d_qiters, sp.d_next_query, sp.d_abort = d_iters.ptr, d_next.ptr, d_next.ptr + 4
+        _check(lib().bang_k_search_lut(C.byref(sp), None), "bang_k_search_lut")
         sync()
         return d_iters.download(np.uint32, (self.Q,))
 

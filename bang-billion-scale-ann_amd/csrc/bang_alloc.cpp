@@ -143,6 +143,10 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     }
     e->search_inmem = true;
   }
+  // LUT path (psz == 0: wide chunks, a pivot table too large for LDS, pq = 1) with the graph in HBM: the query-resident kernel of
+  // bang_search_lut.hip, where search = 1 was asked for explicitly -- "auto" keeps the launch-per-iteration loop on these layouts
+  e->search_lut = dev_graph && e->persistent != 0 && e->search_opt == 1 && e->psz == 0 && !e->search_exact &&
+                  bang_search_lut_supported(e->m, (uint32_t)e->L) != 0;
   // graph in host RAM: the host-paced form of the same kernel, where the walker can write device memory (BAR mode)
   e->search_host = false;
   if (!dev_graph && !e->search_v2 && persist_want && e->use_flag && e->stage_mode_eff == 2 && e->search_opt != 0 && e->psz != 0) {
@@ -242,7 +246,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   int nl = e->lanes_opt;
   if (nl <= 0) nl = dev_graph ? 1 : std::max(1, std::min(4, Q / 512));   // measured best on a 16-CPU-quota MI355X box
   nl = std::min(nl, Q);
-  if (e->search_v2 || e->search_host || e->search_exact) nl = 1;   // the search kernel's waves are the unit of overlap, not lanes
+  if (e->search_v2 || e->search_host || e->search_exact || e->search_lut) nl = 1;   // the search kernel's waves are the unit of overlap, not lanes
   if (e->search_host && e->threads_opt <= 0) e->threads_eff = std::max(1, std::min(12, usable_cpus() - 2));
   else if (e->threads_opt <= 0) e->threads_eff = (dev_graph || e->search_v2) ? 1 : std::max(1, std::min(4, (usable_cpus() - 2) / std::max(1, nl)));   // leave 2 CPUs for the caller + HIP runtime threads: a cgroup that exceeds its quota gets throttled for the rest of the period
   else e->threads_eff = e->threads_opt;
@@ -283,7 +287,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
         HIP_TRY(hipHostGetDevicePointer((void**)&ln.qmap_dev[b], ln.qmap_host[b], 0));
       }
     }
-    if (e->search_v2 || e->search_host || e->search_exact) {
+    if (e->search_v2 || e->search_host || e->search_exact || e->search_lut) {
       BANG_TRY(dmalloc(&ln.d_pcnt, 16));
       HIP_TRY(hipMemset(ln.d_pcnt, 0, 64));
     }
@@ -310,8 +314,8 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     else if (!dev_graph) fprintf(stderr, "[bang] walker threads not pinned\n");
   }
   if (env_flag("BANG_DEBUG"))
-    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d semantics=%d fp_direct=%d vec_on_device=%d\n", Q, nl,
-            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->search_inmem, (int)e->fp_direct, (int)e->vec_on_device);
+    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d/%d semantics=%d fp_direct=%d vec_on_device=%d\n", Q, nl,
+            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->search_lut, (int)e->search_inmem, (int)e->fp_direct, (int)e->vec_on_device);
   start_threads(e);
   return BANG_OK;
 }

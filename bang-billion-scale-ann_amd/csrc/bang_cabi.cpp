@@ -281,7 +281,7 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
     s.sync_ms += ln.sync_ms; s.enqueue_ms += ln.enqueue_ms;
     s.h2d_bytes += ln.h2d_bytes.load();
   }
-  s.persistent = (e->search_v2 || e->search_host || e->search_exact) ? 1 : 0;
+  s.persistent = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
   s.vectors_on_device = e->vec_on_device ? 1 : 0;
   s.graph_mode = (uint64_t)e->graph_mode;
   s.lanes = (uint64_t)nl;
@@ -289,8 +289,8 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   s.wg_queries = e->search_host ? e->sv_W * e->sv_C : 0;
   s.pacing_groups = e->search_host ? e->sv_NG : 0;
   s.graph_pull = (e->pull && e->search_v2 && e->graph_mode != BANG_GRAPH_DEVICE) ? 1 : 0;
-  s.workgroups = e->search_host ? (uint64_t)e->sv_G : (e->search_v2 || e->search_exact) ? (uint64_t)std::min(Q, bang_num_cus()) : 0;
-  s.search_kernel = (e->search_v2 || e->search_host || e->search_exact) ? 1 : 0;
+  s.workgroups = e->search_host ? (uint64_t)e->sv_G : (e->search_v2 || e->search_exact || e->search_lut) ? (uint64_t)std::min(Q, bang_num_cus()) : 0;
+  s.search_kernel = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
   s.rerank_fused = e->rerank_fused ? 1 : 0;
   s.walker_rows = (e->search_host && e->walker_rows) ? 1 : 0;
   s.code_stride = e->code_stride;
@@ -397,7 +397,7 @@ extern "C" int bang_get_query_counters(bang_engine_t* e, uint32_t* dist_evals, u
   }
   if (candidates) HIP_TRY(hipMemcpy(candidates, e->d_cand_cnt, Q * 4, hipMemcpyDeviceToHost));
   if (iterations) {
-    if ((e->search_v2 || e->search_host || e->search_exact) && e->h_qiters.size() >= Q) memcpy(iterations, e->h_qiters.data(), Q * 4);
+    if ((e->search_v2 || e->search_host || e->search_exact || e->search_lut) && e->h_qiters.size() >= Q) memcpy(iterations, e->h_qiters.data(), Q * 4);
     else memset(iterations, 0, Q * 4);
   }
   return BANG_OK;

@@ -221,6 +221,8 @@ struct bang_engine {
   bool search_exact = false;           // resolved at bang_alloc: distance = 1 -- the exact-distance search kernel (bang_search_exact.hip)
   int semantics = 0;                   // option "semantics": 0 = BANG_Base's walk (default), 1 = BANG_Inmemory's (parent after the merge, cap L + 119)
   bool search_inmem = false;           // resolved at bang_alloc: semantics = 1 -- search_v2 on bang_k_search_inmem; candidate log L + 120
+  bool search_lut = false;             // resolved at bang_alloc: LUT path (psz == 0), graph in HBM, search = 1 given explicitly -- K1, then ONE launch of
+                                       // the LUT-path search kernel (bang_search_lut.hip), then the re-rank launch
   uint32_t sv_G = 0, sv_W = 0, sv_C = 1;   // its grid for the running query: workgroups, waves per workgroup, query contexts per wave
   uint32_t sv_GS = 8, sv_NG = 0;           // waves per pacing group; pacing groups = workgroups x groups per workgroup x contexts
   uint32_t* d_srows = nullptr;         // fine-grained device memory [groups*16][64]: adjacency ids per slot, written through the BAR

@@ -196,6 +196,25 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     ENQ_END();
     ++ln.front_launches;
     iter = cap_iter;                                                         // refined from the per-query counts below
+  } else if (e->search_lut) {
+    // LUT path, graph in HBM: ONE launch of the LUT-path search kernel behind K1; its candidate log feeds the re-rank launch below
+    LANE_HIP(hipMemsetAsync(ln.d_pcnt, 0, 64, ln.s_main));
+    bang_search_params sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.Q = ln.nq; sp.R = e->R; sp.m = e->m; sp.L = (uint32_t)e->L; sp.medoid = (uint32_t)e->medoid; sp.cap_iter = cap_iter;
+    sp.d_seed = e->d_seed; sp.d_codes = e->d_codes; sp.code_stride = e->code_stride; sp.d_lut = p.d_lut;
+    sp.d_graph = e->d_graph; sp.entry_len = e->entry_len; sp.vec_bytes = (uint32_t)vb;
+    sp.d_bloom = p.d_bloom; sp.d_cand_ids = p.d_cand_ids; sp.d_cand_cnt = p.d_cand_cnt; sp.d_qstats = p.d_qstats;
+    sp.d_qiters = e->d_qiters + ln.q0; sp.d_next_query = ln.d_pcnt; sp.d_abort = ln.d_pcnt + 1; sp.n_nodes = e->N;
+    sp.d_ktime = ktime_slot(e, ln);
+    sp.max_wgs = (uint32_t)std::max(0L, env_long("BANG_SEARCH_MAX_WGS", 0));          // experiment / test knobs
+    sp.max_waves = (uint32_t)std::max(0L, env_long("BANG_SEARCH_MAX_WAVES", 0));
+    e->rerank_fused = false;
+    ENQ_BEGIN();
+    BANG_TRY(bang_k_search_lut(&sp, ln.s_main));
+    ENQ_END();
+    ++ln.front_launches;
+    iter = cap_iter;                                                         // refined from the per-query counts below
   } else if (e->search_v2) {
     // graph resident in HBM: ONE launch of the query-resident search kernel; no host involvement until the re-rank
     LANE_HIP(hipMemsetAsync(ln.d_pcnt, 0, 64, ln.s_main));
@@ -437,8 +456,8 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   // A copy into the caller's pageable arrays is staged by the runtime and costs ~20 us before the first byte moves, per copy.  The
   // results come back whole in ONE asynchronous copy into the pinned mirror and are handed out with memcpy (measured: 70 -> 17 us for
   // a 1 250-query shard, 92-107 -> 73-82 us for the 10 K batch); only a very large batch keeps the direct, runtime-pipelined copies.
-  if ((e->search_host || e->search_v2 || e->search_exact) && !results_direct) LANE_HIP(hipMemcpyAsync(h_abort, ln.d_pcnt + 1, 4, hipMemcpyDeviceToHost, ln.s_main));
-  const bool iters = e->search_v2 || e->search_host || e->search_exact;
+  if ((e->search_host || e->search_v2 || e->search_exact || e->search_lut) && !results_direct) LANE_HIP(hipMemcpyAsync(h_abort, ln.d_pcnt + 1, 4, hipMemcpyDeviceToHost, ln.s_main));
+  const bool iters = e->search_v2 || e->search_host || e->search_exact || e->search_lut;
   if (to_device) {
     const bool in_place = results_in_launch && whole;           // (the fused re-rank / the exact kernel wrote into the caller's buffers)
     if (!in_place)

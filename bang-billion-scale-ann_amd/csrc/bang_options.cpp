@@ -30,7 +30,7 @@ static const OptionDef kOptions[] = {
      "0 host | 1 device | 2 auto (default): where graph + vectors live; auto = HBM when they fit next to the PQ codes with 16 GB to spare "
      "(environment: host | device | auto)"},
     {"device", "BANG_DEVICE", &bang_engine::device, 0, 1 << 20, INT, BEFORE_LOAD, "HIP device ordinal"},
-    {"pq", "BANG_PQ", &bang_engine::pq_mode, 0, 1, INT, BEFORE_LOAD, "0 = pivot table resident in LDS (default when it fits), 1 = LUT path (K1 + K2)"},
+    {"pq", "BANG_PQ", &bang_engine::pq_mode, 0, 1, INT, BEFORE_LOAD, "0 = pivot table resident in LDS (default when it fits), 1 = LUT path (K1 + K2; with search = 1 and graph = device: bang_k_search_lut)"},
     {"pq_ragged", "BANG_PQ_RAGGED", &bang_engine::pq_ragged, 0, 1, FLAG, BEFORE_LOAD, "2-dim/1-dim PQ layouts: exact-size pivot table where a kernel instance exists (default 1)"},
     {"code_stride", "BANG_CODE_STRIDE", &bang_engine::code_stride_opt, -1, 4096, INT, BEFORE_LOAD,
      "bytes between PQ code rows in HBM: 0 = packed as in <p>_pq_compressed.bin (m), -1 = auto: padded to the next power of two (m = 70 -> 128) "
@@ -50,7 +50,8 @@ static const OptionDef kOptions[] = {
     {"walker", "BANG_WALKER", &bang_engine::walker_opt, 0, 1, INT, BEFORE_ALLOC,
      "host graph loaded in pull mode: 1 = the C++ walker threads serve the adjacency rows to the host-paced search kernel (the reference's data flow, "
      "bang_search.cu:771-813) -- reading the same 256-byte pull rows the kernel would pull itself, so no resident graph image is needed; 0 = the kernel pulls (default)"},
-    {"search", "BANG_SEARCH", &bang_engine::search_opt, -1, 1, INT, BEFORE_ALLOC, "1 = the query-resident search kernel (bang_k_search), 0 = the per-iteration kernels, -1 = auto"},
+    {"search", "BANG_SEARCH", &bang_engine::search_opt, -1, 1, INT, BEFORE_ALLOC, "1 = the query-resident search kernel (bang_k_search; LUT-path indexes with the graph in HBM: bang_k_search_lut, taken only when 1 is given), "
+     "0 = the per-iteration kernels, -1 = auto (LUT-path indexes keep the per-iteration kernels)"},
     {"distance", "BANG_DISTANCE", &bang_engine::distance, 0, 1, INT, BEFORE_ALLOC,
      "0 = PQ distances in the walk + exact re-rank (default), 1 = exact distances in the walk, results = the first k worklist entries (no re-rank; "
      "the reference's BANG_Exactdistance).  1 needs graph = device, search != 0, persistent != 0, L2 distance and a vector layout of "

@@ -1,0 +1,353 @@
+// bang_search_lut.hip -- the query-resident search kernel for indexes on the LUT path (psz == 0: chunks wider than 8 dimensions, a pivot table
+// that does not fit LDS, or option pq = 1): the BANG_Base search loop as bang_search_exact.hip runs it, with every neighbour's distance the PQ
+// estimate gathered from the query's look-up table (K2, compute_neighborDist_par bang_search.cu:1201-1241) and the candidate log as its result
+// (the re-rank launch bang_k_rerank follows, as behind bang_k_search without the fused re-rank).
+//
+//  * Query-resident, self-paced: a wave owns one query from its first iteration to its last (worklist + survivors in LDS), then pulls the
+//    next unstarted query from *d_next_query.  Graph entries resident in HBM (d_graph, row_layout 0).  Filter, eager parent, merge, per-query
+//    activity, the L + 49 cap and the guard against adjacency ids >= n_nodes are those of search_exact_kernel, on the same device code
+//    (bang_worklist.h, bang_device.h).
+//  * Distances: one lane per survivor.  The lane walks its code row 16 chunks at a time -- a 16-byte window read from the row's 4-byte-aligned
+//    base with the non-temporal hint (a row is read once), the next window in flight meanwhile; rows that are not dword-aligned (m = 65, m = 5)
+//    are shifted into place with v_alignbyte -- and gathers the 16 table entries lut[c][code_c] together with ordinary cached loads (the query
+//    re-reads its table every iteration).  The sum is pq_distance_lut's, bit for bit: eight partial sums s[c % 8] in ascending c, the tail
+//    c + l < m added the same way, then ((s0+s1)+(s2+s3)) + ((s4+s5)+(s6+s7)).  Any m, any code stride; one instance, no dtype.
+//    The table d_lut + q * m * 256 (K1, bang_k_lut_build) is read-only for the launch.  A row is over-read by at most 18 bytes (d_codes has
+//    256 bytes of slack).
+//  * LDS per wave: 2L + L/4 + 144 words, as the exact kernel; the launch is bound by VGPRs and bang_search_lut_geometry reads the instance's
+//    register count.
+//
+// Reference line numbers: the reference's BANG_Base/bang_search.cu.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stddef.h>
+
+#include "bang_c.h"
+#include "bang_internal.h"
+#include "bang_device.h"
+#include "bang_worklist.h"
+
+#define LUT_SCRATCH_WORDS 144u       // sd/ti [72] + td/compaction [72] (the survivors' distances, then the sort)
+#define LUT_MAX_LDS (160u * 1024u)
+
+struct LutArgs {
+  bang_search_params p;
+  uint32_t wave_words;               // LDS words per wave: worklist + scratch
+  uint32_t wl_words;                 // LDS words of the worklist (2L + ceil(L/4), rounded to 4)
+};
+
+static inline uint32_t lut_wl_words(uint32_t L) { return (2u * L + (L + 3u) / 4u + 3u) & ~3u; }
+static inline uint32_t lut_wave_bytes(uint32_t L) { return (lut_wl_words(L) + LUT_SCRATCH_WORDS) * 4u; }
+
+__device__ __forceinline__ uint32_t code_byte(const uint32_t (&b)[4], int l) { return (b[l >> 2] >> (8 * (l & 3))) & 255u; }
+
+// PQ distances of the n survivors (ids in LDS: sid[0, n)) -> dist[0, n) in LDS; lane i evaluates survivor i0 + i.  Every lane of the wave
+// executes: a lane without a survivor evaluates sid[0] again and stores nothing.
+__device__ __forceinline__ void lut_dist(const uint8_t GAS* codes, uint32_t stride, uint32_t m, const float GAS* lut, const uint32_t* sid,
+                                         uint32_t n, float* dist, int lane) {
+  const uint32_t nwin = (m + 3u + 15u) >> 4;                       // 16-byte windows a row can touch from its aligned base
+  for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                      // (uniform; a second pass for the 65th id of the seed list only)
+    const uint32_t i = i0 + (uint32_t)lane;
+    const uint32_t id = sid[i < n ? i : 0u];
+    const uint64_t a = (uint64_t)id * stride;                      // 64-bit row offset :1232
+    const uint32_t sh = (uint32_t)a & 3u;
+    const u32x4a GAS* row = (const u32x4a GAS*)(codes + (a & ~3ull));
+    u32x4a cur = __builtin_nontemporal_load(row);
+    float s[8];
+#pragma unroll
+    for (int l = 0; l < 8; ++l) s[l] = 0.0f;
+    uint32_t c = 0, w = 0;
+    for (; c + 16u <= m; c += 16u, ++w) {                          // (uniform) two groups of eight chunks
+      const u32x4a nxt = __builtin_nontemporal_load(row + (w + 1u < nwin ? w + 1u : w));
+      const uint32_t b[4] = {__builtin_amdgcn_alignbyte(cur.y, cur.x, sh), __builtin_amdgcn_alignbyte(cur.z, cur.y, sh),
+                             __builtin_amdgcn_alignbyte(cur.w, cur.z, sh), __builtin_amdgcn_alignbyte(nxt.x, cur.w, sh)};
+      const float GAS* lc = lut + (size_t)c * 256u;
+      float t[16];
+#pragma unroll
+      for (int l = 0; l < 16; ++l) t[l] = lc[(uint32_t)l * 256u + code_byte(b, l)];
+#pragma unroll
+      for (int l = 0; l < 8; ++l) s[l] = s[l] + t[l];
+#pragma unroll
+      for (int l = 0; l < 8; ++l) s[l] = s[l] + t[8 + l];
+      cur = nxt;
+    }
+    const uint32_t r = m - c;                                      // 0..15 chunks left: a group of eight if r >= 8, then the tail
+    if (r != 0u) {                                                 // (uniform)
+      const u32x4a nxt = __builtin_nontemporal_load(row + (w + 1u < nwin ? w + 1u : w));
+      const uint32_t b[4] = {__builtin_amdgcn_alignbyte(cur.y, cur.x, sh), __builtin_amdgcn_alignbyte(cur.z, cur.y, sh),
+                             __builtin_amdgcn_alignbyte(cur.w, cur.z, sh), __builtin_amdgcn_alignbyte(nxt.x, cur.w, sh)};
+      const float GAS* lc = lut + (size_t)c * 256u;
+      float t[16];
+#pragma unroll
+      for (int l = 0; l < 16; ++l) {                               // (a chunk behind the row's end: chunk c again, never added)
+        const bool in = (uint32_t)l < r;
+        t[l] = lc[in ? (uint32_t)l * 256u + code_byte(b, l) : code_byte(b, 0)];
+      }
+#pragma unroll
+      for (int l = 0; l < 8; ++l) s[l] = (uint32_t)l < r ? s[l] + t[l] : s[l];
+#pragma unroll
+      for (int l = 0; l < 8; ++l) s[l] = (uint32_t)(8 + l) < r ? s[l] + t[8 + l] : s[l];
+    }
+    const float x = (s[0] + s[1]) + (s[2] + s[3]);
+    const float y = (s[4] + s[5]) + (s[6] + s[7]);
+    if (i < n) dist[i] = x + y;
+  }
+}
+
+__global__ __launch_bounds__(1024) void search_lut_kernel(const LutArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t llds[];
+  const bang_search_params& p = a.p;
+  const int lane = lane_id();
+  const uint32_t wave = uni(threadIdx.x >> 6);
+  const uint32_t nwaves = blockDim.x >> 6;
+  const uint32_t L = p.L, medoid = p.medoid, cap_iter = p.cap_iter, R = p.R, n_nodes = p.n_nodes, m = p.m;
+  const uint32_t cstride = p.code_stride ? p.code_stride : m;
+  const uint32_t cand_stride = L + BANG_EXTRA_ITERS;
+  const uint8_t GAS* graph = (const uint8_t GAS*)p.d_graph;
+  const uint8_t GAS* codes = (const uint8_t GAS*)p.d_codes;
+  const uint64_t entry_len = p.entry_len;
+  uint32_t* wbase = llds + (size_t)wave * a.wave_words;
+  uint32_t* scratch = wbase + a.wl_words;
+  WaveLds s;
+  s.wd = (float*)wbase; s.wi = wbase + L; s.wv = (uint8_t*)(wbase + 2 * L);
+  s.sd = (float*)scratch; s.ti = scratch; s.td = (float*)(scratch + 72);
+  float* sdist = (float*)scratch;                 // the survivors' distances (dead before the sort writes sd)
+  uint32_t* sc = scratch + 72;                    // the survivors' ids, in input order (== td: dead before the sort)
+  if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+  const uint32_t total_waves = gridDim.x * nwaves;
+  const uint32_t gw = blockIdx.x * nwaves + wave;
+
+  for (bool first_q = true;; first_q = false) {
+    // ---------------- the next query: the first one by position, then from the hand-out counter
+    uint32_t q;
+    if (first_q) q = gw;
+    else {
+      uint32_t t = 0;
+      if (lane == 0) t = __hip_atomic_fetch_add(p.d_next_query, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      q = total_waves + uni(t);
+    }
+    if (q >= p.Q) break;
+    uint32_t GAS* bloom = (uint32_t GAS*)p.d_bloom + (size_t)q * BANG_BF_WORDS;
+    const float GAS* lut = (const float GAS*)p.d_lut + (size_t)q * m * 256u;      // K1's table of this query :1236
+
+    // ---------------- per-query state (bang_init :440-489): candidate log = [MEDOID], seed list [MEDOID, adj(MEDOID)...]
+    uint32_t iter = 1, w_n = 0, cc = 1, mark = 0x01010101u, evals = 0, fetched = 0;
+    WlHead head;
+    head.found = false; head.idx = 0; head.id = 0; head.d = 0.0f; head.tail = 0.0f;
+    if (lane == 0) p.d_cand_ids[(size_t)q * cand_stride] = medoid;
+    uint32_t cnt_in = p.d_seed[0], x0 = p.d_seed[1 + lane], x1 = p.d_seed[65];
+    bool have_row = true;
+
+    for (;;) {
+      const bool first = (iter == 1);
+      // ---------------- K5: filter (neighbor_filtering_new :1140-1165) ----------------
+      uint32_t ci = have_row ? uni(cnt_in) : 0u;
+      {
+        const uint32_t cap = R + (first ? 1u : 0u);
+        if (ci > cap) ci = cap;
+      }
+      if (n_nodes != 0u && (__ballot((uint32_t)lane < ci && x0 >= n_nodes) != 0ull || (ci > 64u && uni(x1) >= n_nodes))) {
+        if (lane == 0 && p.d_abort) *p.d_abort = 2u;
+        ci = 0;
+      }
+      fetched += ci;
+      const bool v0 = (uint32_t)lane < ci;
+      const bool v1 = ci > 64;                                    // the 65th id exists in the seed list only (uniform)
+      const uint32_t h0a = hash1(x0), h0b = hash2(x0);
+      uint32_t h1a = 0, h1b = 0, w0a = 0, w0b = 0, w1a = 0, w1b = 0;
+      // CANON 3: every id is tested against the filter state at entry; the previous iteration's atomic ORs have completed
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (v0) { w0a = ld_bypass_l1(&bloom[h0a >> 5]); w0b = ld_bypass_l1(&bloom[h0b >> 5]); }
+      if (v1) {
+        h1a = hash1(x1); h1b = hash2(x1);
+        if (lane == 0) { w1a = ld_bypass_l1(&bloom[h1a >> 5]); w1b = ld_bypass_l1(&bloom[h1b >> 5]); }
+      }
+      const bool pass0 = v0 && !(((w0a >> (h0a & 31)) & 1u) && ((w0b >> (h0b & 31)) & 1u));
+      const bool pass1 = v1 && (lane == 0) && !(((w1a >> (h1a & 31)) & 1u) && ((w1b >> (h1b & 31)) & 1u));
+      const uint64_t m0 = __ballot(pass0);
+      const uint64_t m1 = __ballot(pass1);
+      const uint32_t n0 = (uint32_t)__popcll(m0);
+      const uint32_t n = n0 + (uint32_t)__popcll(m1);
+      // ... then every survivor's two bits are set (:1159-1160)
+      if (pass0) {
+        (void)__hip_atomic_fetch_or(&bloom[h0a >> 5], 1u << (h0a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_or(&bloom[h0b >> 5], 1u << (h0b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (pass1) {
+        (void)__hip_atomic_fetch_or(&bloom[h1a >> 5], 1u << (h1a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_or(&bloom[h1b >> 5], 1u << (h1b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      // ordered compaction through LDS: survivors keep input order (CANON; the reference emits in atomicAdd order :1161)
+      if (pass0) sc[lanes_below(m0)] = x0;
+      if (pass1) sc[n0] = x1;
+      wave_sync();
+      const uint32_t sid0 = ((uint32_t)lane < n) ? sc[lane] : 0u;
+      const uint32_t sid1 = (lane == 0 && n > 64) ? sc[64] : 0u;
+      evals += n;
+
+      // ---------------- K2: PQ distances from the query's table (compute_neighborDist_par :1201-1241) ----------------
+      if (n > 0) lut_dist(codes, cstride, m, lut, sc, n, sdist, lane);
+      wave_sync();
+      const float d0 = ((uint32_t)lane < n) ? sdist[lane] : BIG_DIST;
+      const float d1 = (lane == 0 && n > 64) ? sdist[64] : BIG_DIST;
+      wave_sync();
+
+      // ---------------- K4: parent (compute_parent1 :1464-1521 / compute_parent2 :1384-1459), as bang_search.hip ----------------
+      uint32_t parent = 0;
+      bool found = false;
+      {
+        const bool elig = (uint32_t)lane < n && sid0 != medoid && d0 < BIG_DIST;
+        // (squared distances are non-negative: their bit patterns order like the floats; {bits, lane}: first minimum wins)
+        uint32_t khi = elig ? __float_as_uint(d0) : 0xFFFFFFFFu, klo = (uint32_t)lane;
+        wave_min_key(khi, klo);
+        uint32_t bi = (khi != 0xFFFFFFFFu) ? klo : 0xFFFFu;
+        float bd = (khi != 0xFFFFFFFFu) ? __uint_as_float(khi) : BIG_DIST;
+        uint32_t bid = (uint32_t)__builtin_amdgcn_readlane((int)sid0, (int)(klo & 63u));
+        if (n > 64) {                                             // element 64 can only win with a strictly smaller distance
+          const float e_d = __shfl(d1, 0);
+          const uint32_t e_id = (uint32_t)__shfl((int)sid1, 0);
+          if (e_id != medoid && e_d < BIG_DIST && (bi == 0xFFFFu || e_d < bd)) { bd = e_d; bi = 64; bid = e_id; }
+        }
+        const bool have_best = (bi != 0xFFFFu);
+        if (!have_best) bd = BIG_DIST;
+        bool from_best = false;
+        if (first) {
+          if (have_best) { found = true; parent = bid; from_best = true; }
+        } else {
+          if (head.found) {                                       // first unvisited entry :1425-1439
+            found = true;
+            if (bd < head.d) { parent = bid; from_best = true; }
+            else { parent = head.id; if (lane == 0) s.wv[head.idx] = 1; }
+          } else if (w_n > 0) {                                   // corner case :1442-1446
+            if (bd < head.tail) { found = true; parent = bid; from_best = true; }
+          }
+        }
+        parent = uni(parent);
+        if (found) {
+          if (from_best) mark = parent;
+          ++cc;
+        }
+      }
+
+      // ---------------- hand the parent over: its adjacency row is requested now and travels during the sort/merge
+      const bool want_row = found && iter < cap_iter;
+      if (want_row) {
+        const uint32_t GAS* nrow = (const uint32_t GAS*)(graph + (uint64_t)parent * entry_len + p.vec_bytes);
+        cnt_in = nrow[0];
+        x0 = nrow[1 + ((uint32_t)lane < R ? (uint32_t)lane : 0u)];
+      }
+      if (found && lane == 0) p.d_cand_ids[(size_t)q * cand_stride + cc - 1u] = parent;      // :1451-1458
+
+      // ---------------- K3a + K3b: sort the survivors, merge them into the worklist (not at the cap: CANON 6) ----------------
+      if (n > 0 && iter < cap_iter) w_n = sort_and_merge(s, n, d0, sid0, d1, sid1, iter, w_n, L, medoid, mark, head.tail, lane);
+
+      // a query is active while it has a parent or unmerged survivors (CANON 4); the loop ends at the cap (:950-956)
+      if ((!found && n == 0) || iter == cap_iter) break;
+      ++iter;
+      have_row = found;
+      head = worklist_head(s, w_n, lane);
+    }
+
+    // ---------------- the query is finished: its candidate log feeds the re-rank launch (K6 + K7)
+    if (lane == 0) {
+      p.d_cand_cnt[q] = cc;
+      if (p.d_qstats) { p.d_qstats[(size_t)q * 2] = evals; p.d_qstats[(size_t)q * 2 + 1] = fetched; }
+      if (p.d_qiters) p.d_qiters[q] = iter;
+    }
+    wave_sync();
+  }
+  if (p.d_ktime) {
+    __syncthreads();
+    if (threadIdx.x == 0) p.d_ktime[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// launcher
+// ---------------------------------------------------------------------------------------------------------------------
+// 1 if one wave's state (2L + L/4 + 144 words) fits LDS; the table stays in HBM / the caches, so m only has to be a chunk count
+extern "C" int bang_search_lut_supported(uint32_t m, uint32_t L) {
+  if (m == 0 || L == 0 || L > BANG_MAX_L) return 0;
+  return lut_wave_bytes(L) <= LUT_MAX_LDS ? 1 : 0;
+}
+
+// Waves per CU: what the instance's registers allow (512 per SIMD lane, allocated in granules of 8, four SIMDs, at most 8 waves per SIMD), what
+// 160 KB of LDS hold, at most 32 -- as bang_search_exact_geometry.  A batch of fewer than a workgroup-full of queries per CU is spread over all
+// CUs with fewer waves each (a wave's iteration is latency bound).
+extern "C" int bang_search_lut_geometry(uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
+  if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
+  if (L == 0 || L > BANG_MAX_L) { bang_set_error("LUT search kernel: bad L"); return BANG_ERR_ARG; }
+  static int regs[BANG_MAX_DEVICES] = {}, max_waves_wg[BANG_MAX_DEVICES] = {};   // per device, read once
+  const int dev = current_device();
+  if (regs[dev] == 0) {
+    hipFuncAttributes at;
+    HIP_TRY(hipFuncGetAttributes(&at, (const void*)search_lut_kernel));
+    max_waves_wg[dev] = at.maxThreadsPerBlock >= WAVE ? at.maxThreadsPerBlock / WAVE : 16;
+    regs[dev] = at.numRegs > 0 ? at.numRegs : 128;
+  }
+  const uint32_t alloc = ((uint32_t)regs[dev] + 7u) & ~7u;
+  uint32_t per_simd = 512u / alloc;
+  if (per_simd > 8u) per_simd = 8u;
+  uint32_t per_cu = 4u * per_simd;
+  const uint32_t by_lds = LUT_MAX_LDS / lut_wave_bytes(L);
+  if (by_lds < per_cu) per_cu = by_lds;
+  if (per_cu > 32u) per_cu = 32u;
+  if (per_cu == 0) { bang_set_error("LUT search kernel: one wave's worklist does not fit LDS at L=%u", L); return BANG_ERR_UNSUPPORTED; }
+  uint32_t W = per_cu < 16u ? per_cu : 16u;
+  if (W > (uint32_t)max_waves_wg[dev]) W = (uint32_t)max_waves_wg[dev];                   // (the instance's launch bound)
+  const uint32_t wgs_per_cu = per_cu / W;
+  if (max_waves && max_waves < W) W = max_waves;
+  const uint32_t cus = (uint32_t)num_cus();
+  uint32_t grid_n;
+  if (Q <= cus * W) {                                             // fewer queries than a wave-full per CU: all CUs, fewer waves each
+    grid_n = Q < cus ? Q : cus;
+    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
+    const uint32_t share = (Q + grid_n - 1) / grid_n;
+    if (share < W) W = share;
+  } else {
+    const uint32_t want = (Q + W - 1) / W;
+    grid_n = cus * wgs_per_cu;
+    if (want < grid_n) grid_n = want;
+    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
+  }
+  *workgroups = grid_n;
+  *waves = W;
+  return BANG_OK;
+}
+
+extern "C" int bang_k_search_lut(const bang_search_params* p, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (p->Q == 0) return BANG_OK;
+  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("LUT search kernel: bad R/L"); return BANG_ERR_ARG; }
+  if (p->psz != 0) { bang_set_error("LUT search kernel: psz = %u (an index with an LDS pivot table runs on bang_k_search)", p->psz); return BANG_ERR_UNSUPPORTED; }
+  if (!p->d_graph || p->row_layout != 0) { bang_set_error("LUT search kernel: needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
+  if (p->m == 0 || (p->code_stride != 0 && p->code_stride < p->m)) { bang_set_error("LUT search kernel: bad m / code stride"); return BANG_ERR_ARG; }
+  if (!p->d_lut || !p->d_codes || !p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt || !p->d_next_query) {
+    bang_set_error("LUT search kernel: null buffer (d_lut, d_codes, d_seed, d_bloom, d_cand_ids, d_cand_cnt, d_next_query)"); return BANG_ERR_ARG;
+  }
+  if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("LUT search kernel: bad iteration cap"); return BANG_ERR_ARG; }
+  if (p->entry_len < (uint64_t)p->vec_bytes + 4u * (1u + p->R)) {
+    bang_set_error("LUT search kernel: a graph entry of %llu bytes does not hold %u vector bytes, the degree and R = %u ids", (unsigned long long)p->entry_len, p->vec_bytes, p->R);
+    return BANG_ERR_ARG;
+  }
+  if ((((uintptr_t)p->d_codes) & 3u) || (((uintptr_t)p->d_lut) & 3u)) { bang_set_error("LUT search kernel: code table and LUT must be 4-byte aligned"); return BANG_ERR_ARG; }
+  if (!bang_search_lut_supported(p->m, p->L)) { bang_set_error("LUT search kernel: one wave's worklist does not fit LDS at L=%u", p->L); return BANG_ERR_UNSUPPORTED; }
+  uint32_t grid_n = 0, waves = 0;
+  const int rc = bang_search_lut_geometry(p->L, p->Q, p->max_wgs, p->max_waves, &grid_n, &waves);
+  if (rc != BANG_OK) return rc;
+  LutArgs a;
+  a.p = *p;
+  a.wl_words = lut_wl_words(p->L);
+  a.wave_words = a.wl_words + LUT_SCRATCH_WORDS;
+  const size_t lds = (size_t)waves * a.wave_words * 4u;
+  static bool attr_done[BANG_MAX_DEVICES] = {};
+  const int dev = current_device();
+  if (!attr_done[dev]) {
+    HIP_TRY(hipFuncSetAttribute((const void*)search_lut_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LUT_MAX_LDS));
+    attr_done[dev] = true;
+  }
+  hipLaunchKernelGGL(search_lut_kernel, dim3(grid_n), dim3(waves * WAVE), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return BANG_OK;
+}

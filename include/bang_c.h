@@ -72,7 +72,8 @@ int bang_destroy(bang_engine_t* e);                          /* ~BANGSearch()   
  *   "numa"    : graph in host RAM: 1 = pin the walker threads (and the caller during bang_query) to the CPUs of the GPU's NUMA node,
  *               one physical core each; 0 = leave them where the OS puts them; -1 = auto = 0 (pinning measured slower on the
  *               2-socket measurement box)
- *   "search"  : graph in HBM: 1 = the query-resident search kernel (bang_k_search), 0 = the round-1 loops, -1 = auto */
+ *   "search"  : graph in HBM: 1 = the query-resident search kernel (bang_k_search; on the LUT path bang_k_search_lut), 0 = the round-1 loops,
+ *               -1 = auto (the LUT path keeps the round-1 loop) */
 int bang_set_option(bang_engine_t* e, const char* key, long value);
 /* The whole table of options and environment switches as text (csrc/bang_options.cpp is the one place they are defined): writes at
  * most cap bytes (NUL-terminated) to buf, returns the size needed.  buf may be NULL. */
@@ -407,6 +408,9 @@ typedef struct {
   uint64_t* rr_ids_out;                /* [rr_Q_total][k] */
   float* rr_dists_out;                 /* [k][rr_Q_total] (rank-major, :999) */
   uint32_t rr_dtype, rr_D, rr_k, rr_q0, rr_Q_total;
+  /* bang_k_search_lut only (psz == 0): the per-query look-up tables of K1 (bang_k_lut_build), read-only for the launch; query q's table is
+   * d_lut + q * m * 256.  The other entries ignore it.  (Appended last: the layout of every earlier member is unchanged.) */
+  const float* d_lut;                  /* [Q][m][256] */
 } bang_search_params;
 /* 1 if a launch with these vectors can carry the fused re-rank (bang_search_params.rr_*) */
 int bang_search_can_rerank(int dtype, uint32_t D, uint64_t vec_stride, uint32_t dim_adjust);
@@ -467,6 +471,21 @@ int bang_k_search_inmem(const bang_search_params* p, void* stream);
 /* grid of a bang_k_search_inmem launch: that of bang_search_geometry's self-paced form (host_paced = 0) */
 int bang_search_inmem_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
                                uint32_t* workgroups, uint32_t* waves);
+
+/* LUT-PATH search kernel (csrc/bang_search_lut.hip; engine option "search" = 1 on an index with psz == 0: chunks wider than 8 dimensions, a pivot
+ * table too large for LDS, or option "pq" = 1): the loop of bang_k_search's self-paced form -- one wave per query from its first iteration to its
+ * last, worklist in LDS, one launch per batch -- with every neighbour's PQ distance gathered from the query's look-up table d_lut (K1,
+ * bang_k_lut_build) in the arithmetic of the per-iteration kernels (compute_neighborDist_par, bang_search.cu:1229-1239: the same bits).  Any m,
+ * any code_stride.  The result is the candidate log (d_cand_ids [Q][L + 50], d_cand_cnt); bang_k_rerank follows.  Graph entries in HBM only
+ * (d_graph, row_layout 0) and psz == 0, else BANG_ERR_UNSUPPORTED.  Uses Q, R, m, L, medoid, cap_iter, max_wgs, max_waves, d_seed, d_codes,
+ * code_stride, d_graph, entry_len, vec_bytes, d_bloom (zeroed), d_cand_ids, d_cand_cnt, d_qstats, d_qiters, d_next_query (zeroed), d_abort,
+ * d_ktime, n_nodes and d_lut; the pivot-table fields and rr_* are ignored.  Arguments are checked before any HIP call. */
+int bang_k_search_lut(const bang_search_params* p, void* stream);
+/* 1 if one wave's state (2L + L/4 + 144 words of LDS) fits: m >= 1 and 1 <= L <= BANG_MAX_L; else 0 */
+int bang_search_lut_supported(uint32_t m, uint32_t L);
+/* grid of a bang_k_search_lut launch over Q queries at worklist length L: as bang_search_exact_geometry (waves per CU from the instance's
+ * registers and LDS, <= 16 per workgroup; max_wgs / max_waves: caps if nonzero; small batches spread over all CUs) */
+int bang_search_lut_geometry(uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
