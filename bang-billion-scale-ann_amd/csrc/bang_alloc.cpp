@@ -95,22 +95,34 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       e->pq_nhi = (w_rag > w_pad) ? e->pq_nhi_avail : 0;
     }
   }
-  // distance = 1: the exact-distance search kernel (bang_search_exact.hip) -- graph entries in HBM, self-paced, one launch per batch.  What it
-  // cannot run is refused: there is no PQ fallback
+  // distance = 1: the exact-distance search kernel (bang_search_exact.hip) -- self-paced, one launch per batch; graph entries in HBM, or, where
+  // pull = 1 was asked for explicitly, the pulled-rows form: adjacency rows from pinned host memory / the HBM row copy / a peer's slice, vectors
+  // from the packed table in HBM.  What it cannot run is refused: there is no PQ fallback
   e->search_exact = false;
   if (e->distance == 1) {
     if (!dev_graph) {
-      bang_set_error("option distance = 1 (exact) needs the graph and vectors in HBM (graph = device; this index was placed in host RAM)");
-      return BANG_ERR_UNSUPPORTED;
+      const char* missing = nullptr;
+      if (e->pull_opt != 1) missing = "option pull = 1 given explicitly (auto does not select the pulled-rows form)";
+      else if (!e->pull || !e->d_adj) missing = "the 256-byte pull rows (this index was loaded without them)";
+      else if (!e->vec_on_device || !e->d_vecs) missing = "the full-precision vectors resident in HBM (option vectors)";
+      else if (e->walker_opt == 1) missing = "walker != 1 (the walker team does not serve the exact-distance kernel)";
+      if (!missing && e->semantics == 1) missing = "semantics = 0 (the Inmemory walk reads graph entries in HBM)";
+      if (missing) {
+        bang_set_error("option distance = 1 (exact) needs the graph and vectors in HBM (graph = device; this index was placed in host RAM), or, with "
+                       "graph = host, the pulled-rows form; missing for that: %s", missing);
+        return BANG_ERR_UNSUPPORTED;
+      }
     }
     if (e->search_opt == 0 || e->persistent == 0) {
       bang_set_error("option distance = 1 (exact) runs on the query-resident search kernel only (search = %d, persistent = %d)", e->search_opt, e->persistent);
       return BANG_ERR_UNSUPPORTED;
     }
     if (e->distfn != BANG_DIST_L2) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
-    if (!bang_search_exact_supported(e->dtype, e->D, e->entry_len)) {
-      bang_set_error("option distance = 1 (exact): unsupported vector layout (dtype %d, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0, "
-                     "float vectors D %% 4 == 0; D <= %u; an entry stride divisible by 4", e->dtype, e->D, (unsigned long long)e->entry_len, BANG_EXACT_MAX_D);
+    const uint64_t vec_stride = dev_graph ? e->entry_len : (uint64_t)vb;     // (pulled rows: the packed vector table d_vecs)
+    if (!bang_search_exact_supported(e->dtype, e->D, vec_stride)) {
+      bang_set_error("option distance = 1 (exact): unsupported vector layout (dtype %d, D = %u, %s stride %llu): 8-bit vectors need D %% 16 == 0, "
+                     "float vectors D %% 4 == 0; D <= %u; %s stride divisible by 4", e->dtype, e->D, dev_graph ? "entry" : "vector",
+                     (unsigned long long)vec_stride, BANG_EXACT_MAX_D, dev_graph ? "an entry" : "a vector");
       return BANG_ERR_UNSUPPORTED;
     }
     e->search_exact = true;
@@ -149,7 +161,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
                   bang_search_lut_supported(e->m, (uint32_t)e->L) != 0;
   // graph in host RAM: the host-paced form of the same kernel, where the walker can write device memory (BAR mode)
   e->search_host = false;
-  if (!dev_graph && !e->search_v2 && persist_want && e->use_flag && e->stage_mode_eff == 2 && e->search_opt != 0 && e->psz != 0) {
+  if (!dev_graph && !e->search_v2 && !e->search_exact && persist_want && e->use_flag && e->stage_mode_eff == 2 && e->search_opt != 0 && e->psz != 0) {
     const int w_pad = bang_search_supported(e->psz, e->mp, 0, (uint32_t)e->L);
     const int w_rag = e->pq_nhi_avail ? bang_search_supported(e->psz, e->mp, e->pq_nhi_avail, (uint32_t)e->L) : 0;
     if (std::max(w_pad, w_rag) >= (e->search_opt == 1 ? 1 : 4)) {
@@ -166,7 +178,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   }
   // a walker form on an index whose graph entries only passed through at load time: map the graph file now (a streamed load
   // from an entry source has nothing to map: error)
-  if (!dev_graph && !e->search_v2 && !e->walker_rows && !e->graph) BANG_TRY(map_graph_file(e));
+  if (!dev_graph && !e->search_v2 && !e->search_exact && !e->walker_rows && !e->graph) BANG_TRY(map_graph_file(e));
   e->fp_direct = false;
   HIP_TRY_ALLOC(hipMalloc(&e->d_queries, nq * e->D * e->tsize + 16));
   if (e->psz) BANG_TRY(dmalloc(&e->d_qc, nq * e->mp * e->psz));
@@ -248,7 +260,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   nl = std::min(nl, Q);
   if (e->search_v2 || e->search_host || e->search_exact || e->search_lut) nl = 1;   // the search kernel's waves are the unit of overlap, not lanes
   if (e->search_host && e->threads_opt <= 0) e->threads_eff = std::max(1, std::min(12, usable_cpus() - 2));
-  else if (e->threads_opt <= 0) e->threads_eff = (dev_graph || e->search_v2) ? 1 : std::max(1, std::min(4, (usable_cpus() - 2) / std::max(1, nl)));   // leave 2 CPUs for the caller + HIP runtime threads: a cgroup that exceeds its quota gets throttled for the rest of the period
+  else if (e->threads_opt <= 0) e->threads_eff = (dev_graph || e->search_v2 || e->search_exact) ? 1 : std::max(1, std::min(4, (usable_cpus() - 2) / std::max(1, nl)));   // leave 2 CPUs for the caller + HIP runtime threads: a cgroup that exceeds its quota gets throttled for the rest of the period
   else e->threads_eff = e->threads_opt;
   if (!dev_graph) {
     const size_t n_flags = std::max<size_t>((size_t)nl, e->search_host ? 8 * KT_WGS : 0);

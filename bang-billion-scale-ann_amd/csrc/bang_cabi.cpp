@@ -198,7 +198,7 @@ extern "C" int bang_init_e(bang_engine_t* e, int Q) {
   hipStream_t st = e->lanes.empty() ? nullptr : e->lanes[0]->s_main;
   BANG_TRY(bang_k_init_all(&ia, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (e->h_parents && !e->search_v2) for (size_t i = 0; i < nq; ++i) e->h_parents[i] = BANG_NO_PARENT;   // (the walker forms read it)
+  if (e->h_parents && !e->search_v2 && !e->search_exact) for (size_t i = 0; i < nq; ++i) e->h_parents[i] = BANG_NO_PARENT;   // (the walker forms read it)
   e->inited = true;
   return BANG_OK;
 }
@@ -285,10 +285,10 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   s.vectors_on_device = e->vec_on_device ? 1 : 0;
   s.graph_mode = (uint64_t)e->graph_mode;
   s.lanes = (uint64_t)nl;
-  s.walker_threads = (e->graph_mode == BANG_GRAPH_DEVICE || e->search_v2) ? 0 : (uint64_t)e->threads_eff;   // (pull mode: nothing walks)
+  s.walker_threads = (e->graph_mode == BANG_GRAPH_DEVICE || e->search_v2 || e->search_exact) ? 0 : (uint64_t)e->threads_eff;   // (pull mode: nothing walks)
   s.wg_queries = e->search_host ? e->sv_W * e->sv_C : 0;
   s.pacing_groups = e->search_host ? e->sv_NG : 0;
-  s.graph_pull = (e->pull && e->search_v2 && e->graph_mode != BANG_GRAPH_DEVICE) ? 1 : 0;
+  s.graph_pull = (e->pull && (e->search_v2 || e->search_exact) && e->graph_mode != BANG_GRAPH_DEVICE) ? 1 : 0;
   s.workgroups = e->search_host ? (uint64_t)e->sv_G : (e->search_v2 || e->search_exact || e->search_lut) ? (uint64_t)std::min(Q, bang_num_cus()) : 0;
   s.search_kernel = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
   s.rerank_fused = e->rerank_fused ? 1 : 0;

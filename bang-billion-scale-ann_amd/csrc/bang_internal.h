@@ -59,6 +59,11 @@ int bang_ragged_supported(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t m);
 // bang_k_search_exact hands them the layouts bang_search_can_rerank refuses, its arguments checked; the grid as bang_search_exact_geometry
 int bang_k_search_exact_wide(const bang_search_params* p, void* stream);
 int bang_search_exact_wide_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+// the pulled-rows instances of both (row_layout 1; the same source built with BANG_EXACT_PULL as bang_search_exact_pull.o / bang_search_exact_wide_pull.o):
+// bang_k_search_exact hands them its checked arguments; each geometry reads the register count of the instance it launches
+int bang_k_search_exact_pull(const bang_search_params* p, void* stream);
+int bang_k_search_exact_wide_pull(const bang_search_params* p, void* stream);
+int bang_search_exact_wide_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 
 #ifdef __cplusplus
 }

@@ -54,8 +54,10 @@ static const OptionDef kOptions[] = {
      "0 = the per-iteration kernels, -1 = auto (LUT-path indexes keep the per-iteration kernels)"},
     {"distance", "BANG_DISTANCE", &bang_engine::distance, 0, 1, INT, BEFORE_ALLOC,
      "0 = PQ distances in the walk + exact re-rank (default), 1 = exact distances in the walk, results = the first k worklist entries (no re-rank; "
-     "the reference's BANG_Exactdistance).  1 needs graph = device, search != 0, persistent != 0, L2 distance and a vector layout of "
-     "bang_search_exact_supported: 8-bit D % 16 == 0, float D % 4 == 0, D <= 1024 (environment: pq | exact)"},
+     "the reference's BANG_Exactdistance).  1 needs graph = device -- or graph = host with pull = 1 given explicitly (not auto), the vectors resident in "
+     "HBM and walker != 1: the pulled-rows form, adjacency rows read by the kernel from pinned host memory, the HBM row copy or a peer's slice -- and "
+     "search != 0, persistent != 0, L2 distance and a vector layout of bang_search_exact_supported: 8-bit D % 16 == 0, float D % 4 == 0, D <= 1024 "
+     "(environment: pq | exact)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

@@ -31,6 +31,11 @@
 //    a float holds, the chain rounds nowhere and its value is the integer -- and from the first piece that takes a survivor past 2^24 the
 //    wave continues with the float chain, dimension by dimension, from the integer it has (CANON 10).
 //
+//  * PULLED ROWS (this file built a third and fourth time with -DBANG_EXACT_PULL=1, as bang_search_exact_pull.o and -- with BANG_EXACT_WIDE --
+//    bang_search_exact_wide_pull.o; kernels search_exact_pull_kernel / search_exact_wide_pull_kernel; row_layout 1).  The same loop; a node's
+//    vector comes from the packed table rr_vec_base + id * rr_vec_stride and the parent's adjacency row as 256 bytes -- one dword per lane -- from
+//    a slice of the node's HBM-resident rows, from the HBM copy of the first rows or from pinned host memory over PCIe.
+//
 // Reference line numbers: the reference's BANG_Base/bang_search.cu unless a file is named.
 
 #include <hip/hip_runtime.h>
@@ -236,13 +241,40 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
     if ((uint32_t)lane < np) dist[i0 + (uint32_t)lane] = acc;
   }
 }
+#ifdef BANG_EXACT_PULL
+#define EXACT_KERNEL search_exact_wide_pull_kernel
+#else
 #define EXACT_KERNEL search_exact_wide_kernel
+#endif
 // the float instance keeps 16 query registers across the whole loop and needs a few registers more than the 128 that 16 waves per CU leave a
 // wave: 12 waves per CU, no scratch (bang_search_exact_wide_geometry reads both figures off the instance)
 #define EXACT_MAX_THREADS(DT) ((DT) == BANG_F32 ? 768 : 1024)
 #else
+#ifdef BANG_EXACT_PULL
+#define EXACT_KERNEL search_exact_pull_kernel
+#else
 #define EXACT_KERNEL search_exact_kernel
+#endif
 #define EXACT_MAX_THREADS(DT) 1024
+#endif
+
+// PULLED ROWS (this file built with -DBANG_EXACT_PULL=1 as bang_search_exact_pull.o, and with -DBANG_EXACT_WIDE=1 as well as
+// bang_search_exact_wide_pull.o: the kernels renamed search_exact_pull_kernel / search_exact_wide_pull_kernel, so that the six instances of the
+// other two builds stay the code they are).  row_layout 1: the vectors in the packed table rr_vec_base (stride rr_vec_stride), the adjacency
+// lists as 256-byte rows of 64 ids (ids first, BANG_ADJ_PAD behind them) in pinned host memory (d_graph), in the HBM copy of the first rows
+// (d_rows_hbm) or in a slice of the node's HBM-resident rows (d_row_slices), read as bang_search.hip's self-paced form reads them.
+#ifdef BANG_EXACT_PULL
+#define EXACT_PULL 1
+// the slice table's entry idx (biased base addresses, 0 = that slice is not there), through the scalar cache
+__device__ __forceinline__ uint64_t slice_base(const uint64_t* tab, uint32_t idx) {
+  uint64_t v;
+  const uint64_t a = (uint64_t)(uintptr_t)tab + 8ull * idx;     // (uniform, but not provably so: made so)
+  const uint64_t at = ((uint64_t)uni((uint32_t)(a >> 32)) << 32) | uni((uint32_t)a);
+  asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(at) : "memory");
+  return v;
+}
+#else
+#define EXACT_PULL 0
 #endif
 
 template <int DT>
@@ -254,8 +286,13 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
   const uint32_t nwaves = blockDim.x >> 6;
   const uint32_t L = p.L, medoid = p.medoid, cap_iter = p.cap_iter, R = p.R, n_nodes = p.n_nodes;
   const uint32_t cand_stride = L + BANG_EXTRA_ITERS;
+#if EXACT_PULL
+  const uint8_t GAS* graph = (const uint8_t GAS*)p.rr_vec_base;   // the vectors: node x's at graph + x * entry_len
+  const uint64_t entry_len = p.rr_vec_stride;
+#else
   const uint8_t GAS* graph = (const uint8_t GAS*)p.d_graph;
   const uint64_t entry_len = p.entry_len;
+#endif
   uint32_t* wbase = xlds + (size_t)wave * a.wave_words;
   uint32_t* scratch = wbase + a.wl_words;
   WaveLds s;
@@ -322,14 +359,28 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       const bool first = (iter == 1);
       // ---------------- K5: filter (neighbor_filtering_new :1140-1165) ----------------
       uint32_t ci = have_row ? uni(cnt_in) : 0u;
+#if EXACT_PULL
+      if (!first && have_row) ci = (uint32_t)__popcll(__ballot(x0 != BANG_ADJ_PAD));   // a 256-byte adjacency row: ids first, padding behind them
+#endif
       {
         const uint32_t cap = R + (first ? 1u : 0u);
         if (ci > cap) ci = cap;
       }
+#if EXACT_PULL
+      {
+        // (a pad value in front of an id -- a row overwritten since bang_load -- is an id out of range whether or not n_nodes was given)
+        const uint32_t lim = n_nodes != 0u ? n_nodes : BANG_ADJ_PAD;
+        if (__ballot((uint32_t)lane < ci && x0 >= lim) != 0ull || (ci > 64u && uni(x1) >= lim)) {
+          if (lane == 0 && p.d_abort) *p.d_abort = 2u;
+          ci = 0;
+        }
+      }
+#else
       if (n_nodes != 0u && (__ballot((uint32_t)lane < ci && x0 >= n_nodes) != 0ull || (ci > 64u && uni(x1) >= n_nodes))) {
         if (lane == 0 && p.d_abort) *p.d_abort = 2u;
         ci = 0;
       }
+#endif
       fetched += ci;
       const bool v0 = (uint32_t)lane < ci;
       const bool v1 = ci > 64;                                    // the 65th id exists in the seed list only (uniform)
@@ -418,11 +469,29 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 
       // ---------------- hand the parent over: its adjacency row is requested now and travels during the sort/merge
       const bool want_row = found && iter < cap_iter;
+#if EXACT_PULL
+      if (want_row) {
+        // all 64 lanes load one dword of the row.  Slice parent / slice_rows of the node's HBM-resident rows (this GPU's HBM or a peer's over
+        // xGMI; 0: that slice is not there), else the HBM copy of the first n_rows_hbm rows, else pinned host memory over PCIe
+        const uint32_t GAS* hb = nullptr;
+        if (p.n_slices > 1u) {
+          const uint32_t sl = parent / p.slice_rows;              // (uniform: scalar)
+          if (sl < p.n_slices) hb = (const uint32_t GAS*)slice_base(p.d_row_slices, sl);
+        } else if (parent < p.n_rows_hbm) hb = (const uint32_t GAS*)p.d_rows_hbm;
+        if (hb) x0 = hb[(uint64_t)parent * 64u + (uint32_t)lane];
+        else {
+          x0 = __builtin_nontemporal_load((const uint32_t GAS*)p.d_graph + (uint64_t)parent * 64u + (uint32_t)lane);
+          asm volatile("; row from host memory");                 // (keeps this load apart from the plain one: merged, the two lose the hint)
+        }
+        cnt_in = 64u;                                             // counted when the row is consumed
+      }
+#else
       if (want_row) {
         const uint32_t GAS* nrow = (const uint32_t GAS*)(graph + (uint64_t)parent * entry_len + p.vec_bytes);
         cnt_in = nrow[0];
         x0 = nrow[1 + ((uint32_t)lane < R ? (uint32_t)lane : 0u)];
       }
+#endif
       if (found && lane == 0) p.d_cand_ids[(size_t)q * cand_stride + cc - 1u] = parent;      // :1451-1458
 
       // ---------------- K3a + K3b: sort the survivors, merge them into the worklist (not at the cap: CANON 6) ----------------
@@ -462,10 +531,18 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 // ---------------------------------------------------------------------------------------------------------------------
 #ifdef BANG_EXACT_WIDE
 #define EXACT_EXTRA_WORDS EXACT_TILE_WORDS                        // the wave's row tile, behind its scratch
+#if EXACT_PULL
+#define EXACT_GEOMETRY bang_search_exact_wide_pull_geometry
+#else
 #define EXACT_GEOMETRY bang_search_exact_wide_geometry
+#endif
 #else
 #define EXACT_EXTRA_WORDS 0u
+#if EXACT_PULL
+#define EXACT_GEOMETRY bang_search_exact_pull_geometry
+#else
 #define EXACT_GEOMETRY bang_search_exact_geometry
+#endif
 #endif
 
 static const void* exact_instance(int dtype) {
@@ -482,7 +559,8 @@ static uint32_t exact_wave_bytes(uint32_t L) { return (exact_wl_words(L) + EXACT
 // 97-98 VGPRs and no scratch (the merge of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves
 // per SIMD, 16 per CU -- one workgroup of 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  The wide instances (at most 128
 // VGPRs, no scratch: DESIGN.md section 4.6) run 16 waves per CU as well, up to L = 704.  A batch of fewer than 16 queries per CU is spread
-// over all CUs with fewer waves each (a wave's iteration is latency bound, as in bang_search_geometry).
+// over all CUs with fewer waves each (a wave's iteration is latency bound, as in bang_search_geometry).  The pulled-rows builds: 99-100 VGPRs
+// narrow, 108-109 / 134 wide, no scratch -- the same waves per CU, read off the pulled instance.
 extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   const void* k = exact_instance(dtype);
@@ -552,7 +630,18 @@ static int exact_launch(const bang_search_params* p, void* stream) {
   return BANG_OK;
 }
 
+#if EXACT_PULL
+// the pulled-rows instances (row_layout 1), called by bang_k_search_exact with its arguments checked: the layouts of the fused re-rank on the
+// narrow instances, the others on the wide ones
 #ifdef BANG_EXACT_WIDE
+extern "C" int bang_k_search_exact_wide_pull(const bang_search_params* p, void* stream) {
+#else
+extern "C" int bang_k_search_exact_pull(const bang_search_params* p, void* stream) {
+#endif
+  if (!p || p->row_layout != 1u || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) return BANG_ERR_ARG;
+  return exact_launch(p, stream);
+}
+#elif defined(BANG_EXACT_WIDE)
 // called by bang_k_search_exact with its arguments checked, for the layouts the narrow instances do not evaluate
 extern "C" int bang_k_search_exact_wide(const bang_search_params* p, void* stream) {
   if (!p || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len)) return BANG_ERR_ARG;
@@ -573,12 +662,32 @@ extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
   if (!p) return BANG_ERR_ARG;
   if (p->Q == 0) return BANG_OK;
   if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("distance = 1: bad R/L"); return BANG_ERR_ARG; }
-  if (!p->d_graph || p->row_layout != 0) { bang_set_error("distance = 1: the exact-distance kernel needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
+  if (p->row_layout > 1u) { bang_set_error("distance = 1: row_layout = %u: the adjacency lists are graph entries in HBM (0) or 256-byte rows (1)", p->row_layout); return BANG_ERR_UNSUPPORTED; }
+  if (p->row_layout == 0u && !p->d_graph) { bang_set_error("distance = 1: the exact-distance kernel needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
   if (!p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt || !p->d_next_query || !p->rr_queries || !p->rr_ids_out || !p->rr_dists_out) {
     bang_set_error("distance = 1: null buffer"); return BANG_ERR_ARG;
   }
   if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("distance = 1: bad iteration cap"); return BANG_ERR_ARG; }
   if (p->rr_k == 0 || p->rr_k > p->L || p->rr_Q_total < p->rr_q0 + p->Q) { bang_set_error("distance = 1: bad k / result rows"); return BANG_ERR_ARG; }
+  if (p->row_layout == 1u) {
+    // the pulled-rows form: adjacency rows in d_graph (pinned host memory; 4-byte aligned), vectors at rr_vec_base + id * rr_vec_stride
+    if (!p->d_graph || (((uintptr_t)p->d_graph) & 3u)) { bang_set_error("distance = 1, row_layout = 1: d_graph (the 256-byte adjacency rows) is null or not 4-byte aligned"); return BANG_ERR_ARG; }
+    if (p->R > 64u) { bang_set_error("distance = 1, row_layout = 1: R = %u, a 256-byte row holds 64 ids", p->R); return BANG_ERR_ARG; }
+    if (!p->rr_vec_base || (((uintptr_t)p->rr_vec_base) & 3u)) { bang_set_error("distance = 1, row_layout = 1: rr_vec_base (the vectors) is null or not 4-byte aligned"); return BANG_ERR_ARG; }
+    if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
+      bang_set_error("distance = 1, row_layout = 1: rr_vec_stride = %llu does not describe vectors the kernel evaluates (dtype %u, D = %u): 8-bit vectors need "
+                     "D %% 16 == 0, float vectors D %% 4 == 0; D <= %u; a stride divisible by 4 that holds the vector", (unsigned long long)p->rr_vec_stride,
+                     p->rr_dtype, p->rr_D, BANG_EXACT_MAX_D);
+      return BANG_ERR_ARG;
+    }
+    if (p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u)) { bang_set_error("distance = 1, row_layout = 1: vec_bytes = %u is not rr_D * the element size", p->vec_bytes); return BANG_ERR_ARG; }
+    if (((uintptr_t)p->rr_queries) & 3u) { bang_set_error("distance = 1, row_layout = 1: rr_queries is not 4-byte aligned"); return BANG_ERR_ARG; }
+    if (p->n_slices > 1u && !p->d_row_slices) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs the slice table d_row_slices", p->n_slices); return BANG_ERR_ARG; }
+    if (p->n_slices > 1u && p->slice_rows == 0u) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs slice_rows != 0", p->n_slices); return BANG_ERR_ARG; }
+    if (p->n_rows_hbm != 0u && !p->d_rows_hbm) { bang_set_error("distance = 1, row_layout = 1: n_rows_hbm = %u needs d_rows_hbm", p->n_rows_hbm); return BANG_ERR_ARG; }
+    if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return bang_k_search_exact_pull(p, stream);
+    return bang_k_search_exact_wide_pull(p, stream);
+  }
   if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
       (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
     bang_set_error("distance = 1: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0, float vectors "

@@ -447,7 +447,7 @@ int bang_k_rerank(const void* d_vec_base, uint64_t vec_stride, const void* d_med
 
 /* EXACT-DISTANCE search kernel (csrc/bang_search_exact.hip; engine option "distance" = 1; the reference's BANG_Exactdistance,
  * BANG_Exactdistance/parANN.cu:1139-1179, :1275): the loop of bang_k_search with every neighbour's distance the exact L2 against its full-precision
- * vector -- the first vec_bytes of its graph entry in d_graph (row_layout 0; graph in HBM only) -- and no re-rank: each query's results are the
+ * vector -- the first vec_bytes of its graph entry in d_graph (row_layout 0: graph in HBM; row_layout 1: below) -- and no re-rank: each query's results are the
  * first min(k, worklist length) worklist entries when its loop ends (padded with UINT64_MAX / 3.402823E+38f), written to rr_ids_out [rr_Q_total][k]
  * (u64) / rr_dists_out [k][rr_Q_total] at row rr_q0 + q.  Uses Q, R, L, medoid, cap_iter, max_wgs, max_waves, d_seed, d_graph, entry_len,
  * vec_bytes, d_bloom (zeroed), d_cand_ids / d_cand_cnt (the expanded nodes, [0] = MEDOID), d_qstats, d_qiters, d_next_query (zeroed), d_abort,
@@ -455,12 +455,25 @@ int bang_k_rerank(const void* d_vec_base, uint64_t vec_stride, const void* d_med
  * ignored.  Vector layouts: bang_search_exact_supported(rr_dtype, rr_D, entry_len); others are BANG_ERR_UNSUPPORTED.  The layouts of the fused re-rank
  * (bang_search_can_rerank with rr_vec_stride = entry_len) run on the instances that share its arithmetic, the others -- D up to BANG_EXACT_MAX_D,
  * 8-bit vectors with any D / 16 -- on the wide instances (rows fetched cooperatively through an LDS tile; 8-bit sums leave the integers at 2^24 and
- * continue as orc_exact_dist's float chain).  Same bits as bang_k_rerank either way. */
+ * continue as orc_exact_dist's float chain).  Same bits as bang_k_rerank either way.
+ *
+ * PULLED ROWS (row_layout = 1; engine: graph = host with pull = 1 given explicitly): the adjacency lists are the 256-byte rows bang_k_search's
+ * self-paced form reads -- 64 ids, the unused slots behind them BANG_ADJ_PAD -- and a node's vector sits at rr_vec_base + id * rr_vec_stride (the
+ * packed table in HBM).  The row of node x is read from slice x / slice_rows of d_row_slices where n_slices > 1 (biased base addresses; a zero entry
+ * or a slice past the table: from d_graph), else from d_rows_hbm where x < n_rows_hbm, else from d_graph (pinned host memory, over PCIe, with the
+ * non-temporal hint).  Contract: d_graph = the rows, 4-byte aligned; rr_vec_base non-null and 4-byte aligned;
+ * bang_search_exact_supported(rr_dtype, rr_D, rr_vec_stride); vec_bytes == rr_D * the element size; R <= 64; n_slices > 1 needs d_row_slices and
+ * slice_rows != 0; n_rows_hbm != 0 needs d_rows_hbm.  A violation is BANG_ERR_ARG with a message naming the member; entry_len is ignored.  An id
+ * >= n_nodes in a row -- the pad value in front of an id included, also where n_nodes == 0 -- is never followed (*d_abort = 2).  Results, counters
+ * and candidate log are those of the graph-entry form, bit for bit.  row_layout > 1 is BANG_ERR_UNSUPPORTED.  Arguments are checked before any HIP
+ * call in both forms. */
 int bang_k_search_exact(const bang_search_params* p, void* stream);
 /* grid of a bang_k_search_exact launch (layouts of bang_search_can_rerank) over Q queries for vectors of dtype at worklist length L: workgroups and waves per workgroup (as many
  * waves per CU as the instance's registers and LDS allow, <= 16 per workgroup; max_wgs / max_waves: caps if nonzero; a batch of fewer than a
  * workgroup-full of queries per CU is spread over all CUs) */
 int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+/* the same for a launch of the pulled-rows form (row_layout = 1): the register count read is that of the pulled instance */
+int bang_search_exact_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 
 /* BANG_INMEMORY SEMANTICS of the query-resident search kernel (csrc/bang_search.hip built as bang_search_inmem.o / bang_search_inmem_b.o; engine
  * option "semantics" = 1; the reference's BANG_Inmemory, BANG_Inmemory/parANN.cu:1287-1420): the loop of bang_k_search with the parent taken AFTER
