@@ -3,13 +3,17 @@
 TEST INFRASTRUCTURE ONLY (a helper module, not a conftest).  The fixtures of tests/conftest.py never reach these places (exact distance
 ties, the 65-id seed list, the iteration cap, a worklist shorter than k, the vector layouts at either end of what the kernels evaluate,
 values at the ends of the 8-bit ranges); every input here is named for the edge it reaches, tests/test_edge_inputs.py asserts ON THE CPU
-REFERENCES that it does reach it, and the GPU files (tests/test_gpu_exact_edges.py, tests/test_gpu_inmemory_edges.py) compare the kernels
-with those references bit for bit.
+REFERENCES that it does reach it, and the GPU files compare the kernels with those references bit for bit: tests/test_gpu_exact_edges.py and
+tests/test_gpu_exact_pull.py (the exact-distance kernels), tests/test_gpu_inmemory_edges.py (the Inmemory build), tests/test_gpu_lut_search.py
+(the LUT-path kernel) and tests/test_gpu_base_edges.py (every form of the BANG_Base PQ walk; the forms are those of tests/base_forms.py).
+The layout list that reaches every compiled instance of that walk's kernel, in both row alignments, is a module of its own:
+tests/instance_inputs.py, asserted by tests/test_instance_inputs.py and run by tests/test_gpu_search_instances.py.
 
     (a) toy(), TOYS               hand-made graphs with level vectors (inmemory_reference.toy_index) in any vector type and dimension
     (b) chain()                   a chain with a falling distance: the walk runs to the iteration cap
     (c) short_worklist()          three nodes, a self-loop and a duplicate id: the worklist stays shorter than k
     (d) seed65()                  a medoid of degree R = 64: a seed list of 65 ids, the 65th best / tying the best / worse
+        degree64()                the first parent has 64 neighbours: a row without a pad
     (e) tie_heavy()               a fixture with its vectors, queries and pivots cut down to a few small integers: ties everywhere
     (f) extreme()                 8-bit vectors of the two end values at D = 256: distances just below 2^24
     (g) SHAPES, shape_index()     synth.make_index at the dimensions and degree bounds at the ends of the supported layouts
@@ -106,6 +110,20 @@ def seed65(dtype: str, variant: str, D: int = 128):
     adj = {0: list(range(1, 65)), 3: [65, 66], 7: [67, 68], 64: [69, 70], 1: [71], 65: [72], 67: [73], 69: [74], 72: [75]}
     levels += [9, 16, 8, 15, 6, 12, 35, 5, 4, 3, 2]                                # nodes 65 .. 75
     assert len(levels) == 76
+    return toy(adj, levels, dtype, D)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# (d2) an expanded row of 64 ids
+# ---------------------------------------------------------------------------------------------------------------------
+DEGREE64_LAYOUTS = (("uint8", 128), ("float", 128))
+DEGREE64_NODE = 1                # the first parent
+
+
+def degree64(dtype: str = "uint8", D: int = 128):
+    """Node 1 is the first parent and has exactly 64 neighbours: its 256-byte row holds no pad and all 64 lanes carry an id."""
+    levels = [200, 100] + [50 + (i * 5) % 41 for i in range(64)] + [7, 3]
+    adj = {0: [1], 1: list(range(2, 66)), 2: [66], 66: [67]}
     return toy(adj, levels, dtype, D)
 
 

@@ -38,6 +38,10 @@ class Reference:
 
     def search_one(self, query: np.ndarray, k: int, L: int, mode: str):
         """-> (ids u64 [k], dists f32 [k], stats (iterations, candidates, dist_evals, fetched))"""
+        return self.search_one_logged(query, k, L, mode)[:3]
+
+    def search_one_logged(self, query: np.ndarray, k: int, L: int, mode: str):
+        """search_one, and the candidate log behind it: -> (ids, dists, stats, candidates u32 [stats[1]], the expanded nodes in order)"""
         if mode not in MODES:
             raise ValueError(mode)
         ix = self.ix
@@ -98,7 +102,7 @@ class Reference:
         c = np.array(cand, np.uint32)                                    # K6 + K7
         cd = np.array([self.orc.exact_dist(int(x), q) for x in c], np.float32)
         ids, dists = O.topk(c, cd, k)
-        return ids, dists, (it, len(cand), evals, fetched)
+        return ids, dists, (it, len(cand), evals, fetched), c
 
     def search(self, queries: np.ndarray, k: int, L: int, mode: str):
         """-> ids u64 [Q][k], dists f32 [k][Q] (rank-major), stats int64 [Q][4] (iterations, candidates, dist_evals, fetched)"""

@@ -40,6 +40,16 @@ def test_toy_compositions_equal_the_oracle(name, dtype, D):
 
 
 @pytest.mark.parametrize("dtype,D", E.TOY_LAYOUTS)
+@pytest.mark.parametrize("name", sorted(E.TOYS))
+def test_toy_walks_expand_a_row_of_pads_only(name, dtype, D):
+    """The leaves of the toy graphs have degree 0.  At L = 10 the BANG_Base walk expands one: no node is expanded twice, and the walk logs more
+    candidates than there are nodes with a neighbour."""
+    ix, q = E.toy_named(name, dtype, D)
+    _, _, st = O.Oracle(ix).search(q, 3, 10, with_stats=True)
+    assert int(st[0][1]) > int((ix.degrees() > 0).sum())
+
+
+@pytest.mark.parametrize("dtype,D", E.TOY_LAYOUTS)
 def test_toy_distances_are_the_level_differences(dtype, D):
     """Exact and PQ distance of node i are both D levels[i]^2, in every layout: equal levels tie in both."""
     adj, levels = E.TOYS["head_tie"]
@@ -137,6 +147,17 @@ def test_seed65_evaluates_65_seeds_and_the_last_one_decides(dtype, D):
         assert res["worse"][mode][0][0].tolist() == [75, 72, 65, 66], mode
 
 
+@pytest.mark.parametrize("dtype,D", E.DEGREE64_LAYOUTS)
+def test_degree64_expands_a_full_row(dtype, D):
+    ix, q = E.degree64(dtype, D)
+    assert ix.R == 64 and int(ix.degrees()[E.DEGREE64_NODE]) == 64 and int(ix.degrees()[ix.medoid]) == 1
+    for L in (5, 37):
+        ids, _, st = O.Oracle(ix).search(q, 5, L, with_stats=True)
+        assert int(st[0][3]) >= 64 + 2                                       # fetched: the seed list and the full row
+        assert ids[0].tolist()[:2] == [67, 66]
+        _pinned_to_the_oracle(ix, q, 5, L)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # (e) ties everywhere
 # ---------------------------------------------------------------------------------------------------------------------
@@ -215,3 +236,20 @@ def test_shapes_build_and_run_through_the_references(shape, libbang):
     assert not (ids == E.ID_PAD).any() and np.all(np.diff(d, axis=0) >= 0)
     assert (st[:, 0] < 37 + 49).all()
     _pinned_to_the_oracle(ix, q, 10, 37)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every input with a search-kernel instance fits the host-paced form
+# ---------------------------------------------------------------------------------------------------------------------
+def test_lds_holds_the_host_paced_form_on_every_input(request, libbang):
+    """tests/test_gpu_base_edges.py skips a host-paced case that reports search_kernel == 0 as "no CPU-writable device memory".  The engine's other
+    reason to decline the form, LDS, is ruled out here, in host code, for every input and up to the longest worklist that file runs on them;
+    the layouts it treats as LUT-path ones are those without an instance."""
+    import base_forms as F
+    inputs = [E.toy_named("head_tie", dtype, D)[0] for dtype, D in E.TOY_LAYOUTS]              # (every toy, chain, seed65, degree64: D / 4 chunks)
+    inputs += [E.shape_index(s)[0] for s in E.SHAPES]
+    inputs += [E.tie_heavy(*request.getfixturevalue(name)[:2])[0] for name in TIE_FIXTURES]
+    inputs += [E.extreme("uint8")[0]]
+    for ix in inputs:
+        for L in (3, 10, 16, F.EDGE_MAX_L):
+            assert (F.host_paced_waves(ix, L) >= 1) == (ix.D < 132), (ix.dtype, ix.D, ix.m, L)

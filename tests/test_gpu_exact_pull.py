@@ -180,12 +180,10 @@ def test_seed_list_of_65(variant, dtype, D):
             _check(e, ("seed65", variant, dtype, D), ix, q, 4, L)
 
 
-@pytest.mark.parametrize("dtype,D", [("uint8", 128), ("float", 128)])
+@pytest.mark.parametrize("dtype,D", E.DEGREE64_LAYOUTS)
 def test_expanded_node_of_degree_64(dtype, D):
     """Node 1 is the first parent and has exactly 64 neighbours: its 256-byte row holds no pad and all 64 lanes carry an id."""
-    levels = [200, 100] + [50 + (i * 5) % 41 for i in range(64)] + [7, 3]
-    adj = {0: [1], 1: list(range(2, 66)), 2: [66], 66: [67]}
-    ix, q = E.toy(adj, levels, dtype, D)
+    ix, q = E.degree64(dtype, D)
     assert int(ix.degrees()[1]) == 64
     with _engine(ix) as e:
         for L in (5, 37):
