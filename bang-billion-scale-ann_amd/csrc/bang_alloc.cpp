@@ -118,8 +118,13 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       return BANG_ERR_UNSUPPORTED;
     }
     if (e->distfn != BANG_DIST_L2) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
-    const uint64_t vec_stride = dev_graph ? e->entry_len : (uint64_t)vb;     // (pulled rows: the packed vector table d_vecs)
-    if (!bang_search_exact_supported(e->dtype, e->D, vec_stride)) {
+    const uint64_t vec_stride = dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e);     // (pulled rows: the packed vector table d_vecs)
+    if (!dev_graph && e->vecs_f16 && (e->D % 8u != 0 || e->D > 256u)) {
+      bang_set_error("options distance = 1 (exact) and vectors_fp16 = 1: the exact-distance kernel reads an fp16 vector table of D %% 8 == 0, D <= 256 only "
+                     "(D = %u; the wide layouts keep float rows: vectors_fp16 = 0)", e->D);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (!(e->vecs_f16 && !dev_graph) && !bang_search_exact_supported(e->dtype, e->D, vec_stride)) {
       bang_set_error("option distance = 1 (exact): unsupported vector layout (dtype %d, D = %u, %s stride %llu): 8-bit vectors need D %% 16 == 0, "
                      "float vectors D %% 4 == 0; D <= %u; %s stride divisible by 4", e->dtype, e->D, dev_graph ? "entry" : "vector",
                      (unsigned long long)vec_stride, BANG_EXACT_MAX_D, dev_graph ? "an entry" : "a vector");

@@ -292,6 +292,8 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   s.workgroups = e->search_host ? (uint64_t)e->sv_G : (e->search_v2 || e->search_exact || e->search_lut) ? (uint64_t)std::min(Q, bang_num_cus()) : 0;
   s.search_kernel = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
   s.rerank_fused = e->rerank_fused ? 1 : 0;
+  s.vectors_fp16 = e->vecs_f16 ? 1 : 0;
+  s.vector_table_bytes = (e->vec_on_device && e->d_vecs) ? (uint64_t)e->N * vec_table_stride(e) + 256 : 0;
   s.walker_rows = (e->search_host && e->walker_rows) ? 1 : 0;
   s.code_stride = e->code_stride;
   // what the kernel was GIVEN (bang_lane.cpp): without a slice table a slice moved off row 0 (bang_rows_slice_e(first > 0)) is not reachable

@@ -245,6 +245,8 @@ struct bang_engine {
                                        // every expanded node's vector, as the reference does), 1 = a packed copy [N][vec_bytes] in HBM (the
                                        // walker ships adjacency rows only), -1 = auto (1 if the copy takes at most 40 % of the free HBM)
   bool vec_on_device = false;          // resolved at load
+  int vectors_fp16 = 0;                // option "vectors_fp16": 1 = that copy as IEEE fp16 rows (float indexes, host placement)
+  bool vecs_f16 = false;               // resolved at load: d_vecs holds fp16 rows of vec_table_stride() bytes
   // PULL mode of the host-graph placement: the adjacency lists alone, as [N][64] u32 rows of 256 B (unused slots 0xFFFFFFFF), in
   // pinned host memory mapped into the GPU's address space.  The self-paced search kernel fetches a parent's row over PCIe by
   // itself (one 256-B read, ~2 us; 57 GB/s of such rows measured) -- no walker thread, no publish / poll round trip.
@@ -275,7 +277,7 @@ struct bang_engine {
   void* peer_ptr[BANG_MAX_ROW_SLICES] = {nullptr};       // hipIpcOpenMemHandle mappings (closed at bang_unload); the own slot stays NULL
   uint64_t slice_base[BANG_MAX_ROW_SLICES] = {0};        // biased addresses handed to the kernel (0: not available -> host rows)
   uint64_t* d_slice_tab = nullptr;     // device copy of slice_base
-  uint8_t* d_vecs = nullptr;           // [N][vec_bytes]
+  uint8_t* d_vecs = nullptr;           // [N][vec_table_stride]
   bool vecs_owned = true;              // false: d_vecs is the caller's buffer (bang_index_desc.d_vectors), never freed here
   uint8_t* ext_vecs = nullptr;         // set for the duration of a load: the caller's vector buffer, and whether it is filled already
   bool ext_vecs_ready = false;
@@ -297,6 +299,8 @@ extern "C" int bang_search_inmem_has_instance(uint32_t psz, uint32_t mp, uint32_
 namespace bang {
 
 inline size_t vec_bytes(const bang_engine* e) { return (size_t)e->D * e->tsize; }
+// bytes between the rows of the HBM vector table d_vecs: the vector as the index holds it, or its fp16 image padded to whole dwords
+inline size_t vec_table_stride(const bang_engine* e) { return e->vecs_f16 ? (((size_t)2 * e->D + 3) & ~(size_t)3) : vec_bytes(e); }
 
 inline int ensure_device(bang_engine* e) {
   if (bang_device_count() == 0) {

@@ -25,6 +25,11 @@ int bang_k_rerank_byquery(const void* d_fp, uint64_t vec_stride, const void* d_m
                           uint32_t Q_total, uint32_t D, uint32_t k, uint32_t dim_adjust, uint64_t* d_ids_out, float* d_dists_out,
                           void* stream);
 
+// bang_k_rerank_f16 (float queries, fp16 vector table) on the sub-range [q0, q0+nq) of a batch of Q_total queries
+int bang_k_rerank_f16_range(const void* d_vec_base, uint64_t vec_stride, const void* d_queries, const uint32_t* d_cand_ids,
+                            const uint32_t* d_cand_cnt, uint32_t cand_stride, uint32_t q0, uint32_t nq, uint32_t Q_total, uint32_t D,
+                            uint32_t k, uint32_t dim_adjust, uint64_t* d_ids_out, float* d_dists_out, void* stream);
+
 // device side of bang_init: candidate log = [MEDOID], empty worklists, mark = 0x01010101
 int bang_k_init_state(uint32_t Q, uint32_t medoid, uint32_t cand_stride, uint32_t* d_cand_ids, uint32_t* d_cand_row,
                       uint32_t* d_cand_cnt, uint32_t* d_wl_cnt, uint32_t* d_mark, uint32_t* d_parents, uint32_t* d_cnt,
@@ -64,6 +69,9 @@ int bang_search_exact_wide_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t 
 int bang_k_search_exact_pull(const bang_search_params* p, void* stream);
 int bang_k_search_exact_wide_pull(const bang_search_params* p, void* stream);
 int bang_search_exact_wide_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+// the pulled-rows instance on an fp16 vector table (rr_vec_f16 = 1; the same source built with BANG_EXACT_PULL and BANG_EXACT_F16 as
+// bang_search_exact_pull_f16.o), handed bang_k_search_exact's checked arguments
+int bang_k_search_exact_pull_f16(const bang_search_params* p, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@
 #include "bang_c.h"
 #include "bang_internal.h"
 #include "bang_device.h"
+#include "bang_f16.h"
 
 // LUT path (PSZ == 0): LUT[m][256] gathered from global memory as the reference does (:1236); any m.
 __device__ __forceinline__ float pq_distance_lut(const uint8_t* __restrict__ codes, uint32_t m, uint32_t stride, uint32_t id,
@@ -752,6 +753,33 @@ struct RerankArgs {
   float* dists_out;
 };
 
+// K7 of rerank_f16_kernel: e[0, n) / ids[0, n) in LDS -> the query's k results (the caller has synchronised the block behind its last store).
+// The code of rerank_kernel's tail below, which stays where it is so that its three instances remain the instructions they were.
+__device__ __forceinline__ void rerank_rank(const RerankArgs& a, uint32_t q, uint32_t n, const float* e, const uint32_t* ids, unsigned long long* keys) {
+  // stable rank by exact distance; ties keep expansion order (:1330-1363): rank = #{(distance, index) pairs below mine}.  Exact
+  // distances are sums of squares -- non-negative floats, which order like their bit patterns -- so the pair is ONE unsigned 64-bit key
+  // {distance bits, index} and the rank one compare per pair (the two-level float rule costs three).
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) keys[i] = ((unsigned long long)__float_as_uint(e[i]) << 32) | i;
+  if (threadIdx.x == 0) keys[n] = ~0ull;                                   // (padding of the last pair: below nobody)
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+    const unsigned long long mine = keys[i];
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < n; j += 2) {
+      const ulonglong2 o = *(const ulonglong2*)&keys[j];
+      r += (o.x < mine ? 1u : 0u) + (o.y < mine ? 1u : 0u);
+    }
+    if (r < a.k) {
+      a.ids_out[(size_t)q * a.k + r] = (uint64_t)ids[i];                 // [Q][k] u64 :1366
+      a.dists_out[(size_t)r * a.Q_total + q] = e[i];                      // [rank][Q] :999,1297
+    }
+  }
+  for (uint32_t r = n + threadIdx.x; r < a.k; r += blockDim.x) {          // CANON tail
+    a.ids_out[(size_t)q * a.k + r] = ~0ull;
+    a.dists_out[(size_t)r * a.Q_total + q] = BIG_DIST;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
   __shared__ float e[RERANK_MAX_CAND + 2];
@@ -875,6 +903,7 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
   }
 ranked:
   __syncthreads();
+  // (rerank_rank above is a copy of this tail for rerank_f16_kernel: a change here belongs there too)
   // stable rank by exact distance; ties keep expansion order (:1330-1363): rank = #{(distance, index) pairs below mine}.  Exact
   // distances are sums of squares -- non-negative floats, which order like their bit patterns -- so the pair is ONE unsigned 64-bit key
   // {distance bits, index} and the rank one compare per pair (the two-level float rule costs three).
@@ -897,6 +926,104 @@ ranked:
     a.ids_out[(size_t)q * a.k + r] = ~0ull;
     a.dists_out[(size_t)r * a.Q_total + q] = BIG_DIST;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// fp16 vector table (option vectors_fp16)
+// ------------------------------------------------------------------------------------------
+// (f32_to_f16_bits: csrc/bang_f16.h -- plain integer C, also compiled on the host by tests/test_f16_convert_host.py)
+// rows of D floats -> rows of halves, one output dword (two elements) per thread; the padding half of an odd D is 0
+__global__ __launch_bounds__(256) void f32_to_f16_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint64_t rows, uint32_t D,
+                                                         uint64_t src_stride, uint64_t dst_stride, uint32_t* bad_count) {
+  const uint32_t ndw = (D + 1u) >> 1;
+  const uint64_t total = rows * ndw;
+  uint32_t bad = 0;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = t / ndw;
+    const uint32_t w = (uint32_t)(t - r * ndw), j = 2u * w;
+    const uint32_t* v = (const uint32_t*)(src + r * src_stride);
+    bool o0 = false, o1 = false;
+    const uint32_t lo = f32_to_f16_bits(v[j], &o0);
+    const uint32_t hi = (j + 1u < D) ? f32_to_f16_bits(v[j + 1u], &o1) : 0u;
+    bad += (o0 ? 1u : 0u) + (o1 ? 1u : 0u);
+    *(uint32_t*)(dst + r * dst_stride + 4ull * w) = lo | (hi << 16);
+  }
+  if (bad_count) {                                          // one atomic per wave that saw any
+    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
+    if ((threadIdx.x & 63u) == 0 && bad) atomicAdd(bad_count, bad);
+  }
+}
+
+__device__ __forceinline__ float f16_bits_to_f32(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }   // exact (v_cvt_f32_f16)
+
+// K6 + K7 out of the fp16 table: candidate id's row at vec_base + id * vec_stride, float query (MIPS-padded), any D.  As in rerank_kernel's
+// float path a WAVE fetches the rows of B = 16 candidates with contiguous dwords -- lane l takes dwords l, l + 64, ... of a row, one request per
+// line -- for a TILE of 128 dwords (256 dimensions) at a time, hands them over through LDS (row stride 129 words: the 16 lanes that then walk
+// their own rows hit 16 banks), and lane c < 16 continues candidate c's ascending chain over the tile while the next tile travels.
+#define RR16_B 16u
+#define RR16_TILE 128u
+#define RR16_STRIDE 129u
+#define RR16_STATIC_LDS ((RERANK_MAX_CAND + 2) * 16u + 4u * RR16_B * RR16_STRIDE * 4u)   /* e + ids + keys + stage_all of rerank_f16_kernel */
+__global__ __launch_bounds__(256) void rerank_f16_kernel(const RerankArgs a) {
+  __shared__ float e[RERANK_MAX_CAND + 2];
+  __shared__ uint32_t ids[RERANK_MAX_CAND + 2];
+  __shared__ __attribute__((aligned(16))) unsigned long long keys[RERANK_MAX_CAND + 2];
+  __shared__ uint32_t stage_all[4 * RR16_B * RR16_STRIDE];
+  static_assert(sizeof(e) + sizeof(ids) + sizeof(keys) + sizeof(stage_all) == RR16_STATIC_LDS, "bang_k_rerank_f16_range checks this figure");
+  extern __shared__ __attribute__((aligned(16))) uint8_t qraw[];
+  float* qv = (float*)qraw;
+  const uint32_t q = a.q0 + blockIdx.x;
+  const uint32_t qdim = a.D - a.dim_adjust;
+  for (uint32_t j = threadIdx.x; j < a.D; j += blockDim.x)          // MIPS zero pad :1276-1286
+    qv[j] = (j < qdim) ? ((const float*)a.queries)[(size_t)q * qdim + j] : 0.0f;
+  uint32_t n = a.cand_cnt[q];
+  if (n > RERANK_MAX_CAND) n = RERANK_MAX_CAND;
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) ids[i] = a.cand_ids[(size_t)q * a.cand_stride + i];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t ndw = (a.D + 1u) >> 1, NT = (ndw + RR16_TILE - 1u) / RR16_TILE;
+  uint32_t* stage = stage_all + wave * (RR16_B * RR16_STRIDE);
+  uint32_t val[RR16_B][2] = {};
+  auto fetch = [&](uint32_t b0, uint32_t t) {                        // tile t of the rows of candidates b0 .. b0 + 15
+#pragma unroll
+    for (uint32_t c = 0; c < RR16_B; ++c) {
+      const uint32_t i = b0 + c;
+      const uint32_t* v = (const uint32_t*)(a.vec_base + (uint64_t)ids[i < n ? i : 0u] * a.vec_stride);
+#pragma unroll
+      for (uint32_t u = 0; u < 2; ++u) {
+        const uint32_t dw = t * RR16_TILE + u * 64u + lane;
+        if (t * RR16_TILE + u * 64u < ndw) val[c][u] = v[dw < ndw ? dw : 0u];      // (uniform: a row of up to 128 dimensions is one load per candidate)
+      }
+    }
+  };
+  if (wave * RR16_B < n) fetch(wave * RR16_B, 0);
+  for (uint32_t b0 = wave * RR16_B; b0 < n; b0 += 4u * RR16_B) {      // (uniform per wave)
+    float acc = 0.0f;
+    for (uint32_t t = 0; t < NT; ++t) {
+#pragma unroll
+      for (uint32_t c = 0; c < RR16_B; ++c)
+#pragma unroll
+        for (uint32_t u = 0; u < 2; ++u)
+          if (t * RR16_TILE + u * 64u < ndw) stage[c * RR16_STRIDE + u * 64u + lane] = val[c][u];
+      __builtin_amdgcn_wave_barrier();                               // (one wave: its LDS operations execute in order)
+      if (t + 1u < NT) fetch(b0, t + 1u);                            // the next tile, or the next batch, travels while this one is evaluated
+      else if (b0 + 4u * RR16_B < n) fetch(b0 + 4u * RR16_B, 0);
+      if (lane < RR16_B && b0 + lane < n) {
+        const uint32_t* sv = stage + lane * RR16_STRIDE;
+        const uint32_t dw0 = t * RR16_TILE, cnt = ndw - dw0 < RR16_TILE ? ndw - dw0 : RR16_TILE;
+        for (uint32_t w = 0; w < cnt; ++w) {
+          const uint32_t x = sv[w], j = 2u * (dw0 + w);
+          float diff = f16_bits_to_f32(x & 0xFFFFu) - qv[j];
+          acc = __builtin_fmaf(diff, diff, acc);
+          if (j + 1u < a.D) { diff = f16_bits_to_f32(x >> 16) - qv[j + 1u]; acc = __builtin_fmaf(diff, diff, acc); }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (lane < RR16_B && b0 + lane < n) e[b0 + lane] = acc;
+  }
+  __syncthreads();
+  rerank_rank(a, q, n, e, ids, keys);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1275,4 +1402,53 @@ extern "C" int bang_k_rerank(const void* d_vec_base, uint64_t vec_stride, const 
                              uint64_t* d_ids_out, float* d_dists_out, void* stream) {
   return bang_k_rerank_range(d_vec_base, vec_stride, d_medoid_vec, d_queries, dtype, d_cand_ids, d_cand_row, d_cand_cnt,
                              cand_stride, 0, Q, Q, D, k, dim_adjust, d_ids_out, d_dists_out, stream);
+}
+
+extern "C" int bang_k_f32_to_f16(const void* d_src, void* d_dst, uint64_t rows, uint32_t D, uint64_t src_stride, uint64_t dst_stride,
+                                 uint32_t* d_bad_count, void* stream) {
+  if (rows == 0) return BANG_OK;
+  const uint64_t row = ((uint64_t)2 * D + 3u) & ~(uint64_t)3;
+  if (!d_src || !d_dst || D == 0 || (((uintptr_t)d_src | (uintptr_t)d_dst | src_stride | dst_stride) & 3u) || src_stride < 4ull * D || dst_stride < row) {
+    bang_set_error("bang_k_f32_to_f16: null / unaligned buffer, or a stride that does not hold a row (D = %u, src_stride = %llu, dst_stride = %llu)", D,
+                   (unsigned long long)src_stride, (unsigned long long)dst_stride);
+    return BANG_ERR_ARG;
+  }
+  const uint64_t total = rows * ((D + 1u) >> 1);
+  const uint64_t want = (total + 255) / 256;
+  const int blocks = (int)(want < 16384 ? want : 16384);
+  hipLaunchKernelGGL(f32_to_f16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, (uint8_t*)d_dst, rows, D, src_stride,
+                     dst_stride, d_bad_count);
+  HIP_TRY(hipGetLastError());
+  return BANG_OK;
+}
+
+extern "C" int bang_k_rerank_f16_range(const void* d_vec_base, uint64_t vec_stride, const void* d_queries, const uint32_t* d_cand_ids,
+                                       const uint32_t* d_cand_cnt, uint32_t cand_stride, uint32_t q0, uint32_t nq, uint32_t Q_total, uint32_t D,
+                                       uint32_t k, uint32_t dim_adjust, uint64_t* d_ids_out, float* d_dists_out, void* stream) {
+  if (nq == 0) return BANG_OK;
+  if (k == 0 || k > BANG_MAX_L) { bang_set_error("bad k"); return BANG_ERR_ARG; }
+  if (!d_vec_base || (((uintptr_t)d_vec_base | vec_stride) & 3u) || D == 0 || vec_stride < (((uint64_t)2 * D + 3u) & ~(uint64_t)3) || dim_adjust >= D) {
+    bang_set_error("bang_k_rerank_f16: the fp16 table is null / not 4-byte aligned, or vec_stride = %llu does not hold a row of D = %u halves",
+                   (unsigned long long)vec_stride, D);
+    return BANG_ERR_ARG;
+  }
+  RerankArgs a;
+  a.vec_base = (const uint8_t*)d_vec_base; a.vec_stride = vec_stride; a.medoid_vec = nullptr;
+  a.queries = d_queries; a.cand_ids = d_cand_ids; a.cand_row = nullptr; a.cand_cnt = d_cand_cnt;
+  a.cand_stride = cand_stride; a.q0 = q0; a.nq = nq; a.Q_total = Q_total; a.D = D; a.k = k; a.dim_adjust = dim_adjust;
+  a.by_query = 0; a.stage_off = 0;
+  a.ids_out = d_ids_out; a.dists_out = d_dists_out;
+  const size_t lds = ((size_t)D * sizeof(float) + 15) & ~(size_t)15;
+  // (the block also holds RR16_STATIC_LDS bytes of static LDS: distances, ids, keys and the four waves' tiles)
+  if (lds + RR16_STATIC_LDS > 64 * 1024) { bang_set_error("bang_k_rerank_f16: D = %u: the query does not fit the block's LDS beside its tiles", D); return BANG_ERR_UNSUPPORTED; }
+  hipLaunchKernelGGL(rerank_f16_kernel, dim3(nq), dim3(256), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return BANG_OK;
+}
+
+extern "C" int bang_k_rerank_f16(const void* d_vec_base, uint64_t vec_stride, const void* d_queries, const uint32_t* d_cand_ids,
+                                 const uint32_t* d_cand_cnt, uint32_t cand_stride, uint32_t Q, uint32_t D, uint32_t k, uint32_t dim_adjust,
+                                 uint64_t* d_ids_out, float* d_dists_out, void* stream) {
+  return bang_k_rerank_f16_range(d_vec_base, vec_stride, d_queries, d_cand_ids, d_cand_cnt, cand_stride, 0, Q, Q, D, k, dim_adjust, d_ids_out,
+                                 d_dists_out, stream);
 }

@@ -115,7 +115,8 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     tl_t = Clock::now();
   };
   // K6 + K7 inside the search launch (8-bit vectors, self-paced form): no launch behind it
-  const bool fused_rerank = e->search_v2 && e->fuse_rerank != 0 && (dev_graph || e->vec_on_device) &&
+  // (an fp16 vector table, option vectors_fp16, is read by the re-rank launch only)
+  const bool fused_rerank = e->search_v2 && e->fuse_rerank != 0 && (dev_graph || e->vec_on_device) && !e->vecs_f16 &&
                             bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : vb, dim_adjust) != 0;
   // distance = 1: the exact-distance kernel writes the results itself, as the fused re-rank does (no launch behind it)
   const bool results_in_launch = fused_rerank || e->search_exact;
@@ -177,7 +178,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
       sp.d_graph = (const uint8_t*)e->d_adj; sp.entry_len = 256; sp.row_layout = 1;
       sp.d_rows_hbm = e->d_rows_hbm; sp.n_rows_hbm = e->rows_first == 0 ? e->n_rows_hbm : 0;      // (a moved slice is only reachable through the table)
       if (e->n_slices > 1 && e->d_slice_tab) { sp.d_row_slices = e->d_slice_tab; sp.n_slices = e->n_slices; sp.slice_rows = e->slice_rows; }
-      sp.rr_vec_base = e->d_vecs; sp.rr_vec_stride = vb;
+      sp.rr_vec_base = e->d_vecs; sp.rr_vec_stride = vec_table_stride(e); sp.rr_vec_f16 = e->vecs_f16 ? 1u : 0u;
     }
     sp.d_bloom = p.d_bloom; sp.d_cand_ids = p.d_cand_ids; sp.d_cand_cnt = p.d_cand_cnt; sp.d_qstats = p.d_qstats;
     sp.d_qiters = e->d_qiters + ln.q0; sp.d_next_query = ln.d_pcnt; sp.d_abort = ln.d_pcnt + 1; sp.n_nodes = e->N;
@@ -444,6 +445,9 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
       BANG_TRY(bang_k_rerank_range(e->d_graph, e->entry_len, e->d_medoid_vec, e->d_queries, e->dtype, e->d_cand_ids,
                                    nullptr, e->d_cand_cnt, e->cand_stride, ln.q0, ln.nq, (uint32_t)Q, e->D,
                                    (uint32_t)e->k, dim_adjust, e->d_ids_out, e->d_dists_out, ln.s_main));
+    else if (e->vec_on_device && e->vecs_f16)
+      BANG_TRY(bang_k_rerank_f16_range(e->d_vecs, vec_table_stride(e), e->d_queries, e->d_cand_ids, e->d_cand_cnt, e->cand_stride, ln.q0, ln.nq,
+                                       (uint32_t)Q, e->D, (uint32_t)e->k, dim_adjust, e->d_ids_out, e->d_dists_out, ln.s_main));
     else if (e->vec_on_device)
       BANG_TRY(bang_k_rerank_range(e->d_vecs, vb, e->d_medoid_vec, e->d_queries, e->dtype, e->d_cand_ids, nullptr, e->d_cand_cnt,
                                    e->cand_stride, ln.q0, ln.nq, (uint32_t)Q, e->D, (uint32_t)e->k, dim_adjust, e->d_ids_out,

@@ -423,9 +423,47 @@ static int stage_medoid(bang_engine* e, const uint8_t* me) {
   return BANG_OK;
 }
 
+// Option vectors_fp16: the HBM vector table as IEEE fp16 rows.  A staged chunk of packed float vectors goes up into ONE bounded device staging
+// buffer and bang_k_f32_to_f16 converts it into the table -- both on the null stream, so a chunk's upload waits for the conversion of the one
+// before it.  Finite values the conversion turns into +-inf are counted on the device; the load fails on them (finish()).
+struct Fp16Fill {
+  uint8_t* d_stage = nullptr;
+  uint32_t* d_bad = nullptr;
+  ~Fp16Fill() { dfree(d_stage); dfree(d_bad); }
+  int open(size_t stage_bytes) {
+    HIP_TRY(hipMalloc((void**)&d_stage, std::max<size_t>(stage_bytes, 16)));
+    BANG_TRY(dmalloc(&d_bad, 1));
+    HIP_TRY(hipMemset(d_bad, 0, 4));
+    return BANG_OK;
+  }
+  // rows [first, first + n) of the table from n packed float vectors in pinned host memory
+  int chunk(bang_engine* e, size_t first, size_t n, const uint8_t* h_packed) {
+    const size_t vb = vec_bytes(e), row = vec_table_stride(e);
+    HIP_TRY(hipMemcpyAsync(d_stage, h_packed, n * vb, hipMemcpyHostToDevice, nullptr));
+    return bang_k_f32_to_f16(d_stage, e->d_vecs + first * row, n, e->D, vb, row, d_bad, nullptr);
+  }
+  int finish(bang_engine* e) {
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
+    if (bad) {
+      bang_set_error("option vectors_fp16 = 1: %u vector element%s finite in the index but beyond the fp16 range (|x| >= 65520); nothing is turned into inf", bad,
+                     bad == 1 ? " is" : "s are");
+      return BANG_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(hipMemset(e->d_vecs + (size_t)e->N * vec_table_stride(e), 0, 256));
+    return BANG_OK;
+  }
+};
+
+// graph entries a streamed load takes per chunk
+static size_t stream_chunk_entries(const bang_engine* e) {
+  return std::max<size_t>(1024, std::min<size_t>((size_t)1 << 20, ((size_t)512 << 20) / e->entry_len));
+}
+
 // Can this index run in pull mode without a resident graph?  (vectors in HBM, rows in host memory, no walker option forced)
 static bool stream_feasible(bang_engine* e, size_t hbm_reserve, std::string* why) {
-  const size_t need = (size_t)e->N * vec_bytes(e);
+  // the table, and while an fp16 table is being filled the device staging buffer of one chunk of float vectors (freed when the load ends)
+  const size_t need = (size_t)e->N * vec_table_stride(e) + (e->vecs_f16 ? std::min<size_t>(stream_chunk_entries(e), e->N) * vec_bytes(e) : 0);
   size_t free_b = 0, total_b = 0;
   (void)hipMemGetInfo(&free_b, &total_b);
   if (e->pull_opt == 0) { if (why) *why = "option pull = 0"; return false; }
@@ -441,10 +479,12 @@ static bool stream_feasible(bang_engine* e, size_t hbm_reserve, std::string* why
 static int stage_entries_streamed(bang_engine* e, bool retried = false) {
   const size_t vb = vec_bytes(e), N = e->N, el = e->entry_len;
   if (e->ext_vecs) { e->d_vecs = e->ext_vecs; e->vecs_owned = false; }      // the caller's buffer: it can hand the vectors on (xGMI broadcast)
-  else { HIP_TRY(hipMalloc((void**)&e->d_vecs, N * vb + 256)); e->vecs_owned = true; }
+  else { HIP_TRY(hipMalloc((void**)&e->d_vecs, N * vec_table_stride(e) + 256)); e->vecs_owned = true; }
   PullRows pr;
   BANG_TRY(pull_rows_open(e, pr, nullptr));
-  const size_t chunk = std::max<size_t>(1024, std::min<size_t>((size_t)1 << 20, ((size_t)512 << 20) / el));
+  const size_t chunk = stream_chunk_entries(e);
+  Fp16Fill f16;
+  if (e->vecs_f16) { const int frc = f16.open(std::min(chunk, N) * vb); if (frc != BANG_OK) { pull_rows_abandon(pr); return frc; } }
   void* bufp = nullptr;
   if (posix_memalign(&bufp, 4096, chunk * el) != 0) { pull_rows_abandon(pr); bang_set_error("streamed load: no memory for a chunk"); return BANG_ERR_NOMEM; }
   uint8_t* buf = (uint8_t*)bufp;
@@ -489,12 +529,14 @@ static int stage_entries_streamed(bang_engine* e, bool retried = false) {
         });
       for (auto& x : th) x.join();
     }
-    if (hipMemcpyAsync(e->d_vecs + first * vb, stage[b], n * vb, hipMemcpyHostToDevice, nullptr) != hipSuccess ||
-        hipEventRecord(ev[b], nullptr) != hipSuccess) { bang_set_error("streamed load: vector upload failed"); rc = BANG_ERR_HIP; break; }
+    if (e->vecs_f16) { rc = f16.chunk(e, first, n, stage[b]); if (rc != BANG_OK) break; }
+    else if (hipMemcpyAsync(e->d_vecs + first * vb, stage[b], n * vb, hipMemcpyHostToDevice, nullptr) != hipSuccess) { bang_set_error("streamed load: vector upload failed"); rc = BANG_ERR_HIP; break; }
+    if (hipEventRecord(ev[b], nullptr) != hipSuccess) { bang_set_error("streamed load: vector upload failed"); rc = BANG_ERR_HIP; break; }
   }
   if (rc == BANG_OK && hipDeviceSynchronize() != hipSuccess) { bang_set_error("streamed load: sync"); rc = BANG_ERR_HIP; }
+  if (rc == BANG_OK && e->vecs_f16) rc = f16.finish(e);
   cleanup();
-  if (rc != BANG_OK) { (void)hipGetLastError(); pull_rows_abandon(pr); return rc; }
+  if (rc != BANG_OK) { if (rc == BANG_ERR_HIP) (void)hipGetLastError(); pull_rows_abandon(pr); return rc; }
   for (uint64_t v : part) h += v;
   {
     const int frc = pull_rows_finish(e, pr, sig_make(e, h));
@@ -728,6 +770,18 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     return BANG_ERR_IO;
   }
   if (e->medoid >= e->N) { bang_set_error("medoid out of range"); return BANG_ERR_IO; }
+  // option vectors_fp16: what it cannot apply to is refused (the table of a device placement IS the graph entries: checked once auto is resolved)
+  e->vecs_f16 = false;
+  if (e->vectors_fp16 == 1) {
+    const char* no = nullptr;
+    if (e->dtype != BANG_F32) no = "the index holds 8-bit vectors (float vectors only)";
+    else if (e->graph_mode == BANG_GRAPH_DEVICE) no = "option graph = device (the vectors are the graph entries there)";
+    else if (e->vectors_opt == 0) no = "option vectors = 0 (there is no vector table in HBM)";
+    else if (e->ext_vecs && e->ext_vecs_ready) no = "a shared load (the table of another rank is not converted)";
+    else if (e->ext_vecs) no = "a caller's vector buffer (bang_index_desc.d_vectors)";
+    if (no) { bang_set_error("option vectors_fp16 = 1 does not apply: %s", no); return BANG_ERR_UNSUPPORTED; }
+    e->vecs_f16 = true;
+  }
   // PQ layout first: it decides how the code rows are laid out in HBM
   uint32_t psz = 0, mp = m;
   BANG_TRY(bang_pq_layout(chunk_off, D, m, &psz, &mp));
@@ -754,7 +808,7 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     if (pad != m) {
       size_t free_b = 0, total_b = 0;
       (void)hipMemGetInfo(&free_b, &total_b);
-      const size_t N_ = e->N, gbytes = N_ * e->entry_len + 256, vbytes = N_ * (size_t)D * e->tsize;
+      const size_t N_ = e->N, gbytes = N_ * e->entry_len + 256, vbytes = N_ * vec_table_stride(e);
       const bool dev_packed = N_ * m + gbytes + hbm_reserve <= free_b;
       bool ok;
       if (e->graph_mode == BANG_GRAPH_DEVICE || (e->graph_mode == BANG_GRAPH_AUTO && dev_packed)) ok = N_ * pad + gbytes + hbm_reserve <= free_b;   // (never flips auto to host)
@@ -804,6 +858,10 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     e->graph_mode = (gbytes + hbm_reserve <= free_b) ? BANG_GRAPH_DEVICE : BANG_GRAPH_HOST;
     if (env_flag("BANG_DEBUG")) fprintf(stderr, "[bang] graph=auto -> %s (graph %.1f GB, free HBM %.1f GB)\n",
                                       e->graph_mode == BANG_GRAPH_DEVICE ? "device" : "host", gbytes / 1e9, free_b / 1e9);
+    if (e->vecs_f16 && e->graph_mode == BANG_GRAPH_DEVICE) {
+      bang_set_error("option vectors_fp16 = 1 does not apply: option graph = auto placed this index in HBM (graph = device: the vectors are the graph entries there)");
+      return BANG_ERR_UNSUPPORTED;
+    }
   }
   // pivots: transposed [D][256] for K1 (bang_search.cu:281-285) and chunk-packed for the LDS kernel
   std::vector<float> pt((size_t)D * 256);
@@ -881,27 +939,42 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     // 288 GB of HBM hold the full-precision vectors of a billion uint8 points (128 GB) next to their PQ codes (70 GB): keep a
     // packed copy on the device for the re-rank, so that the walker ships adjacency rows only (a third less PCIe traffic per
     // expanded node).  "auto" = whenever the copy fits the free HBM with 16 GB to spare.
-    const size_t vb = vec_bytes(e), need = (size_t)e->N * vb;
+    const size_t vb = vec_bytes(e), row = vec_table_stride(e), need = (size_t)e->N * row;
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     if (e->vectors_opt == 1 || need + hbm_reserve <= free_b) {
       HIP_TRY(hipMalloc((void**)&e->d_vecs, need + 256));
       const size_t rows_per = std::max<size_t>(1, ((size_t)32 << 20) / vb);
+      Fp16Fill f16;
       uint8_t* stage[2] = {nullptr, nullptr};
-      hipEvent_t ev[2];
-      for (int b = 0; b < 2; ++b) { HIP_TRY(hipHostMalloc((void**)&stage[b], rows_per * vb, hipHostMallocDefault)); HIP_TRY(hipEventCreate(&ev[b])); }
-      int b = 0;
-      for (size_t r0 = 0; r0 < e->N; r0 += rows_per, b ^= 1) {
-        const size_t nr = std::min(rows_per, (size_t)e->N - r0);
-        HIP_TRY(hipEventSynchronize(ev[b]));               // the previous copy out of this buffer has finished
-        for (size_t r = 0; r < nr; ++r) memcpy(stage[b] + r * vb, e->graph + (r0 + r) * e->entry_len, vb);
-        HIP_TRY(hipMemcpyAsync(e->d_vecs + r0 * vb, stage[b], nr * vb, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipEventRecord(ev[b], nullptr));
-      }
-      HIP_TRY(hipDeviceSynchronize());
-      for (int i = 0; i < 2; ++i) { (void)hipHostFree(stage[i]); (void)hipEventDestroy(ev[i]); }
+      hipEvent_t ev[2] = {nullptr, nullptr};
+      // the loop as a lambda, so that the pinned buffers and events are released on every way out -- a value beyond the fp16 range is an
+      // expected refusal, not a runtime failure
+      auto fill = [&]() -> int {
+        if (e->vecs_f16) BANG_TRY(f16.open(std::min(rows_per, (size_t)e->N) * vb));
+        for (int b = 0; b < 2; ++b) { HIP_TRY(hipHostMalloc((void**)&stage[b], rows_per * vb, hipHostMallocDefault)); HIP_TRY(hipEventCreate(&ev[b])); }
+        int b = 0;
+        for (size_t r0 = 0; r0 < e->N; r0 += rows_per, b ^= 1) {
+          const size_t nr = std::min(rows_per, (size_t)e->N - r0);
+          HIP_TRY(hipEventSynchronize(ev[b]));               // the previous copy out of this buffer has finished
+          for (size_t r = 0; r < nr; ++r) memcpy(stage[b] + r * vb, e->graph + (r0 + r) * e->entry_len, vb);
+          if (e->vecs_f16) BANG_TRY(f16.chunk(e, r0, nr, stage[b]));
+          else HIP_TRY(hipMemcpyAsync(e->d_vecs + r0 * vb, stage[b], nr * vb, hipMemcpyHostToDevice, nullptr));
+          HIP_TRY(hipEventRecord(ev[b], nullptr));
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        return e->vecs_f16 ? f16.finish(e) : BANG_OK;
+      };
+      const int frc = fill();
+      if (frc != BANG_OK) (void)hipDeviceSynchronize();      // nothing reads a staging buffer any more
+      for (int i = 0; i < 2; ++i) { if (stage[i]) (void)hipHostFree(stage[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); }
+      if (frc != BANG_OK) return frc;
       e->vec_on_device = true;
     }
+  }
+  if (e->vecs_f16 && !e->vec_on_device) {
+    bang_set_error("option vectors_fp16 = 1 does not apply: the vector table does not fit HBM even as fp16 (option vectors = auto kept the vectors on the host)");
+    return BANG_ERR_UNSUPPORTED;
   }
   if (e->graph_mode != BANG_GRAPH_DEVICE && e->pull_opt != 0) {
     // pull needs the re-rank's vectors in HBM (nothing walks the graph entries any more) and rows of <= 64 ids
@@ -945,7 +1018,7 @@ void unload_index(bang_engine* e) {
   dfree(e->d_graph);
   if (e->vecs_owned) dfree(e->d_vecs);
   e->d_vecs = nullptr; e->vecs_owned = true; e->ext_vecs = nullptr; e->ext_vecs_ready = false; e->rows_hash = 0;
-  e->vec_on_device = false;
+  e->vec_on_device = false; e->vecs_f16 = false;
   for (uint32_t s = 0; s < BANG_MAX_ROW_SLICES; ++s) {
     if (e->peer_ptr[s]) (void)hipIpcCloseMemHandle(e->peer_ptr[s]);
     e->peer_ptr[s] = nullptr; e->slice_base[s] = 0;

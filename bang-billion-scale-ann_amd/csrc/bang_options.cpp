@@ -38,6 +38,11 @@ static const OptionDef kOptions[] = {
     {"vectors", "BANG_VECTORS", &bang_engine::vectors_opt, -1, 1, INT, BEFORE_LOAD,
      "host graph: 1 = packed copy of the full-precision vectors in HBM for the re-rank, 0 = the walker ships every expanded node's vector "
      "(the reference's data flow), -1 = auto (1 when the copy fits with 16 GB to spare)"},
+    {"vectors_fp16", "BANG_VECTORS_FP16", &bang_engine::vectors_fp16, 0, 1, INT, BEFORE_LOAD,
+     "host graph, float vectors: 1 = that copy holds IEEE fp16 rows (round to nearest even on the GPU at load; half the HBM): the re-rank launch and, with "
+     "distance = 1 and pull = 1 (D % 8 == 0, D <= 256), the exact-distance kernel read it, and every exact distance is the usual arithmetic on the "
+     "ROUNDED vectors; the re-rank is not fused into the search launch.  A load whose vectors hold a finite |x| >= 65520 fails.  Refused for 8-bit "
+     "vectors, graph = device, vectors = 0, a caller's vector buffer and shared loads.  0 = float rows (default)"},
     {"pull", "BANG_PULL", &bang_engine::pull_opt, -1, 1, INT, BEFORE_LOAD,
      "host graph: 1 = the search kernel pulls 256-byte adjacency rows from pinned host memory over PCIe, 0 = C++ walker threads serve them, -1 = auto"},
     {"rows_hbm", "BANG_ROWS_HBM", &bang_engine::rows_hbm_opt, -1, 1 << 22, INT, BEFORE_LOAD,

@@ -35,6 +35,10 @@
 //    bang_search_exact_wide_pull.o; kernels search_exact_pull_kernel / search_exact_wide_pull_kernel; row_layout 1).  The same loop; a node's
 //    vector comes from the packed table rr_vec_base + id * rr_vec_stride and the parent's adjacency row as 256 bytes -- one dword per lane -- from
 //    a slice of the node's HBM-resident rows, from the HBM copy of the first rows or from pinned host memory over PCIe.
+//  * FP16 VECTOR TABLE (a fifth build, -DBANG_EXACT_PULL=1 -DBANG_EXACT_F16=1 as bang_search_exact_pull_f16.o; ONE instance, kernel
+//    search_exact_pull_f16_kernel; rr_vec_f16 = 1).  The pulled-rows loop on a float index whose table holds IEEE fp16 rows (engine option
+//    vectors_fp16): D % 8 == 0, D <= 256, the query float in registers as above; a lane reads its survivor's row eight elements per 16-byte load,
+//    four loads in flight, and runs the same ascending chain on float(h[j]) - q[j] (exact_dist_f16).  Everything it adds sits under BANG_EXACT_F16.
 //
 // Reference line numbers: the reference's BANG_Base/bang_search.cu unless a file is named.
 
@@ -132,6 +136,57 @@ __device__ __forceinline__ void exact_dist_f32(const uint8_t GAS* graph, uint64_
     if (i < n) dist[i] = acc;
   }
 }
+
+#ifdef BANG_EXACT_F16
+#if !defined(BANG_EXACT_PULL) || defined(BANG_EXACT_WIDE)
+#error "BANG_EXACT_F16 builds the narrow pulled-rows instance only"
+#endif
+__device__ __forceinline__ float half_bits_to_float(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }   // exact (v_cvt_f32_f16)
+
+// exact_dist_f32 on rows of IEEE fp16 (D % 8 == 0, <= 256; rows 4-byte aligned): lane i evaluates survivor i0 + i, eight elements per 16-byte
+// load, the ascending fmaf chain on float(h[j]) - q[j]
+__device__ __forceinline__ void exact_dist_f16(const uint8_t GAS* tab, uint64_t stride, uint32_t D, const uint32_t* sid, uint32_t n,
+                                               float* dist, const float (&qr)[4], int lane) {
+  constexpr int RF = 4;                                           // 16-byte loads in flight per lane
+  for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform)
+    const uint32_t i = i0 + (uint32_t)lane;
+    const uint32_t id = sid[i < n ? i : 0u];
+    const uint8_t GAS* v = tab + (uint64_t)id * stride;
+    float acc = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t jt = (uint32_t)t * 64u;
+      if (jt >= D) break;                                         // (uniform)
+      const uint32_t dt = D - jt < 64u ? D - jt : 64u;
+      for (uint32_t jl = 0; jl < dt; jl += 8u * RF) {             // (uniform)
+        u32x4a w[RF];
+#pragma unroll
+        for (int u = 0; u < RF; ++u) {
+          const uint32_t j = jl + 8u * (uint32_t)u;
+          w[u] = *(const u32x4a GAS*)(v + 2u * (jt + (j < dt ? j : 0u)));
+        }
+#pragma unroll
+        for (int u = 0; u < RF; ++u) {
+          const uint32_t j = jl + 8u * (uint32_t)u;
+          if (j < dt) {                                           // (uniform)
+            const uint32_t ww[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+#pragma unroll
+              for (int b = 0; b < 2; ++b) {
+                const float qv = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qr[t]), (int)(j + 2u * (uint32_t)d + (uint32_t)b)));
+                const float diff = half_bits_to_float(b ? ww[d] >> 16 : ww[d] & 0xFFFFu) - qv;      // vector - query, as exact_dist_f32
+                acc = __builtin_fmaf(diff, diff, acc);            // ascending dimension
+              }
+            }
+          }
+        }
+      }
+    }
+    if (i < n) dist[i] = acc;
+  }
+}
+#endif
 
 #ifdef BANG_EXACT_WIDE
 // ---------------------------------------------------------------------------------------------------------------------
@@ -250,7 +305,9 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
 // wave: 12 waves per CU, no scratch (bang_search_exact_wide_geometry reads both figures off the instance)
 #define EXACT_MAX_THREADS(DT) ((DT) == BANG_F32 ? 768 : 1024)
 #else
-#ifdef BANG_EXACT_PULL
+#if defined(BANG_EXACT_F16)
+#define EXACT_KERNEL search_exact_pull_f16_kernel
+#elif defined(BANG_EXACT_PULL)
 #define EXACT_KERNEL search_exact_pull_kernel
 #else
 #define EXACT_KERNEL search_exact_kernel
@@ -421,7 +478,11 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 #ifdef BANG_EXACT_WIDE
         exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, scratch + EXACT_SCRATCH_WORDS, qr, qw, qq, lane);
 #else
+#ifdef BANG_EXACT_F16
+        if (DT == BANG_F32) exact_dist_f16(graph, entry_len, D, sc, n, sdist, qr, lane);
+#else
         if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, sc, n, sdist, qr, lane);
+#endif
         else exact_dist8<DT == BANG_I8>(graph, entry_len, G, sc, n, sdist, qw, qq, lane);
 #endif
       }
@@ -538,7 +599,9 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 #endif
 #else
 #define EXACT_EXTRA_WORDS 0u
-#if EXACT_PULL
+#if defined(BANG_EXACT_F16)
+#define EXACT_GEOMETRY bang_search_exact_pull_f16_geometry
+#elif EXACT_PULL
 #define EXACT_GEOMETRY bang_search_exact_pull_geometry
 #else
 #define EXACT_GEOMETRY bang_search_exact_geometry
@@ -546,8 +609,10 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 #endif
 
 static const void* exact_instance(int dtype) {
+#ifndef BANG_EXACT_F16                                             // (float queries on fp16 rows: the one instance of that build)
   if (dtype == BANG_U8) return (const void*)EXACT_KERNEL<BANG_U8>;
   if (dtype == BANG_I8) return (const void*)EXACT_KERNEL<BANG_I8>;
+#endif
   if (dtype == BANG_F32) return (const void*)EXACT_KERNEL<BANG_F32>;
   return nullptr;
 }
@@ -624,13 +689,22 @@ static int exact_launch(const bang_search_params* p, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(grid_n), block(waves * WAVE);
   if (p->rr_dtype == BANG_F32) hipLaunchKernelGGL(EXACT_KERNEL<BANG_F32>, grid, block, lds, st, a);
+#ifndef BANG_EXACT_F16
   else if (p->rr_dtype == BANG_I8) hipLaunchKernelGGL(EXACT_KERNEL<BANG_I8>, grid, block, lds, st, a);
   else hipLaunchKernelGGL(EXACT_KERNEL<BANG_U8>, grid, block, lds, st, a);
+#endif
   HIP_TRY(hipGetLastError());
   return BANG_OK;
 }
 
-#if EXACT_PULL
+#if defined(BANG_EXACT_F16)
+// the pulled-rows instance on an fp16 vector table, called by bang_k_search_exact with its arguments checked
+extern "C" int bang_k_search_exact_pull_f16(const bang_search_params* p, void* stream) {
+  if (!p || p->row_layout != 1u || p->rr_vec_f16 != 1u || p->rr_dtype != BANG_F32 || p->rr_D % 8u != 0u || p->rr_D > 256u || (p->rr_vec_stride & 3u) ||
+      p->rr_vec_stride < 2ull * p->rr_D) return BANG_ERR_ARG;
+  return exact_launch(p, stream);
+}
+#elif EXACT_PULL
 // the pulled-rows instances (row_layout 1), called by bang_k_search_exact with its arguments checked: the layouts of the fused re-rank on the
 // narrow instances, the others on the wide ones
 #ifdef BANG_EXACT_WIDE
@@ -669,12 +743,24 @@ extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
   }
   if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("distance = 1: bad iteration cap"); return BANG_ERR_ARG; }
   if (p->rr_k == 0 || p->rr_k > p->L || p->rr_Q_total < p->rr_q0 + p->Q) { bang_set_error("distance = 1: bad k / result rows"); return BANG_ERR_ARG; }
+  if (p->rr_vec_f16 > 1u) { bang_set_error("distance = 1: rr_vec_f16 = %u (0 = float / 8-bit rows, 1 = fp16 rows)", p->rr_vec_f16); return BANG_ERR_ARG; }
+  if (p->rr_vec_f16 == 1u) {
+    // fp16 rows in the vector table: the pulled-rows form, float queries, the one layout family that has an instance
+    if (p->row_layout != 1u) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs row_layout = 1 (graph entries in HBM hold float vectors)"); return BANG_ERR_ARG; }
+    if (p->rr_dtype != BANG_F32) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs rr_dtype = BANG_F32 (rr_dtype = %u)", p->rr_dtype); return BANG_ERR_ARG; }
+    if (p->rr_D == 0u || p->rr_D % 8u != 0u || p->rr_D > 256u) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs rr_D %% 8 == 0 and rr_D <= 256 (rr_D = %u)", p->rr_D); return BANG_ERR_ARG; }
+  }
   if (p->row_layout == 1u) {
     // the pulled-rows form: adjacency rows in d_graph (pinned host memory; 4-byte aligned), vectors at rr_vec_base + id * rr_vec_stride
     if (!p->d_graph || (((uintptr_t)p->d_graph) & 3u)) { bang_set_error("distance = 1, row_layout = 1: d_graph (the 256-byte adjacency rows) is null or not 4-byte aligned"); return BANG_ERR_ARG; }
     if (p->R > 64u) { bang_set_error("distance = 1, row_layout = 1: R = %u, a 256-byte row holds 64 ids", p->R); return BANG_ERR_ARG; }
     if (!p->rr_vec_base || (((uintptr_t)p->rr_vec_base) & 3u)) { bang_set_error("distance = 1, row_layout = 1: rr_vec_base (the vectors) is null or not 4-byte aligned"); return BANG_ERR_ARG; }
-    if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
+    if (p->rr_vec_f16 == 1u && ((p->rr_vec_stride & 3u) || p->rr_vec_stride < 2ull * p->rr_D)) {
+      bang_set_error("distance = 1, row_layout = 1, rr_vec_f16 = 1: rr_vec_stride = %llu is not divisible by 4 or does not hold rr_D = %u halves",
+                     (unsigned long long)p->rr_vec_stride, p->rr_D);
+      return BANG_ERR_ARG;
+    }
+    if (p->rr_vec_f16 != 1u && !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
       bang_set_error("distance = 1, row_layout = 1: rr_vec_stride = %llu does not describe vectors the kernel evaluates (dtype %u, D = %u): 8-bit vectors need "
                      "D %% 16 == 0, float vectors D %% 4 == 0; D <= %u; a stride divisible by 4 that holds the vector", (unsigned long long)p->rr_vec_stride,
                      p->rr_dtype, p->rr_D, BANG_EXACT_MAX_D);
@@ -685,6 +771,7 @@ extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
     if (p->n_slices > 1u && !p->d_row_slices) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs the slice table d_row_slices", p->n_slices); return BANG_ERR_ARG; }
     if (p->n_slices > 1u && p->slice_rows == 0u) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs slice_rows != 0", p->n_slices); return BANG_ERR_ARG; }
     if (p->n_rows_hbm != 0u && !p->d_rows_hbm) { bang_set_error("distance = 1, row_layout = 1: n_rows_hbm = %u needs d_rows_hbm", p->n_rows_hbm); return BANG_ERR_ARG; }
+    if (p->rr_vec_f16 == 1u) return bang_k_search_exact_pull_f16(p, stream);
     if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return bang_k_search_exact_pull(p, stream);
     return bang_k_search_exact_wide_pull(p, stream);
   }

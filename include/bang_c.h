@@ -206,6 +206,9 @@ typedef struct {
   uint64_t rows_from_own_hbm; /* ... from this GPU's own HBM copy / slice */
   uint64_t walker_rows;       /* host-paced search kernel: 1 = the walker threads read the 256-byte pull rows (option "walker"), not graph entries */
   uint64_t rerank_fused;      /* 1: K6 + K7 ran inside the search launch (the wave that finished a query re-ranked it), no re-rank launch followed */
+  uint64_t vectors_fp16;      /* host-graph mode: 1 = the vector table in HBM holds IEEE fp16 rows (option "vectors_fp16"): every exact distance is the usual
+                                 arithmetic applied to the vectors rounded to fp16 */
+  uint64_t vector_table_bytes; /* bytes of that table (N rows + 256 bytes of slack), 0 where the index keeps none */
 } bang_stats;
 int bang_get_stats(bang_engine_t* e, bang_stats* out);
 /* Per-query counters of the last bang_query_e (arrays of num_queries words; any pointer may be NULL): PQ distance evaluations,
@@ -408,6 +411,12 @@ typedef struct {
   uint64_t* rr_ids_out;                /* [rr_Q_total][k] */
   float* rr_dists_out;                 /* [k][rr_Q_total] (rank-major, :999) */
   uint32_t rr_dtype, rr_D, rr_k, rr_q0, rr_Q_total;
+  /* bang_k_search_exact's pulled-rows form only (row_layout = 1, rr_dtype = BANG_F32): 1 = rr_vec_base holds IEEE fp16 rows at rr_vec_stride (a float
+   * index loaded with option "vectors_fp16"); the query stays float.  rr_D % 8 == 0, rr_D <= 256.  Every other entry point ignores it.  (The newest
+   * member: it takes the four bytes of padding that lay between rr_Q_total and the pointer below -- no member moves and sizeof is what it was.
+   * bang_k_search_exact therefore READS bytes that used to be padding: a caller must zero the whole struct (memset) before filling it member by
+   * member; garbage there is BANG_ERR_ARG (a value > 1) or, worse, the fp16 reading of a float table (a value of 1).) */
+  uint32_t rr_vec_f16;
   /* bang_k_search_lut only (psz == 0): the per-query look-up tables of K1 (bang_k_lut_build), read-only for the launch; query q's table is
    * d_lut + q * m * 256.  The other entries ignore it.  (Appended last: the layout of every earlier member is unchanged.) */
   const float* d_lut;                  /* [Q][m][256] */
@@ -445,6 +454,23 @@ int bang_k_rerank(const void* d_vec_base, uint64_t vec_stride, const void* d_med
                   uint32_t cand_stride, uint32_t Q, uint32_t D, uint32_t k, uint32_t dim_adjust,
                   uint64_t* d_ids_out, float* d_dists_out, void* stream);
 
+/* FP16 VECTOR TABLE (engine option "vectors_fp16" = 1: a float index on the host placement keeps its HBM vector table as IEEE fp16, half the bytes;
+ * results are the usual arithmetic applied to the vectors rounded to fp16, bit for bit).
+ *
+ * bang_k_f32_to_f16: `rows` rows of D floats at d_src + r * src_stride -> rows of halves at d_dst + r * dst_stride (strides in bytes; both
+ * divisible by 4, src_stride >= 4 D, dst_stride >= align4(2 D); both pointers 4-byte aligned).  Round to nearest even, fp16 subnormals produced;
+ * for odd D the padding half behind a row is written as 0.  A FINITE source value that becomes +-inf (|x| >= 65520) is converted all the same and
+ * counted in *d_bad_count (a device word the caller zeroed; may be NULL) -- the engine fails the load on a non-zero count.  inf stays inf, NaN
+ * stays NaN. */
+int bang_k_f32_to_f16(const void* d_src, void* d_dst, uint64_t rows, uint32_t D, uint64_t src_stride, uint64_t dst_stride,
+                      uint32_t* d_bad_count, void* stream);
+/* bang_k_rerank's device-vector form (d_cand_row == NULL) for float queries on an fp16 table: candidate id's row is d_vec_base + id * vec_stride
+ * (vec_stride % 4 == 0, >= align4(2 D)); distance = the ascending chain diff = float(h[j]) - q[j], acc = fmaf(diff, diff, acc) over the D
+ * dimensions (the query MIPS-padded by dim_adjust as in bang_k_rerank); the same stable rank.  Any D. */
+int bang_k_rerank_f16(const void* d_vec_base, uint64_t vec_stride, const void* d_queries, const uint32_t* d_cand_ids,
+                      const uint32_t* d_cand_cnt, uint32_t cand_stride, uint32_t Q, uint32_t D, uint32_t k, uint32_t dim_adjust,
+                      uint64_t* d_ids_out, float* d_dists_out, void* stream);
+
 /* EXACT-DISTANCE search kernel (csrc/bang_search_exact.hip; engine option "distance" = 1; the reference's BANG_Exactdistance,
  * BANG_Exactdistance/parANN.cu:1139-1179, :1275): the loop of bang_k_search with every neighbour's distance the exact L2 against its full-precision
  * vector -- the first vec_bytes of its graph entry in d_graph (row_layout 0: graph in HBM; row_layout 1: below) -- and no re-rank: each query's results are the
@@ -474,6 +500,8 @@ int bang_k_search_exact(const bang_search_params* p, void* stream);
 int bang_search_exact_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 /* the same for a launch of the pulled-rows form (row_layout = 1): the register count read is that of the pulled instance */
 int bang_search_exact_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+/* ... and of the pulled-rows form on an fp16 vector table (rr_vec_f16 = 1; dtype must be BANG_F32): the register count of that instance */
+int bang_search_exact_pull_f16_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 
 /* BANG_INMEMORY SEMANTICS of the query-resident search kernel (csrc/bang_search.hip built as bang_search_inmem.o / bang_search_inmem_b.o; engine
  * option "semantics" = 1; the reference's BANG_Inmemory, BANG_Inmemory/parANN.cu:1287-1420): the loop of bang_k_search with the parent taken AFTER
