@@ -99,6 +99,10 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   // pull = 1 was asked for explicitly, the pulled-rows form: adjacency rows from pinned host memory / the HBM row copy / a peer's slice, vectors
   // from the packed table in HBM.  What it cannot run is refused: there is no PQ fallback
   e->search_exact = false;
+  if (e->beam > 1) {                                                                 // (a beam belongs to the exact-distance walk alone)
+    if (e->distance != 1) { bang_set_error("option beam = %d needs distance = 1 (exact): the PQ walks expand one parent per iteration", e->beam); return BANG_ERR_UNSUPPORTED; }
+    if (e->semantics == 1) { bang_set_error("option beam = %d is not available with semantics = 1 (inmemory): it belongs to distance = 1 (exact)", e->beam); return BANG_ERR_UNSUPPORTED; }
+  }
   if (e->distance == 1) {
     if (!dev_graph) {
       const char* missing = nullptr;
@@ -129,6 +133,15 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
                      "float vectors D %% 4 == 0; D <= %u; %s stride divisible by 4", e->dtype, e->D, dev_graph ? "entry" : "vector",
                      (unsigned long long)vec_stride, BANG_EXACT_MAX_D, dev_graph ? "an entry" : "a vector");
       return BANG_ERR_UNSUPPORTED;
+    }
+    // beam > 1: the beam form of that kernel (bang_search_beam.hip) -- the narrow layouts on float / 8-bit rows.  What it cannot run is refused:
+    // there is no fallback to one parent per iteration
+    if (e->beam > 1) {
+      if (e->vecs_f16 && !dev_graph) { bang_set_error("option beam = %d is not available with vectors_fp16 = 1: the beam kernel reads float / 8-bit rows", e->beam); return BANG_ERR_UNSUPPORTED; }
+      if (!bang_search_exact_beam_supported(e->dtype, e->D, vec_stride)) {
+        bang_set_error("option beam = %d: the wide vector layouts have no beam kernel (dtype %d, D = %u): 8-bit vectors need D / 16 a power of two, D <= 256", e->beam, e->dtype, e->D);
+        return BANG_ERR_UNSUPPORTED;
+      }
     }
     e->search_exact = true;
     e->search_v2 = false;

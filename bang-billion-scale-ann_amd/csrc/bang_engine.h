@@ -219,6 +219,7 @@ struct bang_engine {
   bool search_host = false;            // resolved at bang_alloc: graph in host RAM, the host-paced form of the same kernel (BAR mode)
   int distance = 0;                    // option "distance": 0 = PQ distances + re-rank (BANG_Base), 1 = exact distances, results from the worklist
   bool search_exact = false;           // resolved at bang_alloc: distance = 1 -- the exact-distance search kernel (bang_search_exact.hip)
+  int beam = 1;                        // option "beam": parents expanded per iteration of the exact-distance walk; 1 = not asked for (bang_search_exact.hip), 2..4 = bang_search_beam.hip
   int semantics = 0;                   // option "semantics": 0 = BANG_Base's walk (default), 1 = BANG_Inmemory's (parent after the merge, cap L + 119)
   bool search_inmem = false;           // resolved at bang_alloc: semantics = 1 -- search_v2 on bang_k_search_inmem; candidate log L + 120
   bool search_lut = false;             // resolved at bang_alloc: LUT path (psz == 0), graph in HBM, search = 1 given explicitly -- K1, then ONE launch of

@@ -72,6 +72,9 @@ int bang_search_exact_wide_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint
 // the pulled-rows instance on an fp16 vector table (rr_vec_f16 = 1; the same source built with BANG_EXACT_PULL and BANG_EXACT_F16 as
 // bang_search_exact_pull_f16.o), handed bang_k_search_exact's checked arguments
 int bang_k_search_exact_pull_f16(const bang_search_params* p, void* stream);
+// the pulled-rows instances of the beam form (bang_search_beam.hip built with BANG_EXACT_PULL as bang_search_beam_pull.o), handed
+// bang_k_search_exact_beam's checked arguments
+int bang_k_search_exact_beam_pull(const bang_search_params* p, uint32_t beam, void* stream);
 
 #ifdef __cplusplus
 }

@@ -199,7 +199,8 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     sp.max_waves = (uint32_t)std::max(0L, env_long("BANG_SEARCH_MAX_WAVES", 0));
     e->rerank_fused = false;
     ENQ_BEGIN();
-    BANG_TRY(bang_k_search_exact(&sp, ln.s_main));
+    if (e->beam > 1) BANG_TRY(bang_k_search_exact_beam(&sp, (uint32_t)e->beam, ln.s_main));   // up to beam parents per iteration (bang_search_beam.hip)
+    else BANG_TRY(bang_k_search_exact(&sp, ln.s_main));
     ENQ_END();
     ++ln.front_launches;
     iter = cap_iter;                                                         // refined from the per-query counts below

@@ -63,6 +63,10 @@ static const OptionDef kOptions[] = {
      "HBM and walker != 1: the pulled-rows form, adjacency rows read by the kernel from pinned host memory, the HBM row copy or a peer's slice -- and "
      "search != 0, persistent != 0, L2 distance and a vector layout of bang_search_exact_supported: 8-bit D % 16 == 0, float D % 4 == 0, D <= 1024 "
      "(environment: pq | exact)"},
+    {"beam", "BANG_BEAM", &bang_engine::beam, 1, 4, INT, BEFORE_ALLOC,
+     "distance = 1 only: parents expanded per iteration.  1 = one, today's walk (default).  2..4: the rows of up to beam parents are filtered against the "
+     "filter state at the iteration's entry, ids that survive in two rows are kept once, the rows are merged one by one, then the first beam unvisited "
+     "worklist entries are expanded together.  Refused: distance = 0, semantics = 1, vectors_fp16 = 1 and the wide layouts (D > 256, 8-bit D / 16 not a power of two)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

@@ -503,6 +503,25 @@ int bang_search_exact_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t 
 /* ... and of the pulled-rows form on an fp16 vector table (rr_vec_f16 = 1; dtype must be BANG_F32): the register count of that instance */
 int bang_search_exact_pull_f16_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 
+/* BEAM form of the exact-distance search kernel (csrc/bang_search_beam.hip; engine options "distance" = 1 and "beam" = W, 2 <= W <= 4): up to beam
+ * parents are expanded per iteration.  Every id of the <= beam adjacency rows of an iteration is tested against the filter state at the
+ * iteration's entry, then the survivors' bits are set; a survivor whose id also survived in an earlier row of the iteration is dropped; the rows
+ * are sorted and merged one after the other with no mark; then the first P = min(beam, room in the candidate log, unvisited entries) unvisited
+ * worklist entries are marked visited, logged in d_cand_ids and expanded together.  P == 0 ends the query; at iteration cap_iter the parents are
+ * logged, not expanded.  Results as bang_k_search_exact: the first min(k, worklist length) worklist entries.  beam = 1 is the post-merge-parent walk
+ * with exact distances (NOT the walk of bang_k_search_exact); the engine never launches it.
+ * Arguments and their checks are those of bang_k_search_exact in both forms (row_layout 0: graph entries in HBM; 1: pulled rows), all made before
+ * any HIP call; beam travels as an argument -- bang_search_params is what it was.  Refused, with a message naming beam: beam == 0 or beam > 4
+ * (BANG_ERR_ARG); rr_vec_f16 = 1 and the wide layouts, i.e. those bang_search_exact_beam_supported refuses (BANG_ERR_UNSUPPORTED). */
+int bang_k_search_exact_beam(const bang_search_params* p, uint32_t beam, void* stream);
+/* 1 if the beam form evaluates vectors of this layout: bang_search_exact_supported and bang_search_can_rerank (8-bit: D % 16 == 0, D / 16 a power
+ * of two; float: D % 4 == 0; D <= 256; a stride divisible by 4 that holds the vector) */
+int bang_search_exact_beam_supported(int dtype, uint32_t D, uint64_t stride);
+/* grid of a bang_k_search_exact_beam launch, as bang_search_exact_geometry; LDS per wave is 2L + L/4 + 144 + 2 (64 beam + 4) words */
+int bang_search_exact_beam_geometry(int dtype, uint32_t L, uint32_t beam, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+/* the same for the pulled-rows form (row_layout = 1) */
+int bang_search_exact_beam_pull_geometry(int dtype, uint32_t L, uint32_t beam, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+
 /* BANG_INMEMORY SEMANTICS of the query-resident search kernel (csrc/bang_search.hip built as bang_search_inmem.o / bang_search_inmem_b.o; engine
  * option "semantics" = 1; the reference's BANG_Inmemory, BANG_Inmemory/parANN.cu:1287-1420): the loop of bang_k_search with the parent taken AFTER
  * the merge -- the first unvisited worklist entry, marked visited -- and an iteration cap of L + 119 (cap_iter <= L + BANG_INMEM_EXTRA_ITERS - 1; the
