@@ -7,5 +7,5 @@ There is no Python or CPU fallback: every compute call needs libbang.so and a HI
 from .binding import (  # noqa: F401
     BangError, Engine, DeviceBuffer, IterState, lib, lib_path, build, device_count,
     U8, I8, F32, DIST_L2, DIST_MIPS, GRAPH_HOST, GRAPH_DEVICE, GRAPH_AUTO, DISTANCE_PQ, DISTANCE_EXACT,
-    SEMANTICS_BASE, SEMANTICS_INMEMORY, DTYPE_CODE,
+    SEMANTICS_BASE, SEMANTICS_INMEMORY, FILTER_SPLIT, FILTER_WORD, DTYPE_CODE,
 )

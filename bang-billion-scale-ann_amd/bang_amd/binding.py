@@ -15,6 +15,7 @@ DIST_L2, DIST_MIPS = 0, 1
 GRAPH_HOST, GRAPH_DEVICE, GRAPH_AUTO = 0, 1, 2
 DISTANCE_PQ, DISTANCE_EXACT = 0, 1       # option "distance": PQ distances + re-rank / exact distances, results from the worklist
 SEMANTICS_BASE, SEMANTICS_INMEMORY = 0, 1   # option "semantics": the walk of BANG_Base / of BANG_Inmemory (parent after the merge, cap L + 119)
+FILTER_SPLIT, FILTER_WORD = 0, 1            # option "filter_layout": an id's two filter bits in two unrelated words / both in the word of hash1
 DTYPE_CODE = {"uint8": U8, "int8": I8, "float": F32}
 NP_DTYPE = {"uint8": np.uint8, "int8": np.int8, "float": np.float32}
 
@@ -85,6 +86,11 @@ class Stats(C.Structure):
                 ("search_kernel", C.c_uint64), ("pacing_groups", C.c_uint64), ("graph_pull", C.c_uint64), ("pulled_bytes", C.c_uint64),
                 ("rows_in_hbm", C.c_uint64), ("code_stride", C.c_uint64), ("filter_loads_skipped", C.c_uint64), ("rows_from_peer", C.c_uint64), ("rows_from_own_hbm", C.c_uint64), ("walker_rows", C.c_uint64), ("rerank_fused", C.c_uint64),
                 ("vectors_fp16", C.c_uint64), ("vector_table_bytes", C.c_uint64)]
+
+
+class StatsExt(C.Structure):
+    """bang_stats_ext: bang_stats with the later options' fields behind it (bang_get_stats_ext)."""
+    _fields_ = Stats._fields_ + [("filter_layout", C.c_uint64)]
 
 
 ENTRY_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)     # bang_entry_source
@@ -318,9 +324,9 @@ class Engine:
         _check(fn(self._h, _vp(q), q.shape[0], C.c_void_p(d_ids), C.c_void_p(d_dists) if d_dists else None), "bang_query_dev")
 
     def stats(self) -> dict:
-        s = Stats()
-        _check(lib().bang_get_stats(self._h, C.byref(s)), "bang_get_stats")
-        return {f: getattr(s, f) for f, _ in Stats._fields_}
+        s = StatsExt()
+        _check(lib().bang_get_stats_ext(self._h, C.byref(s)), "bang_get_stats_ext")
+        return {f: getattr(s, f) for f, _ in StatsExt._fields_}
 
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the
@@ -507,7 +513,7 @@ class IterState:
         _check(getattr(lib(), "bang_k_" + entry)(C.byref(p), None), "bang_k_" + entry)
         sync()
 
-    def run_search(self):
+    def run_search(self, entry: str = "bang_k_search"):
         """The whole search loop in ONE launch of the query-resident search kernel (graph resident in HBM: needs
         device_graph=True).  Fills the candidate log; returns the per-query iteration counts."""
         assert self.d_graph is not None and self.psz != 0
@@ -522,9 +528,15 @@ class IterState:
         d_iters = DeviceBuffer(self.Q * 4)
         d_next = DeviceBuffer(64)
         sp.d_qiters, sp.d_next_query = d_iters.ptr, d_next.ptr
-        _check(lib().bang_k_search(C.byref(sp), None), "bang_k_search")
+        if entry != "bang_k_search":
+            sp.n_nodes, sp.d_abort = ix.N, d_next.ptr + 4       # (an adjacency id >= N ends the batch instead of being followed)
+        _check(getattr(lib(), entry)(C.byref(sp), None), entry)
         sync()
         return d_iters.download(np.uint32, (self.Q,))
+
+    def run_search_wf(self):
+        """The same with the word-local visited filter (option filter_layout = 1): ONE launch of bang_k_search_wf."""
+        return self.run_search("bang_k_search_wf")
 
     def run_search_lut(self):
         """The same on the LUT path (use_lut=True, device_graph=True): ONE launch of bang_k_search_lut behind K1.  Fills the candidate log;

@@ -95,6 +95,34 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       e->pq_nhi = (w_rag > w_pad) ? e->pq_nhi_avail : 0;
     }
   }
+  // filter_layout = 1: the word-local visited filter on the self-paced search kernel (bang_k_search_wf).  Every configuration that does not end
+  // on that kernel is refused: there is no fallback to the split layout
+  e->search_wordfilter = false;
+  if (e->filter_layout == 1) {
+    if (e->search_opt == 0 || e->persistent == 0) {
+      bang_set_error("option filter_layout = 1 (word) runs on the query-resident search kernel only (search = %d, persistent = %d)", e->search_opt, e->persistent);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (e->distance != 0) { bang_set_error("option filter_layout = 1 (word) is not available with distance = 1 (exact)"); return BANG_ERR_UNSUPPORTED; }
+    if (e->beam > 1) { bang_set_error("option filter_layout = 1 (word) is not available with beam = %d", e->beam); return BANG_ERR_UNSUPPORTED; }
+    if (e->semantics == 1) { bang_set_error("option filter_layout = 1 (word) is not available with semantics = 1 (inmemory)"); return BANG_ERR_UNSUPPORTED; }
+    if (e->psz == 0) { bang_set_error("option filter_layout = 1 (word) needs the LDS-resident pivot table (the LUT path, pq = 1, has no such kernel)"); return BANG_ERR_UNSUPPORTED; }
+    if (walk_rows_want) { bang_set_error("option filter_layout = 1 (word) is not available with walker = 1: the host-paced search kernel keeps the split layout"); return BANG_ERR_UNSUPPORTED; }
+    if (!dev_graph && !e->pull) {
+      bang_set_error("option filter_layout = 1 (word) needs graph = device or, with graph = host, the kernel-pulled rows (pull): the host-paced and "
+                     "walker forms keep the split layout");
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (!bang_search_wf_has_instance(e->psz, e->mp, e->code_stride ? e->code_stride : e->m)) {
+      bang_set_error("option filter_layout = 1 (word): no kernel instance for the pivot layout psz = %u, mp = %u", e->psz, e->mp);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    if (!e->search_v2) {
+      bang_set_error("option filter_layout = 1 (word): the pivot table and %s worklist do not fit LDS at L = %d", e->search_opt == 1 ? "one wave's" : "four waves'", e->L);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    e->search_wordfilter = true;
+  }
   // distance = 1: the exact-distance search kernel (bang_search_exact.hip) -- self-paced, one launch per batch; graph entries in HBM, or, where
   // pull = 1 was asked for explicitly, the pulled-rows form: adjacency rows from pinned host memory / the HBM row copy / a peer's slice, vectors
   // from the packed table in HBM.  What it cannot run is refused: there is no PQ fallback
@@ -344,8 +372,8 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     else if (!dev_graph) fprintf(stderr, "[bang] walker threads not pinned\n");
   }
   if (env_flag("BANG_DEBUG"))
-    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d/%d semantics=%d fp_direct=%d vec_on_device=%d\n", Q, nl,
-            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->search_lut, (int)e->search_inmem, (int)e->fp_direct, (int)e->vec_on_device);
+    fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d/%d semantics=%d filter_layout=%d fp_direct=%d vec_on_device=%d\n", Q, nl,
+            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->search_lut, (int)e->search_inmem, (int)e->search_wordfilter, (int)e->fp_direct, (int)e->vec_on_device);
   start_threads(e);
   return BANG_OK;
 }

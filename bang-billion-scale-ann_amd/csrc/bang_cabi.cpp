@@ -295,6 +295,7 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   s.vectors_fp16 = e->vecs_f16 ? 1 : 0;
   s.vector_table_bytes = (e->vec_on_device && e->d_vecs) ? (uint64_t)e->N * vec_table_stride(e) + 256 : 0;
   s.walker_rows = (e->search_host && e->walker_rows) ? 1 : 0;
+  e->stat_filter_layout = e->search_wordfilter ? 1 : 0;          // (reported behind bang_stats: bang_get_stats_ext)
   s.code_stride = e->code_stride;
   // what the kernel was GIVEN (bang_lane.cpp): without a slice table a slice moved off row 0 (bang_rows_slice_e(first > 0)) is not reachable
   const uint32_t rows_direct = (e->rows_first == 0 ? e->n_rows_hbm : 0);
@@ -385,6 +386,13 @@ extern "C" int bang_get_stats(bang_engine_t* e, bang_stats* out) {
     }
   }
   *out = s;
+  return BANG_OK;
+}
+
+extern "C" int bang_get_stats_ext(bang_engine_t* e, bang_stats_ext* out) {
+  if (!e || !out) return BANG_ERR_ARG;
+  BANG_TRY(bang_get_stats(e, &out->base));
+  out->filter_layout = e->stat_filter_layout;
   return BANG_OK;
 }
 

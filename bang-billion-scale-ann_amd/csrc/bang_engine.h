@@ -222,6 +222,8 @@ struct bang_engine {
   int beam = 1;                        // option "beam": parents expanded per iteration of the exact-distance walk; 1 = not asked for (bang_search_exact.hip), 2..4 = bang_search_beam.hip
   int semantics = 0;                   // option "semantics": 0 = BANG_Base's walk (default), 1 = BANG_Inmemory's (parent after the merge, cap L + 119)
   bool search_inmem = false;           // resolved at bang_alloc: semantics = 1 -- search_v2 on bang_k_search_inmem; candidate log L + 120
+  int filter_layout = 0;               // option "filter_layout": 0 = split (an id's two filter bits in two unrelated words, default), 1 = word (both in the word of hash1)
+  bool search_wordfilter = false;      // resolved at bang_alloc: filter_layout = 1 -- search_v2 on bang_k_search_wf
   bool search_lut = false;             // resolved at bang_alloc: LUT path (psz == 0), graph in HBM, search = 1 given explicitly -- K1, then ONE launch of
                                        // the LUT-path search kernel (bang_search_lut.hip), then the re-rank launch
   uint32_t sv_G = 0, sv_W = 0, sv_C = 1;   // its grid for the running query: workgroups, waves per workgroup, query contexts per wave
@@ -292,6 +294,7 @@ struct bang_engine {
   int kernel_go_timeout_ms = 30000;
   int walker_stall_ms = 0;             // test hook: the walker team sleeps this long at the start of the next host-paced query (one shot)
   bang_stats stats{};
+  uint64_t stat_filter_layout = 0;     // bang_stats_ext.filter_layout of the last bang_query
 };
 
 // bang_search.hip, part 2 (semantics = 1): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride

@@ -266,7 +266,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     const uint32_t Gd = (uint32_t)std::min<int>((int)ln.nq, bang_num_cus());
     if (kprof_d) { LANE_HIP(hipMalloc((void**)&d_prof, (size_t)Gd * 128)); LANE_HIP(hipMemsetAsync(d_prof, 0, (size_t)Gd * 128, ln.s_main)); sp.d_prof = d_prof; }
     ENQ_BEGIN();
-    BANG_TRY(e->search_inmem ? bang_k_search_inmem(&sp, ln.s_main) : bang_k_search(&sp, ln.s_main));
+    BANG_TRY(e->search_inmem ? bang_k_search_inmem(&sp, ln.s_main) : e->search_wordfilter ? bang_k_search_wf(&sp, ln.s_main) : bang_k_search(&sp, ln.s_main));
     ENQ_END();
     ++ln.front_launches;
     if (d_prof) {

@@ -71,6 +71,11 @@ static const OptionDef kOptions[] = {
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "
      "(pq = 0), L2 distance and distance = 0 (environment: base | inmemory)"},
+    {"filter_layout", "BANG_FILTER_LAYOUT", &bang_engine::filter_layout, 0, 1, INT, BEFORE_ALLOC,
+     "visited filter of the self-paced search kernel: 0 = split (default): an id's two bits at hash1(x) and hash2(x), two words; 1 = word: both bits in the "
+     "word of hash1(x) -- bit hash1(x) & 31 and bit (hash2(x) >> 5) & 31 -- one probe and one store per id, more false drops (bang_k_search_wf).  1 needs "
+     "graph = device or pulled rows, search != 0, persistent != 0, the LDS pivot table (pq = 0), walker = 0, distance = 0, beam = 1, semantics = 0; "
+     "anything else is refused (environment: split | word)"},
     {"stage_zero_copy", "BANG_STAGE_ZC", &bang_engine::stage_zero_copy, -1, 2, INT, BEFORE_ALLOC,
      "walker forms, where staged adjacency rows travel: 0 = H2D copy per iteration, 1 = kernels read mapped pinned memory, 2 = CPU stores through the PCIe BAR, -1 = auto"},
     {"numa", "BANG_NUMA", &bang_engine::numa_opt, -1, 1, INT, BEFORE_ALLOC, "1 = pin walker threads to the GPU's NUMA node, one physical core each; 0 / -1 = leave them to the scheduler"},
@@ -156,6 +161,8 @@ void apply_env_defaults(bang_engine* e) {
       x = strcmp(v, "exact") == 0 ? 1 : 0;
     else if (o.field == &bang_engine::semantics && !isdigit((unsigned char)*v) && *v != '-')
       x = strcmp(v, "inmemory") == 0 ? 1 : 0;
+    else if (o.field == &bang_engine::filter_layout && !isdigit((unsigned char)*v) && *v != '-')
+      x = strcmp(v, "word") == 0 ? 1 : 0;
     else
       x = atol(v);
     store(e, o, std::min(o.hi, std::max(o.lo, x)));

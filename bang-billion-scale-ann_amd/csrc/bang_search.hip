@@ -60,6 +60,18 @@
 #define BANG_SEARCH_INMEM 0
 #endif
 #define BANG_INMEM_NO_MARK 0xFFFFFFFFu   // semantics = 1 merges with a mark no id equals: the reference variant has no d_mark step
+// BANG_SEARCH_WORDFILTER (Makefile: bang_search_wf.o / bang_search_wf_b.o, BANG_SEARCH_PART 4 / 5): the same kernel once more (search_wf_kernel),
+// self-paced instances only, with the WORD-LOCAL visited filter (option filter_layout = 1): both bits of an id live
+// in the word of hash1(x) -- bit hash1(x) & 31 and bit (hash2(x) >> 5) & 31 -- so an id costs one probe, one summary test, one claim-table item
+// and one store.  Everything that differs sits under #if BANG_SEARCH_WORDFILTER: the other parts compile what they compiled before.
+#ifndef BANG_SEARCH_WORDFILTER
+#define BANG_SEARCH_WORDFILTER 0
+#endif
+#if BANG_SEARCH_WORDFILTER && BANG_SEARCH_INMEM
+#error "the word-local filter is built for the BANG_Base walk only"
+#endif
+// the bits of id x in filter word hash1(x) >> 5 (one bit where the two positions coincide, about 1 id in 32)
+__device__ __forceinline__ uint32_t wf_mask(uint32_t ha, uint32_t hb) { return (1u << (ha & 31u)) | (1u << ((hb >> 5) & 31u)); }
 
 struct SearchArgs;
 // A kernel-argument field read WHERE IT IS USED (a scalar load from the kernarg segment through a pointer the optimiser cannot see through),
@@ -315,6 +327,8 @@ __host__ __device__ constexpr uint32_t search_scratch_words(int ndw, bool host_p
 
 #if BANG_SEARCH_INMEM
 #define search_kernel search_inmem_kernel          // (its own symbols: the instances of parts 0 and 1 keep their names)
+#elif BANG_SEARCH_WORDFILTER
+#define search_kernel search_wf_kernel
 #endif
 template <int PSZ, int NDW, bool ALIGNED, int NHI, bool HOST, bool SPEC>
 __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const SearchArgs a) {
@@ -390,6 +404,9 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
   static_assert(!HOST && !SPEC, "semantics = 1: self-paced instances without the speculative row request");
 #else
   const uint32_t cand_stride = L + BANG_EXTRA_ITERS;
+#endif
+#if BANG_SEARCH_WORDFILTER
+  static_assert(!HOST, "filter_layout = 1: self-paced instances only");
 #endif
   constexpr int SB = (NDW >= 18) ? 6 : 0;          // long rows (70 .. 128 chunks): consumed 6 code dwords (24 chunks) at a time
   constexpr bool EARLY_ROWS = !HOST;                           // code rows requested before the filter update (host-paced instances: behind it --
@@ -592,6 +609,22 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
       // A word the summary knows to be untouched is zero: no request (FilterSummary).
       bool la = v0, lb = v0;                                 // load word a / b?
       const bool summ_on = SUMM && (HOST || iter <= IA32(IA_SUMM_ITERS));     // (uniform; one-way per query: once off, the registers go stale.  bang_k_search resolves 0 = auto)
+#if BANG_SEARCH_WORDFILTER
+      // word-local layout: ONE word per id (that of hash1), its one or two bits in bm0 / bm1; the b side of everything below is gone
+      const uint32_t bm0 = wf_mask(h0a, h0b);
+      uint32_t bm1 = 0;
+      lb = false;
+      if (SUMM && summ_on) {
+        la = summ.test(h0a >> 5) && v0;
+        probes_skipped += (uint32_t)__popcll(__ballot(v0 && !la));
+      }
+      if (la) w0a = ld_bypass_l1(&bloom[h0a >> 5]);
+      if (v1) {
+        h1a = hash1(x1); h1b = hash2(x1);
+        bm1 = wf_mask(h1a, h1b);
+        if (lane == 0) w1a = ld_bypass_l1(&bloom[h1a >> 5]);
+      }
+#else
       if (SUMM && summ_on) {
         la = summ.test(h0a >> 5) && v0;
         lb = summ.test(h0b >> 5) && v0;
@@ -603,6 +636,7 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
         h1a = hash1(x1); h1b = hash2(x1);
         if (lane == 0) { w1a = ld_bypass_l1(&bloom[h1a >> 5]); w1b = ld_bypass_l1(&bloom[h1b >> 5]); }
       }
+#endif
       PqRow<NDW, ALIGNED> row;
       CoopFetch<NDW, ALIGNED> cf;
       const uint8_t GAS* d_codes = IAPTR(const uint8_t, IA_CODES);
@@ -615,8 +649,15 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
       // was enough: 1 250-query shard 1.51 -> 1.63 ms, ISA checked).  A compiler-level memory barrier: loads do not move across it.
       if (SPEC) asm volatile("" ::: "memory");
       if (prio) __builtin_amdgcn_s_setprio(0);
+#if BANG_SEARCH_WORDFILTER
+      // dropped iff ALL bits of the id's mask are set in the word as it stood at the iteration's entry
+      const bool pass0 = v0 && (w0a & bm0) != bm0;
+      const bool pass1 = v1 && (lane == 0) && (w1a & bm1) != bm1;
+      (void)w0b; (void)w1b; (void)lb;
+#else
       const bool pass0 = v0 && !(((w0a >> (h0a & 31)) & 1u) && ((w0b >> (h0b & 31)) & 1u));
       const bool pass1 = v1 && (lane == 0) && !(((w1a >> (h1a & 31)) & 1u) && ((w1b >> (h1b & 31)) & 1u));
+#endif
       const uint64_t m0 = __ballot(pass0);
       const uint64_t m1 = __ballot(pass1);
       const uint32_t n0 = (uint32_t)__popcll(m0);
@@ -641,6 +682,26 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
       // ---------------- K5, second half: set the slots of the survivors (:1159-1160) ----------------
       // (before the distance arithmetic: the hashes and the probed words die here instead of living through the register-hungry K2)
       // The claim rounds run now, on LDS, while the code rows travel; the stores they decide on are issued once the rows are here.
+#if BANG_SEARCH_WORDFILTER
+      // one claim-table item per lane: the survivor's word with its one- or two-bit mask (lanes of one word merge their masks as ever)
+      bool pa = pass0, pb = false, st_a = false, st_b = false;
+      uint32_t sv_a = 0, sv_b = 0;
+      filter_commit<SCR >= 256 ? 256 : 128>(tbl, lane, pa, h0a >> 5, bm0, w0a, pb, 0u, 0u, 0u, st_a, sv_a, st_b, sv_b);
+      if (SUMM && summ_on) {
+        if (SET_LATE && !first) { sl_a = pass0 && !la; sl_ua = h0a >> 5; }
+        else summ.template set<SCR >= 256 ? 4 : 2>(tbl, lane, pass0 && !la, h0a >> 5, false, 0u, pass1, h1a >> 5, h1a >> 5);
+      }
+      auto filter_stores = [&]() {
+        asm volatile("" ::: "memory");
+        if (st_a) bloom[h0a >> 5] = sv_a;
+        const uint64_t left = __ballot(pa || pass1);
+        if (left) {                                            // rare: lost three claim rounds; or the 65th id of the seed list
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // behind the plain stores (which were computed from the old words)
+          if (pa) (void)__hip_atomic_fetch_or(&bloom[h0a >> 5], bm0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (pass1) (void)__hip_atomic_fetch_or(&bloom[h1a >> 5], bm1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      };
+#else
       bool pa = pass0, pb = pass0, st_a = false, st_b = false;
       uint32_t sv_a = 0, sv_b = 0;
       filter_commit<SCR >= 256 ? 256 : 128>(tbl, lane, pa, h0a >> 5, 1u << (h0a & 31), w0a, pb, h0b >> 5, 1u << (h0b & 31), w0b, st_a, sv_a, st_b, sv_b);
@@ -664,6 +725,7 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
           }
         }
       };
+#endif
       if (!EARLY_ROWS) filter_stores();
 
       PH(3);   // filter update (claim table + stores issued)
@@ -996,6 +1058,10 @@ constexpr bool search_in_part1(int ndw, bool aligned, bool host_paced) { return 
 // parts 0 and 1 do
 #define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 3)
 #define bang_search_launch_part1 bang_search_inmem_launch_part3
+#elif BANG_SEARCH_WORDFILTER
+// filter_layout = 1: parts 4 (bang_search_wf.o, iterative-ILP) and 5 (bang_search_wf_b.o, the default scheduler), split the same way
+#define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 5)
+#define bang_search_launch_part1 bang_search_wf_launch_part5
 #else
 #define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 1)
 #endif
@@ -1016,6 +1082,11 @@ template <int PSZ, int NDW, bool ALIGNED, int NHI>
 static int launch_hd(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
 #if BANG_SEARCH_INMEM
   return launch_part<PSZ, NDW, ALIGNED, NHI, false, false>(a, grid, block, lds, st);     // (self-paced, no speculative row request)
+#elif BANG_SEARCH_WORDFILTER
+  if constexpr (search_has_spec(NDW)) {                                                  // (self-paced, both SPEC forms)
+    if (a.p.spec_rows == 1u) return launch_part<PSZ, NDW, ALIGNED, NHI, false, true>(a, grid, block, lds, st);
+  }
+  return launch_part<PSZ, NDW, ALIGNED, NHI, false, false>(a, grid, block, lds, st);
 #else
   if constexpr (search_has_spec(NDW)) {
     if (a.p.d_graph && a.p.spec_rows == 1u) return launch_part<PSZ, NDW, ALIGNED, NHI, false, true>(a, grid, block, lds, st);
@@ -1166,6 +1237,37 @@ extern "C" int bang_k_search_inmem(const bang_search_params* p, void* stream) {
   if (rc != BANG_OK) return rc;
   // the fused re-rank works in the wave's LDS region: its n <= L + 120 candidate words fit (2L + L/4 + 144 words)
   static_assert(BANG_INMEM_EXTRA_ITERS <= 144, "the fused re-rank's candidates fit the wave's LDS region");
+  return search_dispatch(a, grid, block, lds, (hipStream_t)stream);
+}
+
+#elif BANG_SEARCH_WORDFILTER
+
+// filter_layout = 1: the grid is that of the self-paced form of bang_k_search (the filter memory and the LDS per wave are what they were)
+extern "C" int bang_search_wf_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
+                                       uint32_t* workgroups, uint32_t* waves) {
+  uint32_t nctx = 1, gs = 0;
+  return bang_search_geometry(psz, mp, nhi, L, Q, max_wgs, max_waves, 0, workgroups, waves, &nctx, &gs);
+}
+
+// does a search_wf_kernel instance exist for this pivot layout and code-row stride?  (every layout of search_dispatch, in both row alignments)
+extern "C" int bang_search_wf_has_instance(uint32_t psz, uint32_t mp, uint32_t code_stride) {
+  (void)code_stride;
+  if (psz == 0 || (mp & 3u)) return 0;
+  switch (psz * 100u + mp / 4u) {
+    case 108: case 116: case 124: case 132: case 208: case 216: case 218: case 219: case 404: case 408: case 802: case 804: return 1;
+    default: return 0;
+  }
+}
+
+extern "C" int bang_k_search_wf(const bang_search_params* p, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (p->Q == 0) return BANG_OK;
+  if (!p->d_graph) { bang_set_error("filter_layout = 1: the word-local filter belongs to the self-paced form (d_graph: graph entries or pulled rows)"); return BANG_ERR_UNSUPPORTED; }
+  SearchArgs a;
+  dim3 grid, block;
+  size_t lds = 0;
+  const int rc = search_setup(p, false, &a, &grid, &block, &lds);
+  if (rc != BANG_OK) return rc;
   return search_dispatch(a, grid, block, lds, (hipStream_t)stream);
 }
 

@@ -211,6 +211,14 @@ typedef struct {
   uint64_t vector_table_bytes; /* bytes of that table (N rows + 256 bytes of slack), 0 where the index keeps none */
 } bang_stats;
 int bang_get_stats(bang_engine_t* e, bang_stats* out);
+/* bang_stats with what later options report appended BEHIND it: bang_stats itself keeps its size and offsets, so callers built against it are
+ * not disturbed.  The first sizeof(bang_stats) bytes are what bang_get_stats fills. */
+typedef struct {
+  bang_stats base;
+  uint64_t filter_layout;     /* layout of the visited filter the batch ran on (option "filter_layout"): 0 = split, 1 = word (bang_k_search_wf; then
+                                 base.filter_loads_skipped counts of 1 x `fetched` probes) */
+} bang_stats_ext;
+int bang_get_stats_ext(bang_engine_t* e, bang_stats_ext* out);
 /* Per-query counters of the last bang_query_e (arrays of num_queries words; any pointer may be NULL): PQ distance evaluations,
  * adjacency ids offered to the filter, expanded nodes (candidate-log length) and -- search kernel only, else zeros -- the number
  * of iterations the query ran.  Test hook: the oracle reports the same four numbers per query. */
@@ -531,6 +539,20 @@ int bang_k_search_inmem(const bang_search_params* p, void* stream);
 /* grid of a bang_k_search_inmem launch: that of bang_search_geometry's self-paced form (host_paced = 0) */
 int bang_search_inmem_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
                                uint32_t* workgroups, uint32_t* waves);
+
+/* WORD-LOCAL VISITED FILTER of the query-resident search kernel (csrc/bang_search.hip built as bang_search_wf.o / bang_search_wf_b.o; engine option
+ * "filter_layout" = 1): the loop of bang_k_search, self-paced form only (d_graph != NULL: graph entries in HBM, or
+ * row_layout = 1 with the pulled rows, their HBM copy and peer slices), with both filter bits of an id x in ONE word of the query's filter: word
+ * hash1(x) >> 5, bits hash1(x) & 31 and (hash2(x) >> 5) & 31 (one bit where they coincide).  An id is dropped iff all bits of its mask are set in
+ * the word as it stood at the iteration's entry; a survivor sets its mask.  The filter memory (BANG_BF_WORDS words per query, zeroed by the
+ * caller) and bang_search_params are what they are for bang_k_search; spec_rows, summ_iters, the fused re-rank and the counters work as there.
+ * Results differ from bang_k_search's only where the two layouts drop different ids. */
+int bang_k_search_wf(const bang_search_params* p, void* stream);
+/* grid of a bang_k_search_wf launch: that of bang_search_geometry's self-paced form (host_paced = 0) */
+int bang_search_wf_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
+                            uint32_t* workgroups, uint32_t* waves);
+/* 1 if a search_wf_kernel instance exists for this pivot layout and code-row stride (every layout bang_k_search dispatches, rows dword-aligned or not) */
+int bang_search_wf_has_instance(uint32_t psz, uint32_t mp, uint32_t code_stride);
 
 /* LUT-PATH search kernel (csrc/bang_search_lut.hip; engine option "search" = 1 on an index with psz == 0: chunks wider than 8 dimensions, a pivot
  * table too large for LDS, or option "pq" = 1): the loop of bang_k_search's self-paced form -- one wave per query from its first iteration to its
