@@ -206,6 +206,23 @@ def sync():
     _check(lib().bang_dev_sync(), "bang_dev_sync")
 
 
+def upload_rows(buf: DeviceBuffer, table: np.ndarray, offset: int, stride: int):
+    """Row i of a [N][row] table to byte offset + i * stride of a device buffer, one copy per row: a table at a stride of the caller's
+    (every kernel-level entry takes its strides as arguments)."""
+    t = np.ascontiguousarray(table)
+    rows = t.reshape(t.shape[0], -1).view(np.uint8)
+    assert stride >= rows.shape[1]
+    for i in range(rows.shape[0]):
+        buf.upload(rows[i], offset + i * stride)
+
+
+class _Borrowed:
+    """A device address of the caller's where IterState would hold a DeviceBuffer of its own (never freed here)."""
+
+    def __init__(self, ptr: int):
+        self.ptr = int(ptr)
+
+
 class Engine:
     """Engine-level API: same call order as BANGSearch<T> (bang.h) / test_driver.cpp."""
 
@@ -401,19 +418,25 @@ class IterState:
     """Device-side state of Q queries for driving the KERNEL-level entries one by one (tests, bench).
 
     ``use_lut=True`` selects the LUT path (K1 builds [Q][m][256]; K2 gathers from it);
-    otherwise the pivot-stationary path is used when the index layout allows it."""
+    otherwise the pivot-stationary path is used when the index layout allows it.
+
+    ``codes=(address, stride)`` / ``graph=(address, stride)``: the PQ code rows / the graph entries are the caller's, already on the device at
+    that address, `stride` bytes apart (code_stride / entry_len of the launches); nothing is uploaded for them and ``graph`` implies
+    device_graph.  The fused re-rank of run_search reads the vectors from the graph entries."""
 
     def __init__(self, ix, queries: np.ndarray, L: int, use_lut: bool = False, dim_adjust: int = 0,
-                 device_graph: bool = False, ragged: bool = False):
+                 device_graph: bool = False, ragged: bool = False, codes=None, graph=None, extra_iters: int = EXTRA_ITERS):
         self.ix, self.L = ix, L
         self.Q = Q = queries.shape[0]
         self.dim_adjust = dim_adjust
         self.dtype_code = DTYPE_CODE[ix.dtype]
         q = np.ascontiguousarray(queries, dtype=NP_DTYPE[ix.dtype])
-        rows = L + EXTRA_ITERS
+        rows = L + extra_iters                   # (120 under bang_k_search_inmem: its candidate log is that long)
         self.rows = rows
         self.d_queries = DeviceBuffer.from_numpy(q, slack=16)
-        self.d_codes = DeviceBuffer.from_numpy(ix.codes, slack=256)
+        self.code_stride = codes[1] if codes else 0
+        self.entry_len = graph[1] if graph else ix.entry_len
+        self.d_codes = _Borrowed(codes[0]) if codes else DeviceBuffer.from_numpy(ix.codes, slack=256)
         self.d_centroid = DeviceBuffer.from_numpy(ix.centroid.astype(np.float32))
         self.d_chunk_off = DeviceBuffer.from_numpy(ix.chunk_off.astype(np.uint32))
         self.d_pivots_T = DeviceBuffer.from_numpy(np.ascontiguousarray(ix.pivots.T, dtype=np.float32))
@@ -444,7 +467,7 @@ class IterState:
         seed[1] = ix.medoid
         seed[2:2 + len(adj)] = adj
         self.d_seed = DeviceBuffer.from_numpy(seed)
-        self.d_graph = DeviceBuffer.from_numpy(ix.graph, slack=256) if device_graph else None
+        self.d_graph = _Borrowed(graph[0]) if graph else DeviceBuffer.from_numpy(ix.graph, slack=256) if device_graph else None
         self.d_stage = DeviceBuffer(Q * STAGE_STRIDE * 4)
         self.d_bloom = DeviceBuffer(Q * BF_WORDS * 4)
         self.d_nbrs = DeviceBuffer(Q * NBR_STRIDE * 4)
@@ -490,13 +513,13 @@ class IterState:
         p = IterParams()
         p.Q, p.R, p.m, p.L, p.medoid, p.iter = self.Q, ix.R, ix.m, self.L, ix.medoid, self.iter
         p.psz, p.mp, p.first = self.psz, self.mp, self.first
-        p.pq_nhi = self.pq_nhi
+        p.pq_nhi, p.code_stride = self.pq_nhi, self.code_stride
         p.d_stage, p.d_seed, p.d_codes = self.d_stage.ptr, self.d_seed.ptr, self.d_codes.ptr
         p.d_pivots_packed = self.d_pivots_packed.ptr if self.d_pivots_packed else None
         p.d_qc = self.d_qc.ptr if self.d_qc else None
         p.d_lut = self.d_lut.ptr if self.d_lut else None
         p.d_graph = self.d_graph.ptr if self.d_graph else None
-        p.entry_len = ix.entry_len
+        p.entry_len = self.entry_len
         p.vec_bytes = ix.D * np.dtype(NP_DTYPE[ix.dtype]).itemsize
         p.d_bloom, p.d_nbrs, p.d_dist, p.d_cnt = self.d_bloom.ptr, self.d_nbrs.ptr, self.d_dist.ptr, self.d_cnt.ptr
         p.d_wl_ids, p.d_wl_dist, p.d_wl_vis, p.d_wl_cnt = (self.d_wl_ids.ptr, self.d_wl_dist.ptr, self.d_wl_vis.ptr,
@@ -513,25 +536,35 @@ class IterState:
         _check(getattr(lib(), "bang_k_" + entry)(C.byref(p), None), "bang_k_" + entry)
         sync()
 
-    def run_search(self, entry: str = "bang_k_search"):
+    def run_search(self, entry: str = "bang_k_search", rerank_k: int = 0, guard=None):
         """The whole search loop in ONE launch of the query-resident search kernel (graph resident in HBM: needs
-        device_graph=True).  Fills the candidate log; returns the per-query iteration counts."""
+        device_graph=True).  Fills the candidate log; returns the per-query iteration counts.  rerank_k != 0: with the fused re-rank
+        (rr_*: the vectors read from the graph entries), its results in self.rr_ids [Q][k] / self.rr_dists [k][Q].  guard: n_nodes and
+        d_abort are set (None: for every entry but bang_k_search); self.abort is the abort word after the launch."""
         assert self.d_graph is not None and self.psz != 0
         ix = self.ix
         sp = SearchParams()
-        sp.Q, sp.R, sp.m, sp.L, sp.medoid, sp.cap_iter = self.Q, ix.R, ix.m, self.L, ix.medoid, self.L + EXTRA_ITERS - 1
+        sp.Q, sp.R, sp.m, sp.L, sp.medoid, sp.cap_iter = self.Q, ix.R, ix.m, self.L, ix.medoid, self.rows - 1
         sp.psz, sp.mp, sp.pq_nhi = self.psz, self.mp, self.pq_nhi
         sp.d_seed, sp.d_codes, sp.d_pivots_packed, sp.d_qc = self.d_seed.ptr, self.d_codes.ptr, self.d_pivots_packed.ptr, self.d_qc.ptr
-        sp.d_graph, sp.entry_len = self.d_graph.ptr, ix.entry_len
+        sp.d_graph, sp.entry_len, sp.code_stride = self.d_graph.ptr, self.entry_len, self.code_stride
         sp.vec_bytes = ix.D * np.dtype(NP_DTYPE[ix.dtype]).itemsize
         sp.d_bloom, sp.d_cand_ids, sp.d_cand_cnt, sp.d_qstats = self.d_bloom.ptr, self.d_cand_ids.ptr, self.d_cand_cnt.ptr, self.d_qstats.ptr
         d_iters = DeviceBuffer(self.Q * 4)
         d_next = DeviceBuffer(64)
         sp.d_qiters, sp.d_next_query = d_iters.ptr, d_next.ptr
-        if entry != "bang_k_search":
+        if (entry != "bang_k_search") if guard is None else guard:
             sp.n_nodes, sp.d_abort = ix.N, d_next.ptr + 4       # (an adjacency id >= N ends the batch instead of being followed)
+        if rerank_k:
+            d_ids, d_dists = DeviceBuffer(self.Q * rerank_k * 8), DeviceBuffer(self.Q * rerank_k * 4)
+            sp.rr_queries, sp.rr_vec_base, sp.rr_vec_stride = self.d_queries.ptr, self.d_graph.ptr, self.entry_len
+            sp.rr_ids_out, sp.rr_dists_out = d_ids.ptr, d_dists.ptr
+            sp.rr_dtype, sp.rr_D, sp.rr_k, sp.rr_q0, sp.rr_Q_total = self.dtype_code, ix.D, rerank_k, 0, self.Q
         _check(getattr(lib(), entry)(C.byref(sp), None), entry)
         sync()
+        self.abort = int(d_next.download(np.uint32, (2,))[1])
+        if rerank_k:
+            self.rr_ids, self.rr_dists = d_ids.download(np.uint64, (self.Q, rerank_k)), d_dists.download(np.float32, (rerank_k, self.Q))
         return d_iters.download(np.uint32, (self.Q,))
 
     def run_search_wf(self):
@@ -546,7 +579,7 @@ class IterState:
         sp = SearchParams()
         sp.Q, sp.R, sp.m, sp.L, sp.medoid, sp.cap_iter = self.Q, ix.R, ix.m, self.L, ix.medoid, self.L + EXTRA_ITERS - 1
         sp.d_seed, sp.d_codes, sp.d_lut = self.d_seed.ptr, self.d_codes.ptr, self.d_lut.ptr
-        sp.d_graph, sp.entry_len = self.d_graph.ptr, ix.entry_len
+        sp.d_graph, sp.entry_len, sp.code_stride = self.d_graph.ptr, self.entry_len, self.code_stride
         sp.vec_bytes = ix.D * np.dtype(NP_DTYPE[ix.dtype]).itemsize
         sp.n_nodes = ix.N
         sp.d_bloom, sp.d_cand_ids, sp.d_cand_cnt, sp.d_qstats = self.d_bloom.ptr, self.d_cand_ids.ptr, self.d_cand_cnt.ptr, self.d_qstats.ptr
@@ -555,6 +588,7 @@ class IterState:
         sp.d_qiters, sp.d_next_query, sp.d_abort = d_iters.ptr, d_next.ptr, d_next.ptr + 4
         _check(lib().bang_k_search_lut(C.byref(sp), None), "bang_k_search_lut")
         sync()
+        self.abort = int(d_next.download(np.uint32, (2,))[1])
         return d_iters.download(np.uint32, (self.Q,))
 
     def stage(self, lists):
@@ -591,11 +625,12 @@ class IterState:
         """K6+K7 with the vectors taken straight from a device copy of the graph."""
         if self.d_graph is None:
             self.d_graph = DeviceBuffer.from_numpy(self.ix.graph, slack=256)
+            self.entry_len = self.ix.entry_len
         ix = self.ix
         d_ids = DeviceBuffer(self.Q * k * 8)
         d_dists = DeviceBuffer(self.Q * k * 4)
         medoid_vec = DeviceBuffer.from_numpy(np.ascontiguousarray(ix.graph[ix.medoid]), slack=16)
-        _check(lib().bang_k_rerank(C.c_void_p(self.d_graph.ptr), C.c_uint64(ix.entry_len), C.c_void_p(medoid_vec.ptr),
+        _check(lib().bang_k_rerank(C.c_void_p(self.d_graph.ptr), C.c_uint64(self.entry_len), C.c_void_p(medoid_vec.ptr),
                                    C.c_void_p(self.d_queries.ptr), self.dtype_code, C.c_void_p(self.d_cand_ids.ptr),
                                    None, C.c_void_p(self.d_cand_cnt.ptr), self.rows, self.Q, ix.D, k, self.dim_adjust,
                                    C.c_void_p(d_ids.ptr), C.c_void_p(d_dists.ptr), None), "bang_k_rerank")

@@ -6,7 +6,12 @@
 * configs[2]/[3] layouts (DEEP100M: float32 x 96 in 74 chunks; SIFT1B: uint8 x 128 in 70 chunks) at an N whose PQ-code
   table AND graph are larger than 4 GiB, so that every 64-bit offset of the path is exercised -- `id * m`
   (bang_search.cu:1232), `parent * entry_len` in the device graph and in the host walker (:796-810), `id * vec_bytes` of the
-  resident vectors -- against the oracle on a small batch, bit for bit, in every placement."""
+  resident vectors -- against the oracle on a small batch, bit for bit, in every placement.
+
+Covered here: the engine forms of the BANG_Base PQ walk on the 70- and 74-chunk `search_kernel` instances, the launch-per-iteration kernels, the
+plain re-rank, and the fixed-stride 256-byte adjacency rows of the pulled forms; every other kernel-level entry (the exact-distance, beam, LUT,
+Inmemory and word-filter kernels, the fused and fp16 re-ranks, the fp16 conversion, the by-query and by-row re-rank) meets offsets beyond 4 GiB in
+tests/test_gpu_offsets64.py, on small tables at stretched strides."""
 import os
 import subprocess
 
