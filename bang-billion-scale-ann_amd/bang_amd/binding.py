@@ -93,6 +93,11 @@ class StatsExt(C.Structure):
     _fields_ = Stats._fields_ + [("filter_layout", C.c_uint64)]
 
 
+class StatsExt2(C.Structure):
+    """bang_stats_ext2: bang_stats_ext with the excluded-ids fields behind it (bang_get_stats_ext2)."""
+    _fields_ = StatsExt._fields_ + [("excluded", C.c_uint64), ("exclude_launches", C.c_uint64)]
+
+
 ENTRY_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)     # bang_entry_source
 
 
@@ -340,10 +345,28 @@ class Engine:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _check(fn(self._h, _vp(q), q.shape[0], C.c_void_p(d_ids), C.c_void_p(d_dists) if d_dists else None), "bang_query_dev")
 
+    def set_excluded(self, ids):
+        """bang_set_excluded_e: REPLACE the set of node ids no query returns (lazy deletes; the walk still passes through them).  ids: any integer
+        array-like, duplicates are fine, an empty one clears the set.  After load, before alloc."""
+        a = np.asarray(ids).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise BangError(f"set_excluded: ids must be integers (got {a.dtype})")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise BangError(f"set_excluded: an id is out of range for a node id ({int(a.min())} .. {int(a.max())})")
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        fn = lib().bang_set_excluded_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        _check(fn(self._h, _vp(a) if a.size else None, C.c_uint64(a.size)), "bang_set_excluded")
+
+    def clear_excluded(self):
+        fn = lib().bang_clear_excluded_e
+        fn.argtypes = [C.c_void_p]
+        _check(fn(self._h), "bang_clear_excluded")
+
     def stats(self) -> dict:
-        s = StatsExt()
-        _check(lib().bang_get_stats_ext(self._h, C.byref(s)), "bang_get_stats_ext")
-        return {f: getattr(s, f) for f, _ in StatsExt._fields_}
+        s = StatsExt2()
+        _check(lib().bang_get_stats_ext2(self._h, C.byref(s)), "bang_get_stats_ext2")
+        return {f: getattr(s, f) for f, _ in StatsExt2._fields_}
 
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the

@@ -29,6 +29,7 @@ void free_batch(bang_engine* e) {
   dfree(e->d_active); dfree(e->d_qstats); dfree(e->d_qskip); dfree(e->d_fp); dfree(e->d_results);
   e->d_ids_out = nullptr; e->d_dists_out = nullptr; e->d_qiters = nullptr;             // (inside d_results)
   if (e->h_results) { (void)hipHostFree(e->h_results); e->h_results = nullptr; e->h_results_dev = nullptr; }
+  dfree(e->d_live_ids); dfree(e->d_live_cnt); dfree(e->d_wl_ids_full); dfree(e->d_wl_dists_full);      // (excluded ids)
   dfree(e->d_done_count); dfree(e->d_stage); dfree(e->d_srows); dfree(e->d_sctl);
   if (e->h_parents) (void)hipHostFree(e->h_parents);
   if (e->h_pub_q) (void)hipHostFree(e->h_pub_q);
@@ -225,6 +226,14 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   // a walker form on an index whose graph entries only passed through at load time: map the graph file now (a streamed load
   // from an entry source has nothing to map: error)
   if (!dev_graph && !e->search_v2 && !e->search_exact && !e->walker_rows && !e->graph) BANG_TRY(map_graph_file(e));
+  // excluded ids (bang_set_excluded_e): the re-rank then reads the candidate log WITHOUT its excluded entries, a compacted list -- which only the
+  // forms that find a candidate's vector by its id can take (graph entries or the vector table in HBM).  Where the vectors travel in a log, their
+  // rows are found by a candidate's position in the candidate log, which compaction would break: refused, there is no unmasked fallback
+  if (e->n_excl != 0 && !e->search_exact && !dev_graph && !e->vec_on_device) {
+    bang_set_error("an engine with excluded ids needs the full-precision vectors resident in HBM (graph = device, or graph = host with vectors = 1): "
+                   "this form re-ranks from a vector log (%s), whose rows are indexed by log position", e->search_host ? "by query" : "by iteration");
+    return BANG_ERR_UNSUPPORTED;
+  }
   e->fp_direct = false;
   HIP_TRY_ALLOC(hipMalloc(&e->d_queries, nq * e->D * e->tsize + 16));
   if (e->psz) BANG_TRY(dmalloc(&e->d_qc, nq * e->mp * e->psz));
@@ -261,6 +270,15 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     e->d_dists_out = (float*)(e->d_results + e->res_off_dists);
     e->d_qiters = (uint32_t*)(e->d_results + e->res_off_iters);
     e->h_qiters.assign(nq, 0);
+  }
+  if (e->n_excl != 0) {                                                      // excluded ids: what bang_k_cand_live / bang_k_worklist_pick work on
+    if (e->search_exact) {
+      BANG_TRY(dmalloc(&e->d_wl_ids_full, nq * L));
+      BANG_TRY(dmalloc(&e->d_wl_dists_full, nq * L));
+    } else {
+      BANG_TRY(dmalloc(&e->d_live_ids, nq * rows));
+      BANG_TRY(dmalloc(&e->d_live_cnt, nq));
+    }
   }
   BANG_TRY(dmalloc(&e->d_parents_dev, nq));
   if (dev_graph) {

@@ -1,6 +1,8 @@
 // bang_cabi.cpp -- the engine-level C-ABI of include/bang_c.h: thin entry points over the engine (bang.h:36-87 / :89-101).
 #include "bang_engine.h"
 
+#include <cerrno>
+
 using namespace bang;
 
 // ------------------------------------------------------------------ errors
@@ -38,6 +40,74 @@ extern "C" int bang_dev_d2h(void* h_dst, const void* d_src, size_t bytes) {
 }
 extern "C" int bang_dev_sync(void) { HIP_TRY(hipDeviceSynchronize()); return BANG_OK; }
 
+// ------------------------------------------------------------------ excluded ids (lazy deletes)
+static void drop_excluded(bang_engine* e) {
+  dfree(e->d_excl);
+  e->n_excl = 0;
+}
+
+// the set as a bitmap, built on the host and copied to the device; nothing is touched before every id has been checked
+static int set_excluded(bang_engine* e, const uint32_t* ids, uint64_t n, const char* what) {
+  if (!e->loaded) { bang_set_error("%s: no index is loaded", what); return BANG_ERR_ARG; }
+  if (e->allocated) { bang_set_error("%s: the excluded ids must be set before bang_alloc (an allocation is live: call bang_free first)", what); return BANG_ERR_ARG; }
+  if (n != 0 && !ids) { bang_set_error("%s: ids is null", what); return BANG_ERR_ARG; }
+  for (uint64_t i = 0; i < n; ++i)
+    if (ids[i] >= e->N) {
+      bang_set_error("%s: id %u (entry %llu of the list) is out of range: the index has N = %u nodes", what, ids[i], (unsigned long long)i, e->N);
+      return BANG_ERR_ARG;
+    }
+  if (n == 0) { (void)hipSetDevice(e->device); drop_excluded(e); return BANG_OK; }
+  const size_t words = ((size_t)e->N + 31) / 32 + 1;               // + a word of slack
+  std::vector<uint32_t> bits(words, 0u);
+  for (uint64_t i = 0; i < n; ++i) bits[ids[i] >> 5] |= 1u << (ids[i] & 31u);
+  uint64_t distinct = 0;
+  for (uint32_t w : bits) distinct += (uint64_t)__builtin_popcount(w);
+  BANG_TRY(ensure_device(e));
+  if (!e->d_excl) BANG_TRY(dmalloc(&e->d_excl, words));
+  const hipError_t err = hipMemcpy(e->d_excl, bits.data(), words * 4, hipMemcpyHostToDevice);
+  if (err != hipSuccess) { drop_excluded(e); HIP_TRY(err); }
+  e->n_excl = distinct;
+  return BANG_OK;
+}
+
+extern "C" int bang_set_excluded_e(bang_engine_t* e, const uint32_t* ids, uint64_t n) {
+  if (!e) return BANG_ERR_ARG;
+  return set_excluded(e, ids, n, "bang_set_excluded");
+}
+
+extern "C" int bang_clear_excluded_e(bang_engine_t* e) {
+  if (!e) return BANG_ERR_ARG;
+  return set_excluded(e, nullptr, 0, "bang_clear_excluded");
+}
+
+// BANG_EXCLUDE_FILE: the last step of every load.  The file has the .bin layout (i32 count, i32 1, count u32 ids)
+static int load_exclude_file(bang_engine* e) {
+  const char* path = env_str("BANG_EXCLUDE_FILE");
+  if (!path) return BANG_OK;
+  FILE* f = fopen(path, "rb");
+  if (!f) { bang_set_error("BANG_EXCLUDE_FILE %s: cannot be opened: %s", path, strerror(errno)); return BANG_ERR_IO; }
+  int32_t hdr[2] = {0, 0};
+  std::vector<uint32_t> ids;
+  bool ok = fread(hdr, 4, 2, f) == 2 && hdr[0] >= 0 && hdr[1] == 1;
+  if (ok) {
+    ids.resize((size_t)hdr[0]);
+    ok = fread(ids.data(), 4, ids.size(), f) == ids.size() && fgetc(f) == EOF;
+  }
+  fclose(f);
+  if (!ok) { bang_set_error("BANG_EXCLUDE_FILE %s: not a .bin file of ids (i32 count, i32 1, count u32 ids)", path); return BANG_ERR_IO; }
+  const int rc = set_excluded(e, ids.data(), ids.size(), "BANG_EXCLUDE_FILE");
+  if (rc != BANG_OK) {
+    const std::string why = bang_last_error();
+    bang_set_error("BANG_EXCLUDE_FILE %s: %s", path, why.c_str());
+  }
+  return rc;
+}
+static int finish_load(bang_engine* e, int rc) {
+  if (rc == BANG_OK) rc = load_exclude_file(e);
+  if (rc != BANG_OK) { drop_excluded(e); unload_index(e); }
+  return rc;
+}
+
 // ------------------------------------------------------------------ C-ABI, engine level
 extern "C" int bang_create(int dtype, bang_engine_t** out) {
   if (!out || dtype < BANG_U8 || dtype > BANG_F32) { bang_set_error("bad dtype"); return BANG_ERR_ARG; }
@@ -55,6 +125,7 @@ extern "C" int bang_create(int dtype, bang_engine_t** out) {
 extern "C" int bang_destroy(bang_engine_t* e) {
   if (!e) return BANG_OK;
   if (e->allocated) free_batch(e);
+  drop_excluded(e);
   if (e->loaded) unload_index(e);
   delete e;
   return BANG_OK;
@@ -64,7 +135,9 @@ extern "C" int bang_load_e(bang_engine_t* e, const char* prefix) {
   if (!e || !prefix) return BANG_ERR_ARG;
   if (e->loaded) { bang_set_error("index already loaded"); return BANG_ERR_ARG; }
   BANG_TRY(ensure_device(e));
-  return load_files(e, prefix);
+  const int rc = load_files(e, prefix);
+  if (rc != BANG_OK) return rc;
+  return finish_load(e, rc);
 }
 
 extern "C" int bang_load_mem_e(bang_engine_t* e, const bang_index_desc* d) {
@@ -79,8 +152,7 @@ extern "C" int bang_load_mem_e(bang_engine_t* e, const bang_index_desc* d) {
   e->graph_owned = nullptr;
   e->graph_path.clear();
   const int rc = upload_index(e, d->codes, d->d_codes, d->pivots, d->centroid, d->chunk_off, d->d_codes ? d->code_stride : 0);
-  if (rc != BANG_OK) unload_index(e);
-  return rc;
+  return finish_load(e, rc);
 }
 
 extern "C" int bang_load_stream_e(bang_engine_t* e, const bang_index_desc* d, bang_entry_source src, void* ctx) {
@@ -104,8 +176,7 @@ extern "C" int bang_load_stream_e(bang_engine_t* e, const bang_index_desc* d, ba
   e->ext_vecs = (uint8_t*)d->d_vectors; e->ext_vecs_ready = false;
   const int rc = upload_index(e, d->codes, d->d_codes, d->pivots, d->centroid, d->chunk_off, d->d_codes ? d->code_stride : 0);
   e->entry_fn = nullptr; e->entry_ctx = nullptr; e->ext_vecs = nullptr;
-  if (rc != BANG_OK) unload_index(e);
-  return rc;
+  return finish_load(e, rc);
 }
 
 extern "C" int bang_load_shared_e(bang_engine_t* e, const bang_index_desc* d) {
@@ -127,8 +198,7 @@ extern "C" int bang_load_shared_e(bang_engine_t* e, const bang_index_desc* d) {
   e->ext_vecs = (uint8_t*)d->d_vectors; e->ext_vecs_ready = true; e->rows_hash = d->rows_hash;
   const int rc = upload_index(e, d->codes, d->d_codes, d->pivots, d->centroid, d->chunk_off, d->d_codes ? d->code_stride : 0);
   e->ext_vecs = nullptr; e->ext_vecs_ready = false;
-  if (rc != BANG_OK) unload_index(e);
-  return rc;
+  return finish_load(e, rc);
 }
 
 extern "C" int bang_get_rows_hash(bang_engine_t* e, uint64_t* out) {
@@ -281,6 +351,8 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
     s.sync_ms += ln.sync_ms; s.enqueue_ms += ln.enqueue_ms;
     s.h2d_bytes += ln.h2d_bytes.load();
   }
+  e->stat_exclude_launches = 0;
+  for (auto& lp : e->lanes) e->stat_exclude_launches += lp->exclude_launches;
   s.persistent = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
   s.vectors_on_device = e->vec_on_device ? 1 : 0;
   s.graph_mode = (uint64_t)e->graph_mode;
@@ -396,6 +468,14 @@ extern "C" int bang_get_stats_ext(bang_engine_t* e, bang_stats_ext* out) {
   return BANG_OK;
 }
 
+extern "C" int bang_get_stats_ext2(bang_engine_t* e, bang_stats_ext2* out) {
+  if (!e || !out) return BANG_ERR_ARG;
+  BANG_TRY(bang_get_stats_ext(e, &out->ext));
+  out->excluded = e->n_excl;
+  out->exclude_launches = e->stat_exclude_launches;
+  return BANG_OK;
+}
+
 extern "C" int bang_get_query_counters(bang_engine_t* e, uint32_t* dist_evals, uint32_t* fetched, uint32_t* candidates, uint32_t* iterations) {
   if (!e) return BANG_ERR_ARG;
   if (!e->allocated || e->Qcur <= 0) { bang_set_error("bang_get_query_counters: no query has run on this allocation"); return BANG_ERR_ARG; }
@@ -436,7 +516,7 @@ extern "C" int bang_free_e(bang_engine_t* e) {
 extern "C" int bang_unload_e(bang_engine_t* e) {
   if (!e) return BANG_ERR_ARG;
   if (e->allocated) free_batch(e);
-  if (e->loaded) { (void)hipSetDevice(e->device); unload_index(e); }
+  if (e->loaded) { (void)hipSetDevice(e->device); drop_excluded(e); unload_index(e); }
   return BANG_OK;
 }
 

@@ -94,6 +94,7 @@ struct Lane {
   std::string err;
   uint32_t iterations = 0;
   uint64_t front_launches = 0;
+  uint64_t exclude_launches = 0;      // bang_k_cand_live / bang_k_worklist_pick launches of the last run
   double walker_ms = 0, front_ms = 0, back_ms = 0, rerank_ms = 0, sync_ms = 0, enqueue_ms = 0;
 };
 
@@ -295,6 +296,14 @@ struct bang_engine {
   int walker_stall_ms = 0;             // test hook: the walker team sleeps this long at the start of the next host-paced query (one shot)
   bang_stats stats{};
   uint64_t stat_filter_layout = 0;     // bang_stats_ext.filter_layout of the last bang_query
+  // excluded ids (bang_set_excluded_e): the set lives from load to unload, its per-batch buffers from bang_alloc to bang_free
+  uint32_t* d_excl = nullptr;          // bitmap [ceil(N / 32) + 1]: bit (id & 31) of word id >> 5; NULL = the set is empty
+  uint64_t n_excl = 0;                 // distinct ids in the set
+  uint32_t* d_live_ids = nullptr;      // [Q][cand_stride] the candidate log without its excluded entries (bang_k_cand_live) -- what the re-rank reads
+  uint32_t* d_live_cnt = nullptr;      // [Q]
+  uint64_t* d_wl_ids_full = nullptr;   // distance = 1: [Q][L] the exact kernel's results at rr_k = L (the whole final worklist) ...
+  float* d_wl_dists_full = nullptr;    // ... and [L][Q] their distances; bang_k_worklist_pick takes the first k live entries from there
+  uint64_t stat_exclude_launches = 0;  // bang_stats_ext2.exclude_launches of the last bang_query
 };
 
 // bang_search.hip, part 2 (semantics = 1): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride

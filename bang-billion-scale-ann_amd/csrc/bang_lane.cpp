@@ -79,7 +79,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   const uint32_t cap_iter = (uint32_t)e->L + (e->search_inmem ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS) - 1;   // :950 (semantics = 1: L + 119)
   if (ln.kt_used) { (void)hipMemset(ln.d_ktime, 0, ln.kt_used * KT_WGS * 16); ln.kt_used = 0; }   // stats not collected
   if (e->h_fin.size() >= (size_t)ln.q0 + ln.nq) memset(e->h_fin.data() + ln.q0, 0, ln.nq);
-  ln.h2d_bytes.store(0); ln.iterations = 0; ln.front_launches = 0; ln.walker_ms = 0; ln.sync_ms = 0; ln.enqueue_ms = 0;
+  ln.h2d_bytes.store(0); ln.iterations = 0; ln.front_launches = 0; ln.exclude_launches = 0; ln.walker_ms = 0; ln.sync_ms = 0; ln.enqueue_ms = 0;
   auto t_enq = Clock::now();
 #define ENQ_BEGIN() (t_enq = Clock::now())
 #define ENQ_END() (ln.enqueue_ms += ms_since(t_enq))
@@ -116,7 +116,10 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   };
   // K6 + K7 inside the search launch (8-bit vectors, self-paced form): no launch behind it
   // (an fp16 vector table, option vectors_fp16, is read by the re-rank launch only)
-  const bool fused_rerank = e->search_v2 && e->fuse_rerank != 0 && (dev_graph || e->vec_on_device) && !e->vecs_f16 &&
+  // excluded ids (bang_set_excluded_e): the walk runs as ever; the re-rank is a launch of its own on the log without its excluded
+  // entries (PQ walks), the exact-distance kernel hands over its whole worklist (rr_k = L) and bang_k_worklist_pick takes the first k live entries
+  const bool masked = e->n_excl != 0 && e->d_excl != nullptr;
+  const bool fused_rerank = !masked && e->search_v2 && e->fuse_rerank != 0 && (dev_graph || e->vec_on_device) && !e->vecs_f16 &&
                             bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : vb, dim_adjust) != 0;
   // distance = 1: the exact-distance kernel writes the results itself, as the fused re-rank does (no launch behind it)
   const bool results_in_launch = fused_rerank || e->search_exact;
@@ -135,7 +138,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   const bool mailbox = !to_device && whole && e->res_off_iters <= mailbox_max;
   // ... and with the re-rank fused into the search launch the kernel writes ids, distances, iteration counts and its abort word straight
   // into that pinned mirror (posted PCIe writes, a query at a time as the queries finish): nothing is copied behind the launch
-  const bool results_direct = mailbox && results_in_launch && e->h_results_dev != nullptr && env_long("BANG_RESULTS_DIRECT", 1) != 0;
+  const bool results_direct = !masked && mailbox && results_in_launch && e->h_results_dev != nullptr && env_long("BANG_RESULTS_DIRECT", 1) != 0;
   // queries H2D (:612) + K1 (:623)
   uint8_t* dq = (uint8_t*)e->d_queries + (size_t)ln.q0 * qbytes;
   LANE_HIP(hipMemcpyAsync(dq, (const uint8_t*)h_queries + (size_t)ln.q0 * qbytes, (size_t)ln.nq * qbytes,
@@ -189,6 +192,11 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
       sp.rr_ids_out = d_ids_user;
       if (d_dists_user) sp.rr_dists_out = d_dists_user;
     }
+    uint64_t* pick_ids = sp.rr_ids_out;                               // (where the query's k results belong)
+    float* pick_dists = sp.rr_dists_out;
+    if (masked) {                                                     // excluded ids: the whole final worklist, [Q][L] / [L][Q]; the pick follows
+      sp.rr_k = (uint32_t)e->L; sp.rr_ids_out = e->d_wl_ids_full; sp.rr_dists_out = e->d_wl_dists_full;
+    }
     if (results_direct) {                                             // straight into the pinned mirror
       sp.rr_ids_out = (uint64_t*)e->h_results_dev; sp.rr_dists_out = (float*)(e->h_results_dev + e->res_off_dists);
       sp.d_qiters = (uint32_t*)(e->h_results_dev + e->res_off_iters) + ln.q0;
@@ -201,6 +209,11 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     ENQ_BEGIN();
     if (e->beam > 1) BANG_TRY(bang_k_search_exact_beam(&sp, (uint32_t)e->beam, ln.s_main));   // up to beam parents per iteration (bang_search_beam.hip)
     else BANG_TRY(bang_k_search_exact(&sp, ln.s_main));
+    if (masked) {
+      BANG_TRY(bang_k_worklist_pick(e->d_wl_ids_full, e->d_wl_dists_full, (uint32_t)e->L, ln.q0, ln.nq, (uint32_t)Q, e->d_excl, e->N, (uint32_t)e->k,
+                                    pick_ids, pick_dists, ln.s_main));
+      ++ln.exclude_launches;
+    }
     ENQ_END();
     ++ln.front_launches;
     iter = cap_iter;                                                         // refined from the per-query counts below
@@ -442,15 +455,22 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     LANE_HIP(hipStreamWaitEvent(ln.s_main, ln.ev_fp, 0));
   }
   if (!results_in_launch) {
+    const uint32_t* rr_ids = e->d_cand_ids;
+    const uint32_t* rr_cnt = e->d_cand_cnt;
+    if (masked) {                                    // the log without its excluded entries, in log order (the log itself stays the walk's)
+      BANG_TRY(bang_k_cand_live(e->d_cand_ids, e->d_cand_cnt, e->cand_stride, ln.q0, ln.nq, e->d_excl, e->N, e->d_live_ids, e->d_live_cnt, ln.s_main));
+      ++ln.exclude_launches;
+      rr_ids = e->d_live_ids; rr_cnt = e->d_live_cnt;
+    }
     if (dev_graph)
-      BANG_TRY(bang_k_rerank_range(e->d_graph, e->entry_len, e->d_medoid_vec, e->d_queries, e->dtype, e->d_cand_ids,
-                                   nullptr, e->d_cand_cnt, e->cand_stride, ln.q0, ln.nq, (uint32_t)Q, e->D,
+      BANG_TRY(bang_k_rerank_range(e->d_graph, e->entry_len, e->d_medoid_vec, e->d_queries, e->dtype, rr_ids,
+                                   nullptr, rr_cnt, e->cand_stride, ln.q0, ln.nq, (uint32_t)Q, e->D,
                                    (uint32_t)e->k, dim_adjust, e->d_ids_out, e->d_dists_out, ln.s_main));
     else if (e->vec_on_device && e->vecs_f16)
-      BANG_TRY(bang_k_rerank_f16_range(e->d_vecs, vec_table_stride(e), e->d_queries, e->d_cand_ids, e->d_cand_cnt, e->cand_stride, ln.q0, ln.nq,
+      BANG_TRY(bang_k_rerank_f16_range(e->d_vecs, vec_table_stride(e), e->d_queries, rr_ids, rr_cnt, e->cand_stride, ln.q0, ln.nq,
                                        (uint32_t)Q, e->D, (uint32_t)e->k, dim_adjust, e->d_ids_out, e->d_dists_out, ln.s_main));
     else if (e->vec_on_device)
-      BANG_TRY(bang_k_rerank_range(e->d_vecs, vb, e->d_medoid_vec, e->d_queries, e->dtype, e->d_cand_ids, nullptr, e->d_cand_cnt,
+      BANG_TRY(bang_k_rerank_range(e->d_vecs, vb, e->d_medoid_vec, e->d_queries, e->dtype, rr_ids, nullptr, rr_cnt,
                                    e->cand_stride, ln.q0, ln.nq, (uint32_t)Q, e->D, (uint32_t)e->k, dim_adjust, e->d_ids_out,
                                    e->d_dists_out, ln.s_main));
     else if (e->search_host)

@@ -160,6 +160,23 @@ int bang_query_e(bang_engine_t* e, const void* h_queries, int num_queries, uint6
  * 8(e)) instead of bouncing them through the host.  Complete (stream synchronised) on return. */
 int bang_query_dev_e(bang_engine_t* e, const void* h_queries, int num_queries, uint64_t* d_ids, float* d_dists);
 int bang_free_e(bang_engine_t* e);                                                          /* bang.h:80 */
+
+/* EXCLUDED IDS (lazy deletes, DESIGN.md section 2 CANON 17): an engine carries a set X of node ids that bang_query_e / bang_query_dev_e never
+ * return.  The walk ignores X -- excluded nodes are evaluated, expanded and logged like any other, so counters and candidate log are those of the
+ * same run with X empty, bit for bit -- and the results are composed behind it: on the PQ walks the re-rank (K6 + K7) runs on the candidate log
+ * without its entries in X (bang_k_cand_live; the re-rank is then a launch of its own: bang_stats.rerank_fused = 0), with distance = 1 the results
+ * are the first k entries of the final worklist that are not in X (bang_k_worklist_pick).  Fewer than k left: the tail is UINT64_MAX /
+ * 3.402823E+38f.  An allow-list is the exclusion of its complement.
+ * bang_set_excluded_e REPLACES the set by the n ids (duplicates are fine; n = 0 clears it; ids may be NULL then): a bitmap of ceil(N / 32) + 1
+ * words is built on the host and copied to HBM (125 MB at N = 10^9).  An id >= N is refused (BANG_ERR_ARG, "out of range") before anything is
+ * copied and the set stays what it was.  Both calls need a loaded index and are refused while an allocation is live (bang_free_e first): the
+ * allocation holds the buffers the set needs.  bang_unload_e drops the set.  With X empty nothing changes -- same launches, the fused re-rank where
+ * it was fused.  Not served, refused by bang_alloc_e with "excluded" in the message: the forms whose re-rank reads a vector LOG (graph in host RAM
+ * without the vectors resident in HBM).
+ * Environment, for callers of the bang.h class and the bang_search CLI: BANG_EXCLUDE_FILE names a .bin file (i32 count, i32 1, count u32 ids)
+ * that every load (bang_load_e, _mem_e, _stream_e, _shared_e) reads as its last step; an unreadable file or an id out of range fails the load. */
+int bang_set_excluded_e(bang_engine_t* e, const uint32_t* ids, uint64_t n);
+int bang_clear_excluded_e(bang_engine_t* e);
 int bang_unload_e(bang_engine_t* e);                                                        /* bang.h:82 */
 
 /* statistics of the last bang_query_e */
@@ -219,6 +236,14 @@ typedef struct {
                                  base.filter_loads_skipped counts of 1 x `fetched` probes) */
 } bang_stats_ext;
 int bang_get_stats_ext(bang_engine_t* e, bang_stats_ext* out);
+/* ... and the same once more for the excluded ids (bang_set_excluded_e): bang_stats_ext keeps its size and offsets as bang_stats did, the two new
+ * fields sit at the end of the statistics, behind it.  The first sizeof(bang_stats_ext) bytes are what bang_get_stats_ext fills. */
+typedef struct {
+  bang_stats_ext ext;
+  uint64_t excluded;          /* distinct ids in the engine's exclusion set, 0 = none */
+  uint64_t exclude_launches;  /* launches of bang_k_cand_live / bang_k_worklist_pick of the last bang_query_e, summed over the lanes (0 with an empty set) */
+} bang_stats_ext2;
+int bang_get_stats_ext2(bang_engine_t* e, bang_stats_ext2* out);
 /* Per-query counters of the last bang_query_e (arrays of num_queries words; any pointer may be NULL): PQ distance evaluations,
  * adjacency ids offered to the filter, expanded nodes (candidate-log length) and -- search kernel only, else zeros -- the number
  * of iterations the query ran.  Test hook: the oracle reports the same four numbers per query. */
@@ -568,6 +593,25 @@ int bang_search_lut_supported(uint32_t m, uint32_t L);
 /* grid of a bang_k_search_lut launch over Q queries at worklist length L: as bang_search_exact_geometry (waves per CU from the instance's
  * registers and LDS, <= 16 per workgroup; max_wgs / max_waves: caps if nonzero; small batches spread over all CUs) */
 int bang_search_lut_geometry(uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+
+/* EXCLUDED IDS, device side (csrc/bang_exclude.hip; engine: bang_set_excluded_e).  d_bitmap holds bit (id & 31) of word id >> 5 for every id of the
+ * set: ceil(n_nodes / 32) words plus one word of slack.  An id >= n_nodes is in no set and is never looked up.  Both kernels: one wave per query,
+ * four waves per workgroup, no LDS; both entries check their arguments before any HIP call -- a null buffer, cand_stride = 0, k = 0, k > L,
+ * Q_total = 0 or < q0 + nq is BANG_ERR_ARG with the member named -- and nq = 0 is no launch.
+ *
+ * bang_k_cand_live, the PQ walks: for the queries q0 .. q0 + nq - 1 (rows of the [Q][cand_stride] arrays, as in bang_k_rerank's sub-range form) the
+ * first min(d_cand_cnt[q], cand_stride) entries of the candidate log row d_cand_ids[q] that are NOT in the set go to d_live_ids[q], in log order,
+ * their number to d_live_cnt[q].  The log and its counts are only read.  bang_k_rerank / bang_k_rerank_f16 then take d_live_ids / d_live_cnt where
+ * they took the log: same arithmetic, same stable rank, ties in expansion order. */
+int bang_k_cand_live(const uint32_t* d_cand_ids, const uint32_t* d_cand_cnt, uint32_t cand_stride, uint32_t q0, uint32_t nq,
+                     const uint32_t* d_bitmap, uint32_t n_nodes, uint32_t* d_live_ids, uint32_t* d_live_cnt, void* stream);
+/* bang_k_worklist_pick, the exact-distance walks: the input is what bang_k_search_exact / _beam write at rr_k = L -- d_wl_ids [Q_total][L] u64, the
+ * whole final worklist of a query (UINT64_MAX behind a short one), and d_wl_dists [L][Q_total] f32, rank-major.  For the queries q0 .. q0 + nq - 1
+ * the first k entries in worklist order that are not in the set go to d_ids_out [Q_total][k] / d_dists_out [k][Q_total], distance bits unchanged;
+ * every copy of an id that the worklist holds twice is kept or dropped alike; an entry UINT64_MAX ends the scan; the tail is padded with
+ * UINT64_MAX / 3.402823E+38f.  The outputs must not be the inputs. */
+int bang_k_worklist_pick(const uint64_t* d_wl_ids, const float* d_wl_dists, uint32_t L, uint32_t q0, uint32_t nq, uint32_t Q_total,
+                         const uint32_t* d_bitmap, uint32_t n_nodes, uint32_t k, uint64_t* d_ids_out, float* d_dists_out, void* stream);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
