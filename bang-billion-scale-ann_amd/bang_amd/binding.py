@@ -98,6 +98,16 @@ class StatsExt2(C.Structure):
     _fields_ = StatsExt._fields_ + [("excluded", C.c_uint64), ("exclude_launches", C.c_uint64)]
 
 
+class StatsExt3(C.Structure):
+    """bang_stats_ext3: bang_stats_ext2 with the label-filter fields behind it (bang_get_stats_ext3)."""
+    _fields_ = StatsExt2._fields_ + [("labelled", C.c_uint64), ("filtered_queries", C.c_uint64), ("label_launches", C.c_uint64)]
+
+
+class LabelFilter(C.Structure):
+    """bang_label_filter: what bang_k_search_exact_labels takes beside bang_search_params (device addresses)."""
+    _fields_ = [("d_labels", C.c_void_p), ("d_filters", C.c_void_p), ("d_excluded", C.c_void_p), ("d_matched", C.c_void_p)]
+
+
 ENTRY_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)     # bang_entry_source
 
 
@@ -363,10 +373,59 @@ class Engine:
         fn.argtypes = [C.c_void_p]
         _check(fn(self._h), "bang_clear_excluded")
 
+    def set_labels(self, labels):
+        """bang_set_labels_e: REPLACE the label table -- one 32-bit word (up to 32 tags) per node, N of them; an empty one clears it.  After
+        load, before alloc."""
+        a = np.asarray(labels).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise BangError(f"set_labels: labels must be integers (got {a.dtype})")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise BangError(f"set_labels: a label word is out of range for 32 bits ({int(a.min())} .. {int(a.max())})")
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        fn = lib().bang_set_labels_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        _check(fn(self._h, _vp(a) if a.size else None, C.c_uint64(a.size)), "bang_set_labels")
+
+    def clear_labels(self):
+        fn = lib().bang_clear_labels_e
+        fn.argtypes = [C.c_void_p]
+        _check(fn(self._h), "bang_clear_labels")
+
+    def set_filters(self, any, all):
+        """bang_set_query_filters_e: the filters of the batches to come, one {any, all} pair per query: node x matches when
+        (any == 0 or labels[x] & any) and labels[x] & all == all.  After alloc; kept until replaced, cleared or free."""
+        words = []
+        for name, w in (("any", any), ("all", all)):
+            w = np.asarray(w).reshape(-1)
+            if w.size and w.dtype.kind not in "iu":
+                raise BangError(f"set_filters: `{name}` must be integers (got {w.dtype})")
+            if w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF):
+                raise BangError(f"set_filters: a word of `{name}` is out of range for 32 bits ({int(w.min())} .. {int(w.max())})")
+            words.append(np.ascontiguousarray(w, dtype=np.uint32))
+        a, b = words
+        if a.size != b.size:
+            raise BangError(f"set_filters: {a.size} `any` words and {b.size} `all` words")
+        fn = lib().bang_set_query_filters_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _check(fn(self._h, _vp(a) if a.size else None, _vp(b) if b.size else None, int(a.size)), "bang_set_query_filters")
+
+    def clear_filters(self):
+        fn = lib().bang_clear_query_filters_e
+        fn.argtypes = [C.c_void_p]
+        _check(fn(self._h), "bang_clear_query_filters")
+
+    def matched_counts(self, Q: int) -> np.ndarray:
+        """[Q] matching survivors offered to each query's result list in the last filtered batch."""
+        out = np.zeros(Q, np.uint32)
+        fn = lib().bang_get_matched_counts
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        _check(fn(self._h, _vp(out), C.c_uint32(Q)), "bang_get_matched_counts")
+        return out
+
     def stats(self) -> dict:
-        s = StatsExt2()
-        _check(lib().bang_get_stats_ext2(self._h, C.byref(s)), "bang_get_stats_ext2")
-        return {f: getattr(s, f) for f, _ in StatsExt2._fields_}
+        s = StatsExt3()
+        _check(lib().bang_get_stats_ext3(self._h, C.byref(s)), "bang_get_stats_ext3")
+        return {f: getattr(s, f) for f, _ in StatsExt3._fields_}
 
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the

@@ -30,6 +30,8 @@ void free_batch(bang_engine* e) {
   e->d_ids_out = nullptr; e->d_dists_out = nullptr; e->d_qiters = nullptr;             // (inside d_results)
   if (e->h_results) { (void)hipHostFree(e->h_results); e->h_results = nullptr; e->h_results_dev = nullptr; }
   dfree(e->d_live_ids); dfree(e->d_live_cnt); dfree(e->d_wl_ids_full); dfree(e->d_wl_dists_full);      // (excluded ids)
+  dfree(e->d_qfilters); dfree(e->d_matched); e->n_qfilters = 0; e->n_filtered = 0;                      // (query filters)
+  e->qfilter_file_rows.clear(); e->qfilters_from_file = false;
   dfree(e->d_done_count); dfree(e->d_stage); dfree(e->d_srows); dfree(e->d_sctl);
   if (e->h_parents) (void)hipHostFree(e->h_parents);
   if (e->h_pub_q) (void)hipHostFree(e->h_pub_q);

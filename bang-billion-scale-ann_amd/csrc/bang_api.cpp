@@ -12,6 +12,7 @@
 
 #include "bang.h"
 #include "bang_c.h"
+#include "bang_internal.h"
 
 namespace {
 template <typename T> constexpr int dtype_of() {
@@ -64,6 +65,7 @@ template <typename T>
 void BANGSearch<T>::bang_query(T* query_array, int num_queries, result_ann_t* nearestNeighbours,
                                float* nearestNeighbours_dist) {
   static_assert(sizeof(result_ann_t) == sizeof(uint64_t), "result_ann_t must be 64-bit");
+  die_on(bang_apply_query_filter_file_e(static_cast<bang_engine_t*>(m_pImpl), num_queries), "bang_query");   // BANG_QUERY_FILTER_FILE, if set
   die_on(bang_query_e(static_cast<bang_engine_t*>(m_pImpl), query_array, num_queries,
                       reinterpret_cast<uint64_t*>(nearestNeighbours), nearestNeighbours_dist),
          "bang_query");

@@ -80,21 +80,32 @@ extern "C" int bang_clear_excluded_e(bang_engine_t* e) {
   return set_excluded(e, nullptr, 0, "bang_clear_excluded");
 }
 
+// a .bin file of u32 words with `cols` columns (i32 rows, i32 cols, rows x cols u32) -> words.  The header's row count must be what the file's size
+// says before anything is allocated for it: a corrupt header is a refused file, not an allocation of up to 2^31 rows
+static int read_u32_bin(const char* var, const char* path, int32_t cols, const char* layout, std::vector<uint32_t>& words) {
+  FILE* f = fopen(path, "rb");
+  if (!f) { bang_set_error("%s %s: cannot be opened: %s", var, path, strerror(errno)); return BANG_ERR_IO; }
+  int32_t hdr[2] = {0, 0};
+  bool ok = fread(hdr, 4, 2, f) == 2 && hdr[0] >= 0 && hdr[1] == cols;
+  if (ok) {
+    const long long want = 8ll + 4ll * (long long)hdr[0] * (long long)cols;
+    ok = fseek(f, 0, SEEK_END) == 0 && (long long)ftell(f) == want && fseek(f, 8, SEEK_SET) == 0;
+  }
+  if (ok) {
+    words.resize((size_t)hdr[0] * (size_t)cols);
+    ok = fread(words.data(), 4, words.size(), f) == words.size();
+  }
+  fclose(f);
+  if (!ok) { bang_set_error("%s %s: not a .bin file of %s", var, path, layout); return BANG_ERR_IO; }
+  return BANG_OK;
+}
+
 // BANG_EXCLUDE_FILE: the last step of every load.  The file has the .bin layout (i32 count, i32 1, count u32 ids)
 static int load_exclude_file(bang_engine* e) {
   const char* path = env_str("BANG_EXCLUDE_FILE");
   if (!path) return BANG_OK;
-  FILE* f = fopen(path, "rb");
-  if (!f) { bang_set_error("BANG_EXCLUDE_FILE %s: cannot be opened: %s", path, strerror(errno)); return BANG_ERR_IO; }
-  int32_t hdr[2] = {0, 0};
   std::vector<uint32_t> ids;
-  bool ok = fread(hdr, 4, 2, f) == 2 && hdr[0] >= 0 && hdr[1] == 1;
-  if (ok) {
-    ids.resize((size_t)hdr[0]);
-    ok = fread(ids.data(), 4, ids.size(), f) == ids.size() && fgetc(f) == EOF;
-  }
-  fclose(f);
-  if (!ok) { bang_set_error("BANG_EXCLUDE_FILE %s: not a .bin file of ids (i32 count, i32 1, count u32 ids)", path); return BANG_ERR_IO; }
+  BANG_TRY(read_u32_bin("BANG_EXCLUDE_FILE", path, 1, "ids (i32 count, i32 1, count u32 ids)", ids));
   const int rc = set_excluded(e, ids.data(), ids.size(), "BANG_EXCLUDE_FILE");
   if (rc != BANG_OK) {
     const std::string why = bang_last_error();
@@ -102,9 +113,133 @@ static int load_exclude_file(bang_engine* e) {
   }
   return rc;
 }
+// ------------------------------------------------------------------ labels and per-query filters
+static void drop_labels(bang_engine* e) { dfree(e->d_labels); }
+
+static int set_labels(bang_engine* e, const uint32_t* labels, uint64_t n, const char* what) {
+  if (!e->loaded) { bang_set_error("%s: no index is loaded", what); return BANG_ERR_ARG; }
+  if (e->allocated) { bang_set_error("%s: the labels must be set before bang_alloc (an allocation is live: call bang_free first)", what); return BANG_ERR_ARG; }
+  if (n == 0) { (void)hipSetDevice(e->device); drop_labels(e); return BANG_OK; }
+  if (n != e->N) { bang_set_error("%s: %llu labels for an index of N = %u nodes: every node carries one label word", what, (unsigned long long)n, e->N); return BANG_ERR_ARG; }
+  if (!labels) { bang_set_error("%s: labels is null", what); return BANG_ERR_ARG; }
+  BANG_TRY(ensure_device(e));
+  if (!e->d_labels) BANG_TRY(dmalloc(&e->d_labels, (size_t)e->N));
+  const hipError_t err = hipMemcpy(e->d_labels, labels, (size_t)e->N * 4, hipMemcpyHostToDevice);
+  if (err != hipSuccess) { drop_labels(e); HIP_TRY(err); }
+  return BANG_OK;
+}
+
+extern "C" int bang_set_labels_e(bang_engine_t* e, const uint32_t* labels, uint64_t n) {
+  if (!e) return BANG_ERR_ARG;
+  return set_labels(e, labels, n, "bang_set_labels");
+}
+
+extern "C" int bang_clear_labels_e(bang_engine_t* e) {
+  if (!e) return BANG_ERR_ARG;
+  return set_labels(e, nullptr, 0, "bang_clear_labels");
+}
+
+// BANG_LABEL_FILE: read behind BANG_EXCLUDE_FILE as the last step of every load.  The file has the .bin layout (i32 N, i32 1, N u32 label words)
+static int load_label_file(bang_engine* e) {
+  const char* path = env_str("BANG_LABEL_FILE");
+  if (!path) return BANG_OK;
+  std::vector<uint32_t> words;
+  BANG_TRY(read_u32_bin("BANG_LABEL_FILE", path, 1, "labels (i32 N, i32 1, N u32 label words)", words));
+  if (words.empty()) { bang_set_error("BANG_LABEL_FILE %s: the file holds 0 labels for an index of N = %u nodes", path, e->N); return BANG_ERR_ARG; }
+  const int rc = set_labels(e, words.data(), words.size(), "BANG_LABEL_FILE");
+  if (rc != BANG_OK) {
+    const std::string why = bang_last_error();
+    bang_set_error("BANG_LABEL_FILE %s: %s", path, why.c_str());
+  }
+  return rc;
+}
+
+static void drop_query_filters(bang_engine* e) {
+  dfree(e->d_qfilters); dfree(e->d_matched);
+  e->n_qfilters = 0; e->n_filtered = 0; e->qfilters_from_file = false;
+}
+
+extern "C" int bang_set_query_filters_e(bang_engine_t* e, const uint32_t* any, const uint32_t* all, int nq) {
+  if (!e) return BANG_ERR_ARG;
+  const char* what = "bang_set_query_filters";
+  if (!e->allocated) { bang_set_error("%s: the filters of a batch live in its allocation: call bang_alloc first", what); return BANG_ERR_ARG; }
+  if (nq < 0 || nq > e->Qcap) { bang_set_error("%s: %d filters exceed the allocation of %d queries", what, nq, e->Qcap); return BANG_ERR_ARG; }
+  if (nq == 0) { (void)hipSetDevice(e->device); drop_query_filters(e); return BANG_OK; }
+  if (!any || !all) { bang_set_error("%s: any / all is null", what); return BANG_ERR_ARG; }
+  if (!e->d_labels) { bang_set_error("%s: no labels are set (bang_set_labels_e or BANG_LABEL_FILE, before bang_alloc)", what); return BANG_ERR_UNSUPPORTED; }
+  // the forms without a label-filter kernel are refused: there is no unfiltered fallback
+  const bool dev_graph = (e->graph_mode == BANG_GRAPH_DEVICE);
+  if (!e->search_exact) {
+    bang_set_error("%s: filters on labels need option distance = 1 (exact): the PQ walks have no exact distance when a node is evaluated", what);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  if (e->beam > 1) { bang_set_error("%s: filters on labels are not available with option beam = %d: the beam kernel keeps no result list", what, e->beam); return BANG_ERR_UNSUPPORTED; }
+  if (e->vecs_f16 && !dev_graph) { bang_set_error("%s: filters on labels are not available with vectors_fp16 = 1: the label-filter kernel reads float / 8-bit rows", what); return BANG_ERR_UNSUPPORTED; }
+  if (!bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e), 0)) {
+    bang_set_error("%s: filters on labels are not available on the wide vector layouts (dtype %d, D = %u): 8-bit vectors need D / 16 a power of two, D <= 256",
+                   what, e->dtype, e->D);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  BANG_TRY(ensure_device(e));
+  std::vector<uint32_t> rows((size_t)nq * 2);
+  uint64_t filtered = 0;
+  for (int i = 0; i < nq; ++i) { rows[2 * (size_t)i] = any[i]; rows[2 * (size_t)i + 1] = all[i]; filtered += (any[i] | all[i]) != 0u; }
+  if (!e->d_qfilters) BANG_TRY(dmalloc(&e->d_qfilters, (size_t)e->Qcap * 2));
+  if (!e->d_matched) BANG_TRY(dmalloc(&e->d_matched, (size_t)e->Qcap));
+  const hipError_t err = hipMemcpy(e->d_qfilters, rows.data(), rows.size() * 4, hipMemcpyHostToDevice);
+  if (err != hipSuccess) { drop_query_filters(e); HIP_TRY(err); }
+  e->n_qfilters = (uint32_t)nq;
+  e->n_filtered = filtered;
+  e->qfilters_from_file = false;
+  return BANG_OK;
+}
+
+extern "C" int bang_clear_query_filters_e(bang_engine_t* e) {
+  if (!e) return BANG_ERR_ARG;
+  if (e->allocated) (void)hipSetDevice(e->device);
+  drop_query_filters(e);
+  return BANG_OK;
+}
+
+// BANG_QUERY_FILTER_FILE, for the bang.h class and the CLI (bang_internal.h; called by BANGSearch<T>::bang_query): row i of the file is the filter of
+// query i of the batch about to run.  The file is read once per allocation (bang_free forgets it) and its rows go to HBM when the first batch
+// runs or a batch of another size follows; a batch of the size the filters already have costs nothing here
+extern "C" int bang_apply_query_filter_file_e(bang_engine_t* e, int nq) {
+  if (!e) return BANG_ERR_ARG;
+  const char* path = env_str("BANG_QUERY_FILTER_FILE");
+  if (!path) return BANG_OK;
+  if (e->qfilters_from_file && nq > 0 && e->n_qfilters == (uint32_t)nq) return BANG_OK;
+  if (e->qfilter_file_rows.empty()) BANG_TRY(read_u32_bin("BANG_QUERY_FILTER_FILE", path, 2, "filters (i32 Q, i32 2, Q x {any, all} u32)", e->qfilter_file_rows));
+  const std::vector<uint32_t>& words = e->qfilter_file_rows;
+  if (nq <= 0 || words.size() / 2 < (size_t)nq) {
+    bang_set_error("BANG_QUERY_FILTER_FILE %s: the file holds %zu filters, the batch has %d queries", path, words.size() / 2, nq);
+    return BANG_ERR_ARG;
+  }
+  std::vector<uint32_t> any((size_t)nq), all((size_t)nq);
+  for (int i = 0; i < nq; ++i) { any[(size_t)i] = words[2 * (size_t)i]; all[(size_t)i] = words[2 * (size_t)i + 1]; }
+  const int rc = bang_set_query_filters_e(e, any.data(), all.data(), nq);
+  if (rc != BANG_OK) {
+    const std::string why = bang_last_error();
+    bang_set_error("BANG_QUERY_FILTER_FILE %s: %s", path, why.c_str());
+  } else e->qfilters_from_file = true;
+  return rc;
+}
+
+extern "C" int bang_get_matched_counts(bang_engine_t* e, uint32_t* out, uint32_t num_queries) {
+  if (!e || !out) return BANG_ERR_ARG;
+  if (!e->allocated || e->Qcur <= 0 || e->stat_label_launches == 0 || !e->d_matched) {
+    bang_set_error("bang_get_matched_counts: the last query on this allocation did not run with filters on labels");
+    return BANG_ERR_ARG;
+  }
+  if (num_queries > (uint32_t)e->Qcur) { bang_set_error("bang_get_matched_counts: %u counts asked for, the last batch had %d queries", num_queries, e->Qcur); return BANG_ERR_ARG; }
+  HIP_TRY(hipMemcpy(out, e->d_matched, (size_t)num_queries * 4, hipMemcpyDeviceToHost));
+  return BANG_OK;
+}
+
 static int finish_load(bang_engine* e, int rc) {
   if (rc == BANG_OK) rc = load_exclude_file(e);
-  if (rc != BANG_OK) { drop_excluded(e); unload_index(e); }
+  if (rc == BANG_OK) rc = load_label_file(e);
+  if (rc != BANG_OK) { drop_excluded(e); drop_labels(e); unload_index(e); }
   return rc;
 }
 
@@ -126,6 +261,7 @@ extern "C" int bang_destroy(bang_engine_t* e) {
   if (!e) return BANG_OK;
   if (e->allocated) free_batch(e);
   drop_excluded(e);
+  drop_labels(e);
   if (e->loaded) unload_index(e);
   delete e;
   return BANG_OK;
@@ -288,6 +424,10 @@ extern "C" int bang_query_dev_e(bang_engine_t* e, const void* h_queries, int Q, 
 static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* h_ids, float* h_dists, uint64_t* d_ids_user, float* d_dists_user) {
   if (!e->allocated || !e->inited) { bang_set_error("bang_query: bang_alloc + bang_init must precede every query"); return BANG_ERR_ARG; }
   if (Q <= 0 || Q > e->Qcap) { bang_set_error("bang_query: numQueries %d exceeds allocation %d", Q, e->Qcap); return BANG_ERR_ARG; }
+  if (e->n_qfilters != 0 && (uint32_t)Q != e->n_qfilters) {
+    bang_set_error("bang_query: a batch of %d queries, but the filters were set for %u (bang_set_query_filters_e; bang_clear_query_filters_e drops them)", Q, e->n_qfilters);
+    return BANG_ERR_ARG;
+  }
   e->inited = false;   // state is consumed
   e->Qcur = Q;
   // the calling thread is lane 0's walker: it joins the GPU's NUMA node for the duration of the query
@@ -353,6 +493,9 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   }
   e->stat_exclude_launches = 0;
   for (auto& lp : e->lanes) e->stat_exclude_launches += lp->exclude_launches;
+  e->stat_label_launches = 0;
+  for (auto& lp : e->lanes) e->stat_label_launches += lp->label_launches;
+  e->stat_filtered_queries = e->stat_label_launches != 0 ? e->n_filtered : 0;
   s.persistent = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
   s.vectors_on_device = e->vec_on_device ? 1 : 0;
   s.graph_mode = (uint64_t)e->graph_mode;
@@ -476,6 +619,15 @@ extern "C" int bang_get_stats_ext2(bang_engine_t* e, bang_stats_ext2* out) {
   return BANG_OK;
 }
 
+extern "C" int bang_get_stats_ext3(bang_engine_t* e, bang_stats_ext3* out) {
+  if (!e || !out) return BANG_ERR_ARG;
+  BANG_TRY(bang_get_stats_ext2(e, &out->ext2));
+  out->labelled = e->d_labels ? (uint64_t)e->N : 0;
+  out->filtered_queries = e->stat_filtered_queries;
+  out->label_launches = e->stat_label_launches;
+  return BANG_OK;
+}
+
 extern "C" int bang_get_query_counters(bang_engine_t* e, uint32_t* dist_evals, uint32_t* fetched, uint32_t* candidates, uint32_t* iterations) {
   if (!e) return BANG_ERR_ARG;
   if (!e->allocated || e->Qcur <= 0) { bang_set_error("bang_get_query_counters: no query has run on this allocation"); return BANG_ERR_ARG; }
@@ -516,7 +668,7 @@ extern "C" int bang_free_e(bang_engine_t* e) {
 extern "C" int bang_unload_e(bang_engine_t* e) {
   if (!e) return BANG_ERR_ARG;
   if (e->allocated) free_batch(e);
-  if (e->loaded) { (void)hipSetDevice(e->device); drop_excluded(e); unload_index(e); }
+  if (e->loaded) { (void)hipSetDevice(e->device); drop_excluded(e); drop_labels(e); unload_index(e); }
   return BANG_OK;
 }
 

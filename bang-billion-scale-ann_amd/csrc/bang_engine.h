@@ -95,6 +95,7 @@ struct Lane {
   uint32_t iterations = 0;
   uint64_t front_launches = 0;
   uint64_t exclude_launches = 0;      // bang_k_cand_live / bang_k_worklist_pick launches of the last run
+  uint64_t label_launches = 0;        // bang_k_search_exact_labels launches of the last run
   double walker_ms = 0, front_ms = 0, back_ms = 0, rerank_ms = 0, sync_ms = 0, enqueue_ms = 0;
 };
 
@@ -304,6 +305,16 @@ struct bang_engine {
   uint64_t* d_wl_ids_full = nullptr;   // distance = 1: [Q][L] the exact kernel's results at rr_k = L (the whole final worklist) ...
   float* d_wl_dists_full = nullptr;    // ... and [L][Q] their distances; bang_k_worklist_pick takes the first k live entries from there
   uint64_t stat_exclude_launches = 0;  // bang_stats_ext2.exclude_launches of the last bang_query
+  // labels and per-query filters (bang_set_labels_e / bang_set_query_filters_e): the label table lives from load to unload, the
+  // filters and the matched counts from bang_set_query_filters_e to bang_free
+  uint32_t* d_labels = nullptr;        // [N] one label word per node; NULL = no table
+  uint32_t* d_qfilters = nullptr;      // [Qcap][2] {any, all}
+  uint32_t* d_matched = nullptr;       // [Qcap] matching survivors offered to each query's result list (bang_get_matched_counts)
+  uint32_t n_qfilters = 0;             // queries the filters were set for; 0 = no filters: today's launches
+  uint64_t n_filtered = 0;             // ... of which any | all != 0
+  std::vector<uint32_t> qfilter_file_rows;   // BANG_QUERY_FILTER_FILE as read for this allocation ({any, all} per row); empty = not read yet
+  bool qfilters_from_file = false;     // the filters in HBM are the file's first n_qfilters rows
+  uint64_t stat_filtered_queries = 0, stat_label_launches = 0;   // bang_stats_ext3 of the last bang_query
 };
 
 // bang_search.hip, part 2 (semantics = 1): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride

@@ -75,6 +75,13 @@ int bang_k_search_exact_pull_f16(const bang_search_params* p, void* stream);
 // the pulled-rows instances of the beam form (bang_search_beam.hip built with BANG_EXACT_PULL as bang_search_beam_pull.o), handed
 // bang_k_search_exact_beam's checked arguments
 int bang_k_search_exact_beam_pull(const bang_search_params* p, uint32_t beam, void* stream);
+// the label-filter instances of the exact-distance search kernel (the same source built with BANG_EXACT_LABELS as bang_search_exact_labels.o and, with
+// BANG_EXACT_PULL, bang_search_exact_labels_pull.o), handed bang_k_search_exact_labels' checked arguments
+int bang_k_search_exact_labels_hbm(const bang_search_params* p, const bang_label_filter* f, void* stream);
+int bang_k_search_exact_labels_pull(const bang_search_params* p, const bang_label_filter* f, void* stream);
+// BANG_QUERY_FILTER_FILE (bang_cabi.cpp), for the bang.h class alone: applies the file's first num_queries rows as the filters of the batch about to
+// run (bang_set_query_filters_e); no-op without the variable.  The file is read once per allocation
+int bang_apply_query_filter_file_e(bang_engine_t* e, int num_queries);
 
 #ifdef __cplusplus
 }

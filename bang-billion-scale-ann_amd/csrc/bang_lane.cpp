@@ -79,7 +79,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   const uint32_t cap_iter = (uint32_t)e->L + (e->search_inmem ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS) - 1;   // :950 (semantics = 1: L + 119)
   if (ln.kt_used) { (void)hipMemset(ln.d_ktime, 0, ln.kt_used * KT_WGS * 16); ln.kt_used = 0; }   // stats not collected
   if (e->h_fin.size() >= (size_t)ln.q0 + ln.nq) memset(e->h_fin.data() + ln.q0, 0, ln.nq);
-  ln.h2d_bytes.store(0); ln.iterations = 0; ln.front_launches = 0; ln.exclude_launches = 0; ln.walker_ms = 0; ln.sync_ms = 0; ln.enqueue_ms = 0;
+  ln.h2d_bytes.store(0); ln.iterations = 0; ln.front_launches = 0; ln.exclude_launches = 0; ln.label_launches = 0; ln.walker_ms = 0; ln.sync_ms = 0; ln.enqueue_ms = 0;
   auto t_enq = Clock::now();
 #define ENQ_BEGIN() (t_enq = Clock::now())
 #define ENQ_END() (ln.enqueue_ms += ms_since(t_enq))
@@ -194,7 +194,10 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     }
     uint64_t* pick_ids = sp.rr_ids_out;                               // (where the query's k results belong)
     float* pick_dists = sp.rr_dists_out;
-    if (masked) {                                                     // excluded ids: the whole final worklist, [Q][L] / [L][Q]; the pick follows
+    // per-query label filters (bang_set_query_filters_e): the kernel collects the results itself, from every node the walk evaluates,
+    // and tests the exclusion bitmap on the way -- no pick behind it
+    const bool filtered = e->n_qfilters != 0;
+    if (masked && !filtered) {                                        // excluded ids: the whole final worklist, [Q][L] / [L][Q]; the pick follows
       sp.rr_k = (uint32_t)e->L; sp.rr_ids_out = e->d_wl_ids_full; sp.rr_dists_out = e->d_wl_dists_full;
     }
     if (results_direct) {                                             // straight into the pinned mirror
@@ -207,9 +210,14 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     sp.max_waves = (uint32_t)std::max(0L, env_long("BANG_SEARCH_MAX_WAVES", 0));
     e->rerank_fused = false;
     ENQ_BEGIN();
-    if (e->beam > 1) BANG_TRY(bang_k_search_exact_beam(&sp, (uint32_t)e->beam, ln.s_main));   // up to beam parents per iteration (bang_search_beam.hip)
+    if (filtered) {
+      bang_label_filter lf;
+      lf.d_labels = e->d_labels; lf.d_filters = e->d_qfilters; lf.d_excluded = masked ? e->d_excl : nullptr; lf.d_matched = e->d_matched;
+      BANG_TRY(bang_k_search_exact_labels(&sp, &lf, ln.s_main));
+      ++ln.label_launches;
+    } else if (e->beam > 1) BANG_TRY(bang_k_search_exact_beam(&sp, (uint32_t)e->beam, ln.s_main));   // up to beam parents per iteration (bang_search_beam.hip)
     else BANG_TRY(bang_k_search_exact(&sp, ln.s_main));
-    if (masked) {
+    if (masked && !filtered) {
       BANG_TRY(bang_k_worklist_pick(e->d_wl_ids_full, e->d_wl_dists_full, (uint32_t)e->L, ln.q0, ln.nq, (uint32_t)Q, e->d_excl, e->N, (uint32_t)e->k,
                                     pick_ids, pick_dists, ln.s_main));
       ++ln.exclude_launches;

@@ -106,6 +106,8 @@ static const SwitchDef kSwitches[] = {
     {"BANG_STREAM_LOAD", "0 = bang_load maps <prefix>_disk.bin up front instead of streaming it through (pull mode)"},
     {"BANG_GRAPH_MMAP", "0 = private copy of the graph file (transparent huge pages) instead of a shared read-only mapping"},
     {"BANG_EXCLUDE_FILE", ".bin file (i32 count, i32 1, count u32 ids) of node ids no query returns: read as the last step of every load (bang_set_excluded_e)"},
+    {"BANG_LABEL_FILE", ".bin file (i32 N, i32 1, N u32 label words) of the index's labels: read as the last step of every load, behind BANG_EXCLUDE_FILE (bang_set_labels_e)"},
+    {"BANG_QUERY_FILTER_FILE", ".bin file (i32 Q, i32 2, Q x {any, all} u32) of per-query label filters: the bang.h bang_query applies row i to query i of every batch (bang_set_query_filters_e)"},
     {"BANG_SEARCH_MAX_WGS", "search kernel: cap on workgroups (experiments / tests)"},
     {"BANG_SEARCH_MAX_WAVES", "search kernel: cap on waves per workgroup"},
     {"BANG_FILTER_MEM", "visited filters in 1 = uncached / 2 = fine-grained device memory instead of ordinary device memory (experiment, read at bang_alloc)"},

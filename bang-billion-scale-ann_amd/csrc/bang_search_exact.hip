@@ -39,6 +39,13 @@
 //    search_exact_pull_f16_kernel; rr_vec_f16 = 1).  The pulled-rows loop on a float index whose table holds IEEE fp16 rows (engine option
 //    vectors_fp16): D % 8 == 0, D <= 256, the query float in registers as above; a lane reads its survivor's row eight elements per 16-byte load,
 //    four loads in flight, and runs the same ascending chain on float(h[j]) - q[j] (exact_dist_f16).  Everything it adds sits under BANG_EXACT_F16.
+//  * LABEL FILTERS (a sixth and seventh build, -DBANG_EXACT_LABELS=1 as bang_search_exact_labels.o and -- with BANG_EXACT_PULL --
+//    bang_search_exact_labels_pull.o; kernels search_exact_labels_kernel / search_exact_labels_pull_kernel; the narrow layouts only; entry
+//    bang_k_search_exact_labels).  The same walk, bit for bit; beside its worklist a wave keeps a second sorted list of capacity L in LDS, the RESULT
+//    LIST.  Every survivor carries a 32-bit label word (d_labels[id]) and every query two words {any, all}; in every iteration whose survivors are
+//    merged into the worklist, those that match -- and are not in the exclusion bitmap -- are compacted in input order, with the distance bits the
+//    walk computed, and go through the same sort_and_merge into the result list.  The results are the first k entries of that list
+//    (CANON 18).  Everything it adds sits under BANG_EXACT_LABELS.
 //
 // Reference line numbers: the reference's BANG_Base/bang_search.cu unless a file is named.
 
@@ -58,6 +65,9 @@ struct ExactArgs {
   bang_search_params p;
   uint32_t wave_words;               // LDS words per wave: worklist + scratch
   uint32_t wl_words;                 // LDS words of the worklist (2L + ceil(L/4), rounded to 4)
+#ifdef BANG_EXACT_LABELS
+  bang_label_filter f;               // labels, the batch's filters, the exclusion bitmap, the matched counts
+#endif
 };
 
 static __host__ __device__ inline uint32_t exact_wl_words(uint32_t L) { return (2u * L + (L + 3u) / 4u + 3u) & ~3u; }
@@ -189,6 +199,9 @@ __device__ __forceinline__ void exact_dist_f16(const uint8_t GAS* tab, uint64_t 
 #endif
 
 #ifdef BANG_EXACT_WIDE
+#ifdef BANG_EXACT_LABELS
+#error "BANG_EXACT_LABELS builds the narrow instances only"
+#endif
 // ---------------------------------------------------------------------------------------------------------------------
 // wide layouts: rows fetched cooperatively through an LDS tile (one per wave: 64 rows x 64 bytes)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -305,7 +318,16 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
 // wave: 12 waves per CU, no scratch (bang_search_exact_wide_geometry reads both figures off the instance)
 #define EXACT_MAX_THREADS(DT) ((DT) == BANG_F32 ? 768 : 1024)
 #else
+#if defined(BANG_EXACT_LABELS)
 #if defined(BANG_EXACT_F16)
+#error "BANG_EXACT_LABELS builds the narrow instances on float / 8-bit rows only"
+#endif
+#if defined(BANG_EXACT_PULL)
+#define EXACT_KERNEL search_exact_labels_pull_kernel
+#else
+#define EXACT_KERNEL search_exact_labels_kernel
+#endif
+#elif defined(BANG_EXACT_F16)
 #define EXACT_KERNEL search_exact_pull_f16_kernel
 #elif defined(BANG_EXACT_PULL)
 #define EXACT_KERNEL search_exact_pull_kernel
@@ -351,12 +373,25 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
   const uint64_t entry_len = p.entry_len;
 #endif
   uint32_t* wbase = xlds + (size_t)wave * a.wave_words;
+#ifdef BANG_EXACT_LABELS
+  uint32_t* scratch = wbase + 2u * a.wl_words;                    // [worklist][result list][scratch]
+#else
   uint32_t* scratch = wbase + a.wl_words;
+#endif
   WaveLds s;
   s.wd = (float*)wbase; s.wi = wbase + L; s.wv = (uint8_t*)(wbase + 2 * L);
   s.sd = (float*)scratch; s.ti = scratch; s.td = (float*)(scratch + 72);
   float* sdist = (float*)scratch;                 // the survivors' distances (dead before the sort writes sd)
   uint32_t* sc = scratch + 72;                    // the survivors' ids, in input order (== td: dead before the sort)
+#ifdef BANG_EXACT_LABELS
+  // the result list: a second sorted list of capacity L behind the worklist; it sorts and merges through the same scratch words, after the worklist's
+  // merge is done (the survivors' ids and distances are in registers by then).  Its visited flags are written and never read.
+  WaveLds rl;
+  rl.wd = (float*)(wbase + a.wl_words); rl.wi = wbase + a.wl_words + L; rl.wv = (uint8_t*)(wbase + a.wl_words + 2 * L);
+  rl.sd = s.sd; rl.ti = s.ti; rl.td = s.td;
+  const uint32_t GAS* labels = (const uint32_t GAS*)a.f.d_labels;
+  const uint32_t GAS* excluded = (const uint32_t GAS*)a.f.d_excluded;    // or null
+#endif
   if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
   const uint32_t total_waves = gridDim.x * nwaves;
   const uint32_t gw = blockIdx.x * nwaves + wave;
@@ -406,6 +441,11 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 
     // ---------------- per-query state (bang_init :440-489): candidate log = [MEDOID], seed list [MEDOID, adj(MEDOID)...]
     uint32_t iter = 1, w_n = 0, cc = 1, mark = 0x01010101u, evals = 0, fetched = 0;
+#ifdef BANG_EXACT_LABELS
+    const uint32_t f_any = uni(((const uint32_t GAS*)a.f.d_filters)[2u * qabs]), f_all = uni(((const uint32_t GAS*)a.f.d_filters)[2u * qabs + 1u]);
+    uint32_t r_n = 0, matched = 0;
+    float r_tail = 0.0f;                          // the result list's last distance (read while r_n > 0 only)
+#endif
     WlHead head;
     head.found = false; head.idx = 0; head.id = 0; head.d = 0.0f; head.tail = 0.0f;
     if (lane == 0) p.d_cand_ids[(size_t)q * cand_stride] = medoid;
@@ -472,6 +512,13 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       const uint32_t sid0 = ((uint32_t)lane < n) ? sc[lane] : 0u;
       const uint32_t sid1 = (lane == 0 && n > 64) ? sc[64] : 0u;
       evals += n;
+#ifdef BANG_EXACT_LABELS
+      // the survivors' label words, and their words of the exclusion bitmap: requested here, so that they travel with the vectors (every survivor id
+      // is < n_nodes: the check above, and bang_k_search_exact_labels refuses n_nodes == 0)
+      uint32_t lab0 = 0, lab1 = 0, ex0 = 0, ex1 = 0;
+      if ((uint32_t)lane < n) { lab0 = labels[sid0]; if (excluded) ex0 = excluded[sid0 >> 5]; }
+      if (lane == 0 && n > 64) { lab1 = labels[sid1]; if (excluded) ex1 = excluded[sid1 >> 5]; }
+#endif
 
       // ---------------- exact distances (CANON 10: replaces K2) ----------------
       if (n > 0) {
@@ -557,6 +604,30 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 
       // ---------------- K3a + K3b: sort the survivors, merge them into the worklist (not at the cap: CANON 6) ----------------
       if (n > 0 && iter < cap_iter) w_n = sort_and_merge(s, n, d0, sid0, d1, sid1, iter, w_n, L, medoid, mark, head.tail, lane);
+#ifdef BANG_EXACT_LABELS
+      // ---------------- CANON 18: the matching survivors of a merged iteration, in input order, go through the same K3a + K3b into the result list
+      if (n > 0 && iter < cap_iter) {
+        const bool mt0 = (uint32_t)lane < n && (f_any == 0u || (lab0 & f_any) != 0u) && (lab0 & f_all) == f_all && ((ex0 >> (sid0 & 31u)) & 1u) == 0u;
+        const bool mt1 = lane == 0 && n > 64 && (f_any == 0u || (lab1 & f_any) != 0u) && (lab1 & f_all) == f_all && ((ex1 >> (sid1 & 31u)) & 1u) == 0u;
+        const uint64_t mm0 = __ballot(mt0), mm1 = __ballot(mt1);
+        const uint32_t nm0 = (uint32_t)__popcll(mm0), nm = nm0 + (uint32_t)__popcll(mm1);
+        matched += nm;
+        if (nm > 0) {                                             // (uniform)
+          // (the worklist's merge has left the scratch words: its last LDS access is behind a wave_sync)
+          if (mt0) { const uint32_t at = lanes_below(mm0); sdist[at] = d0; sc[at] = sid0; }
+          if (mt1) { sdist[nm0] = d1; sc[nm0] = sid1; }
+          wave_sync();
+          const float cd0 = ((uint32_t)lane < nm) ? sdist[lane] : BIG_DIST;
+          const uint32_t ci0 = ((uint32_t)lane < nm) ? sc[lane] : 0u;
+          const float cd1 = (lane == 0 && nm > 64) ? sdist[64] : BIG_DIST;
+          const uint32_t ci1 = (lane == 0 && nm > 64) ? sc[64] : 0u;
+          wave_sync();
+          // an empty list takes the iteration-1 path (the first min(nm, L) sorted entries); r_tail is the list's own last distance
+          r_n = sort_and_merge(rl, nm, cd0, ci0, cd1, ci1, r_n == 0u ? 1u : 2u, r_n, L, medoid, mark, r_tail, lane);
+          r_tail = __uint_as_float(uni(__float_as_uint(rl.wd[r_n - 1u])));     // (nm > 0: r_n >= 1)
+        }
+      }
+#endif
 
       // a query is active while it has a parent or unmerged survivors (CANON 4); the loop ends at the cap (:950-956)
       if ((!found && n == 0) || iter == cap_iter) break;
@@ -574,11 +645,20 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
     const uint32_t k = p.rr_k, Qt = p.rr_Q_total;
     uint64_t GAS* ids_out = (uint64_t GAS*)p.rr_ids_out;
     float GAS* dists_out = (float GAS*)p.rr_dists_out;
+#ifdef BANG_EXACT_LABELS
+    if (lane == 0 && a.f.d_matched) ((uint32_t GAS*)a.f.d_matched)[qabs] = matched;
+    for (uint32_t r = (uint32_t)lane; r < k; r += WAVE) {         // CANON 18: the result list where the loop below reads the worklist
+      const bool have = r < r_n;
+      ids_out[qabs * k + r] = have ? (uint64_t)rl.wi[r] : ~0ull;
+      dists_out[(size_t)r * Qt + qabs] = have ? rl.wd[r] : BIG_DIST;
+    }
+#else
     for (uint32_t r = (uint32_t)lane; r < k; r += WAVE) {
       const bool have = r < w_n;                                  // a short worklist is padded (CANON 8)
       ids_out[qabs * k + r] = have ? (uint64_t)s.wi[r] : ~0ull;                     // [Q][k] u64
       dists_out[(size_t)r * Qt + qabs] = have ? s.wd[r] : BIG_DIST;                 // [rank][Q]
     }
+#endif
     wave_sync();                                                  // (the worklist is read before the next query overwrites it)
   }
   if (p.d_ktime) {
@@ -599,7 +679,11 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 #endif
 #else
 #define EXACT_EXTRA_WORDS 0u
-#if defined(BANG_EXACT_F16)
+#if defined(BANG_EXACT_LABELS) && EXACT_PULL
+#define EXACT_GEOMETRY bang_search_exact_labels_pull_geometry
+#elif defined(BANG_EXACT_LABELS)
+#define EXACT_GEOMETRY bang_search_exact_labels_geometry
+#elif defined(BANG_EXACT_F16)
 #define EXACT_GEOMETRY bang_search_exact_pull_f16_geometry
 #elif EXACT_PULL
 #define EXACT_GEOMETRY bang_search_exact_pull_geometry
@@ -617,13 +701,20 @@ static const void* exact_instance(int dtype) {
   return nullptr;
 }
 
+#ifdef BANG_EXACT_LABELS
+// worklist + result list + scratch: 2 (2L + L/4) + 144 words per wave -- 16 waves per CU up to L = 512
+static uint32_t exact_wave_bytes(uint32_t L) { return (2u * exact_wl_words(L) + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS) * 4u; }
+#else
 static uint32_t exact_wave_bytes(uint32_t L) { return (exact_wl_words(L) + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS) * 4u; }
+#endif
 
 // Waves per CU: what the instance's registers allow (512 per SIMD lane, allocated in granules of 8, four SIMDs, at most 8 waves per SIMD),
 // what 160 KB of LDS hold (2L + L/4 + 144 words per wave; the wide instances 1024 more), at most 32.  The three narrow instances compile to
 // 97-98 VGPRs and no scratch (the merge of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves
 // per SIMD, 16 per CU -- one workgroup of 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  The wide instances (at most 128
-// VGPRs, no scratch: DESIGN.md section 4.6) run 16 waves per CU as well, up to L = 704.  A batch of fewer than 16 queries per CU is spread
+// VGPRs, no scratch: DESIGN.md section 4.6) run 16 waves per CU as well, up to L = 704.  The label-filter builds (BANG_EXACT_LABELS: this function
+// as bang_search_exact_labels_geometry / _pull_geometry) hold a second list per wave -- 2 (2L + L/4) + 144 words -- and compile to 114-118 VGPRs, no
+// scratch: 120 allocated, 16 waves per CU again, whose lists fit LDS up to L = 512.  A batch of fewer than 16 queries per CU is spread
 // over all CUs with fewer waves each (a wave's iteration is latency bound, as in bang_search_geometry).  The pulled-rows builds: 99-100 VGPRs
 // narrow, 108-109 / 134 wide, no scratch -- the same waves per CU, read off the pulled instance.
 extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
@@ -670,14 +761,23 @@ extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wg
 }
 
 // one launch of this translation unit's instances (the arguments are checked: bang_k_search_exact)
+#ifdef BANG_EXACT_LABELS
+static int exact_launch(const bang_search_params* p, const bang_label_filter* f, void* stream) {
+#else
 static int exact_launch(const bang_search_params* p, void* stream) {
+#endif
   uint32_t grid_n = 0, waves = 0;
   const int rc = EXACT_GEOMETRY((int)p->rr_dtype, p->L, p->Q, p->max_wgs, p->max_waves, &grid_n, &waves);
   if (rc != BANG_OK) return rc;
   ExactArgs a;
   a.p = *p;
   a.wl_words = exact_wl_words(p->L);
+#ifdef BANG_EXACT_LABELS
+  a.wave_words = 2u * a.wl_words + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS;
+  a.f = *f;
+#else
   a.wave_words = a.wl_words + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS;
+#endif
   const size_t lds = (size_t)waves * a.wave_words * 4u;
   const void* k = exact_instance((int)p->rr_dtype);
   static bool attr_done[3][BANG_MAX_DEVICES] = {};
@@ -697,7 +797,19 @@ static int exact_launch(const bang_search_params* p, void* stream) {
   return BANG_OK;
 }
 
-#if defined(BANG_EXACT_F16)
+#if defined(BANG_EXACT_LABELS)
+// the label-filter instances, called by bang_k_search_exact_labels with its arguments checked: graph entries in HBM (row_layout 0) / pulled rows (1)
+#if EXACT_PULL
+extern "C" int bang_k_search_exact_labels_pull(const bang_search_params* p, const bang_label_filter* f, void* stream) {
+  if (!p || !f || p->row_layout != 1u || !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return BANG_ERR_ARG;
+#else
+extern "C" int bang_k_search_exact_labels_hbm(const bang_search_params* p, const bang_label_filter* f, void* stream) {
+  if (!p || !f || p->row_layout != 0u || !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->entry_len, 0)) return BANG_ERR_ARG;
+#endif
+  if (!f->d_labels || !f->d_filters || p->n_nodes == 0u) return BANG_ERR_ARG;
+  return exact_launch(p, f, stream);
+}
+#elif defined(BANG_EXACT_F16)
 // the pulled-rows instance on an fp16 vector table, called by bang_k_search_exact with its arguments checked
 extern "C" int bang_k_search_exact_pull_f16(const bang_search_params* p, void* stream) {
   if (!p || p->row_layout != 1u || p->rr_vec_f16 != 1u || p->rr_dtype != BANG_F32 || p->rr_D % 8u != 0u || p->rr_D > 256u || (p->rr_vec_stride & 3u) ||
@@ -732,9 +844,8 @@ extern "C" int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry
   return 0;
 }
 
-extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
-  if (!p) return BANG_ERR_ARG;
-  if (p->Q == 0) return BANG_OK;
+// every check of a launch's arguments, before any HIP call (shared by bang_k_search_exact and bang_k_search_exact_labels)
+static int exact_check(const bang_search_params* p) {
   if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("distance = 1: bad R/L"); return BANG_ERR_ARG; }
   if (p->row_layout > 1u) { bang_set_error("distance = 1: row_layout = %u: the adjacency lists are graph entries in HBM (0) or 256-byte rows (1)", p->row_layout); return BANG_ERR_UNSUPPORTED; }
   if (p->row_layout == 0u && !p->d_graph) { bang_set_error("distance = 1: the exact-distance kernel needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
@@ -771,9 +882,7 @@ extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
     if (p->n_slices > 1u && !p->d_row_slices) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs the slice table d_row_slices", p->n_slices); return BANG_ERR_ARG; }
     if (p->n_slices > 1u && p->slice_rows == 0u) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs slice_rows != 0", p->n_slices); return BANG_ERR_ARG; }
     if (p->n_rows_hbm != 0u && !p->d_rows_hbm) { bang_set_error("distance = 1, row_layout = 1: n_rows_hbm = %u needs d_rows_hbm", p->n_rows_hbm); return BANG_ERR_ARG; }
-    if (p->rr_vec_f16 == 1u) return bang_k_search_exact_pull_f16(p, stream);
-    if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return bang_k_search_exact_pull(p, stream);
-    return bang_k_search_exact_wide_pull(p, stream);
+    return BANG_OK;
   }
   if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
       (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
@@ -781,7 +890,42 @@ extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
                    "D %% 4 == 0; D <= %u; an entry stride divisible by 4", p->rr_dtype, p->rr_D, (unsigned long long)p->entry_len, BANG_EXACT_MAX_D);
     return BANG_ERR_UNSUPPORTED;
   }
+  return BANG_OK;
+}
+
+extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (p->Q == 0) return BANG_OK;
+  const int rc = exact_check(p);
+  if (rc != BANG_OK) return rc;
+  if (p->row_layout == 1u) {
+    if (p->rr_vec_f16 == 1u) return bang_k_search_exact_pull_f16(p, stream);
+    if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return bang_k_search_exact_pull(p, stream);
+    return bang_k_search_exact_wide_pull(p, stream);
+  }
   if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->entry_len, 0)) return exact_launch(p, stream);
   return bang_k_search_exact_wide(p, stream);
+}
+
+// The walk of bang_k_search_exact with per-query label filters (CANON 18): the narrow layouts only, routed on row_layout to the
+// instances of bang_search_exact_labels.o / bang_search_exact_labels_pull.o
+extern "C" int bang_k_search_exact_labels(const bang_search_params* p, const bang_label_filter* f, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (!f) { bang_set_error("distance = 1, labels: the filter arguments f (bang_label_filter) are null"); return BANG_ERR_ARG; }
+  if (!f->d_labels) { bang_set_error("distance = 1, labels: d_labels (one label word per node) is null"); return BANG_ERR_ARG; }
+  if (!f->d_filters) { bang_set_error("distance = 1, labels: d_filters (the queries' {any, all} words) is null"); return BANG_ERR_ARG; }
+  if (p->n_nodes == 0u) { bang_set_error("distance = 1, labels: n_nodes = 0: d_labels and d_excluded are indexed by node id and need the number of nodes"); return BANG_ERR_ARG; }
+  if (p->Q == 0) return BANG_OK;
+  const int rc = exact_check(p);
+  if (rc != BANG_OK) return rc;
+  if (p->rr_vec_f16 == 1u) { bang_set_error("distance = 1, labels: rr_vec_f16 = 1 (fp16 rows) has no label-filter instance"); return BANG_ERR_UNSUPPORTED; }
+  const uint64_t stride = p->row_layout == 1u ? p->rr_vec_stride : p->entry_len;
+  if (!bang_search_can_rerank((int)p->rr_dtype, p->rr_D, stride, 0)) {
+    bang_set_error("distance = 1, labels: the vector layout (dtype %u, rr_D = %u, stride %llu) runs on the wide instances, which have no label-filter form "
+                   "(8-bit vectors need D / 16 a power of two; D <= 256)", p->rr_dtype, p->rr_D, (unsigned long long)stride);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  if (p->row_layout == 1u) return bang_k_search_exact_labels_pull(p, f, stream);
+  return bang_k_search_exact_labels_hbm(p, f, stream);
 }
 #endif

@@ -177,6 +177,33 @@ int bang_free_e(bang_engine_t* e);                                              
  * that every load (bang_load_e, _mem_e, _stream_e, _shared_e) reads as its last step; an unreadable file or an id out of range fails the load. */
 int bang_set_excluded_e(bang_engine_t* e, const uint32_t* ids, uint64_t n);
 int bang_clear_excluded_e(bang_engine_t* e);
+
+/* LABELS AND PER-QUERY FILTERS (DESIGN.md section 2 CANON 18, section 4.13): every point carries a 32-bit label word (up to 32 tags), every query of
+ * a batch two words, `any` and `all`; node x MATCHES when (any == 0 || (labels[x] & any) != 0) && (labels[x] & all) == all (any = all = 0: an
+ * unfiltered query).  A filtered batch runs the exact-distance walk unchanged -- counters and candidate log are those of the same batch without
+ * filters, bit for bit -- and collects each query's results from EVERY node the walk evaluates: the matching survivors of an iteration go through
+ * the worklist's sort + merge rule into a second sorted list of capacity L, whose first k entries are the results (bang_k_search_exact_labels); the
+ * tail behind fewer than k is UINT64_MAX / 3.402823E+38f.  An unfiltered query of a filtered batch returns exactly today's ids and distance bits.  A
+ * node in the engine's exclusion set never enters the list (the kernel tests the bitmap itself; bang_k_worklist_pick is not launched).
+ * bang_set_labels_e REPLACES the table: n must be N ("labels" and both numbers in the message), n = 0 clears it (labels may be NULL then).  Both
+ * calls need a loaded index and are refused while an allocation is live; bang_unload_e drops the table.  An engine with labels and no filters runs
+ * today's launches unchanged.
+ * bang_set_query_filters_e sets the filters of the batches to come, nq of them (row i for query i): valid while an allocation is live, nq <= the
+ * allocated batch size, nq = 0 clears; copied to HBM and kept until replaced, cleared or bang_free_e.  bang_query_e / bang_query_dev_e refuse a
+ * batch whose size differs from nq ("filters" in the message).  Refused at bang_set_query_filters_e, with "labels" in the message, no fallback: no
+ * labels set; distance = 0 (the PQ walks have no exact distance when a node is evaluated); beam > 1; vectors_fp16 = 1; a vector layout of the wide
+ * instances.
+ * bang_get_matched_counts: per query of the last filtered batch, the number of matching survivors offered to its result list -- a caller sees from
+ * it when a filter was too selective for its L.
+ * Environment, for callers of the bang.h class and the bang_search CLI: BANG_LABEL_FILE names a .bin file (i32 N, i32 1, N u32 label words) that
+ * every load reads as its last step, behind BANG_EXCLUDE_FILE, with the same failure behaviour; BANG_QUERY_FILTER_FILE names a .bin file (i32 Q,
+ * i32 2, Q x {any, all}) whose row i the bang.h bang_query applies to query i of every batch (read once per allocation; fewer rows than
+ * queries is an error). */
+int bang_set_labels_e(bang_engine_t* e, const uint32_t* labels, uint64_t n);
+int bang_clear_labels_e(bang_engine_t* e);
+int bang_set_query_filters_e(bang_engine_t* e, const uint32_t* any, const uint32_t* all, int nq);
+int bang_clear_query_filters_e(bang_engine_t* e);
+int bang_get_matched_counts(bang_engine_t* e, uint32_t* out, uint32_t num_queries);
 int bang_unload_e(bang_engine_t* e);                                                        /* bang.h:82 */
 
 /* statistics of the last bang_query_e */
@@ -244,6 +271,14 @@ typedef struct {
   uint64_t exclude_launches;  /* launches of bang_k_cand_live / bang_k_worklist_pick of the last bang_query_e, summed over the lanes (0 with an empty set) */
 } bang_stats_ext2;
 int bang_get_stats_ext2(bang_engine_t* e, bang_stats_ext2* out);
+/* ... and once more for labels and per-query filters (bang_set_labels_e / bang_set_query_filters_e): the earlier structs keep size and offsets */
+typedef struct {
+  bang_stats_ext2 ext2;
+  uint64_t labelled;          /* nodes the engine's label table covers (N), 0 = no table */
+  uint64_t filtered_queries;  /* queries of the last bang_query_e that ran with a filter other than any = all = 0 */
+  uint64_t label_launches;    /* launches of bang_k_search_exact_labels of the last bang_query_e (0 without filters) */
+} bang_stats_ext3;
+int bang_get_stats_ext3(bang_engine_t* e, bang_stats_ext3* out);
 /* Per-query counters of the last bang_query_e (arrays of num_queries words; any pointer may be NULL): PQ distance evaluations,
  * adjacency ids offered to the filter, expanded nodes (candidate-log length) and -- search kernel only, else zeros -- the number
  * of iterations the query ran.  Test hook: the oracle reports the same four numbers per query. */
@@ -612,6 +647,32 @@ int bang_k_cand_live(const uint32_t* d_cand_ids, const uint32_t* d_cand_cnt, uin
  * UINT64_MAX / 3.402823E+38f.  The outputs must not be the inputs. */
 int bang_k_worklist_pick(const uint64_t* d_wl_ids, const float* d_wl_dists, uint32_t L, uint32_t q0, uint32_t nq, uint32_t Q_total,
                          const uint32_t* d_bitmap, uint32_t n_nodes, uint32_t k, uint64_t* d_ids_out, float* d_dists_out, void* stream);
+
+/* LABEL FILTERS on the exact-distance walk (csrc/bang_search_exact.hip built as bang_search_exact_labels.o / bang_search_exact_labels_pull.o; engine:
+ * bang_set_labels_e + bang_set_query_filters_e; DESIGN.md section 2, CANON 18).  Every node carries a 32-bit label word, every query two words:
+ * node x MATCHES query q when (any == 0 || (d_labels[x] & any) != 0) && (d_labels[x] & all) == all; any = all = 0 matches every node.  The walk is
+ * bang_k_search_exact's, bit for bit -- filter, parent, worklist, the L + 49 cap, candidate log, counters.  Beside its worklist a query keeps a
+ * RESULT LIST of capacity L: in every iteration whose survivors are merged into the worklist (not the cap iteration) the matching survivors that
+ * are not in d_excluded are taken in input order, with the distance bits the walk computed, and merged into the result list by the worklist's own
+ * K3a + K3b rule (stable rank sort; a full list takes only entries strictly closer than its last; new before equal old; an empty list takes the
+ * first min(n, L) sorted survivors).  The query's results are the first k entries of that list, padded with UINT64_MAX / 3.402823E+38f; an id that
+ * a row lists twice is in twice, as in the worklist.  d_matched[rr_q0 + q] = the number of matching survivors offered to the list.  An unfiltered
+ * query returns exactly what bang_k_search_exact returns.
+ * bang_search_params is what it is for bang_k_search_exact (no member added or moved); the new arguments travel beside it.  Routed on row_layout to
+ * search_exact_labels_kernel (0) / search_exact_labels_pull_kernel (1).  Every check of bang_k_search_exact is made, before any HIP call; refused in
+ * addition, with the member named: f, d_labels or d_filters null and n_nodes == 0 -- the tables are indexed by node id -- (BANG_ERR_ARG);
+ * rr_vec_f16 = 1 and the layouts of the wide instances, i.e. those bang_search_can_rerank refuses (BANG_ERR_UNSUPPORTED). */
+typedef struct {
+  const uint32_t* d_labels;   /* [n_nodes] */
+  const uint32_t* d_filters;  /* [rr_Q_total][2] {any, all}; row rr_q0 + q is this launch's query q */
+  const uint32_t* d_excluded; /* bitmap as bang_k_worklist_pick reads it, or NULL */
+  uint32_t* d_matched;        /* [rr_Q_total] out, or NULL */
+} bang_label_filter;
+int bang_k_search_exact_labels(const bang_search_params* p, const bang_label_filter* f, void* stream);
+/* grid of a bang_k_search_exact_labels launch, as bang_search_exact_geometry: LDS per wave is 2 (2L + L/4) + 144 words (worklist + result list), the
+ * register count that of the label-filter instance; the second one for the pulled-rows form (row_layout = 1) */
+int bang_search_exact_labels_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+int bang_search_exact_labels_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
