@@ -607,6 +607,21 @@ static inline int num_cus() {
   return cus[dev];
 }
 
+// Launch geometry of a wave-resident kernel (bang_wave_geometry) from the figures of instance k itself: its register count and its launch bound,
+// read once per device into the caller's cache (one WaveKernelAttr per instance; 128 registers / 16 waves where the runtime reports none)
+struct WaveKernelAttr { int regs[BANG_MAX_DEVICES], max_waves_wg[BANG_MAX_DEVICES]; };
+static inline int wave_kernel_geometry(const void* k, WaveKernelAttr& c, uint32_t wave_bytes, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
+                                       uint32_t* workgroups, uint32_t* waves) {
+  const int dev = current_device();
+  if (c.regs[dev] == 0) {
+    hipFuncAttributes at;
+    HIP_TRY(hipFuncGetAttributes(&at, k));
+    c.max_waves_wg[dev] = at.maxThreadsPerBlock >= WAVE ? at.maxThreadsPerBlock / WAVE : 16;
+    c.regs[dev] = at.numRegs > 0 ? at.numRegs : 128;
+  }
+  return bang_wave_geometry((uint32_t)c.regs[dev], (uint32_t)c.max_waves_wg[dev], wave_bytes, (uint32_t)num_cus(), Q, max_wgs, max_waves, workgroups, waves);
+}
+
 // floats of the packed pivot table (multiple of 4: it is staged into LDS with 16-byte copies)
 static inline uint32_t pivot_table_floats(uint32_t psz, uint32_t mp, uint32_t nhi) {
   if (psz == 2 && nhi != 0) return ((nhi * 512u + (mp - nhi) * 256u + 3u) & ~3u) + 4u;

@@ -60,8 +60,23 @@ int bang_num_cus(void);
 int bang_ragged_supported(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t m);
 
 
-// the wide-layout instances of the exact-distance search kernel (bang_search_exact.hip built with BANG_EXACT_WIDE as bang_search_exact_wide.o):
-// bang_k_search_exact hands them the layouts bang_search_can_rerank refuses, its arguments checked; the grid as bang_search_exact_geometry
+#define BANG_WAVE_MAX_LDS (160u * 1024u)   /* LDS of a CU */
+// Launch geometry of the wave-resident search kernels (exact-distance, beam, LUT), pure arithmetic: a kernel of `regs` VGPRs whose launch bound is
+// max_waves_wg waves and whose waves take wave_bytes of LDS each, Q queries on `cus` CUs; max_wgs / max_waves cap the result (0: no cap).
+// BANG_ERR_ARG on a zero or null argument, BANG_ERR_UNSUPPORTED when not one wave fits a CU (no message set: the caller names its kernel)
+int bang_wave_geometry(uint32_t regs, uint32_t max_waves_wg, uint32_t wave_bytes, uint32_t cus, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
+                       uint32_t* workgroups, uint32_t* waves);
+
+// The argument checks of an exact-distance launch, made before any HIP call, for bang_k_search_exact, _labels and _beam; every message opens with
+// `prefix` ("distance = 1", "distance = 1, beam = 4").  In call order: bang_exact_check_args (R/L, row_layout, buffers, iteration cap, k / result
+// rows, rr_vec_f16 > 1), the caller's own rule for rr_vec_f16 = 1, then bang_exact_check_layout (the pulled-rows contract or the graph-entry layout)
+__attribute__((visibility("hidden"))) int bang_exact_check_args(const bang_search_params* p, const char* prefix);
+__attribute__((visibility("hidden"))) int bang_exact_check_layout(const bang_search_params* p, const char* prefix);
+
+// the instances of the exact-distance search kernel, one entry per build of bang_search_exact.hip; bang_k_search_exact hands them its checked
+// arguments.  Graph entries in HBM, the layouts of bang_search_can_rerank (bang_search_exact.o) ...
+int bang_k_search_exact_hbm(const bang_search_params* p, void* stream);
+// ... and the layouts it refuses (the wide instances, BANG_EXACT_WIDE: bang_search_exact_wide.o); the grid as bang_search_exact_geometry
 int bang_k_search_exact_wide(const bang_search_params* p, void* stream);
 int bang_search_exact_wide_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 // the pulled-rows instances of both (row_layout 1; the same source built with BANG_EXACT_PULL as bang_search_exact_pull.o / bang_search_exact_wide_pull.o):

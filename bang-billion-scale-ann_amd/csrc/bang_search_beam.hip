@@ -6,7 +6,7 @@
 //   1. the ids of the <= W rows of an iteration are ALL tested against the filter state at entry (CANON 3), then the bits of those that
 //      passed are set;
 //   2. a survivor of row j whose id also survived in a row i < j is dropped (exact on ids; duplicates inside one row stay);
-//   3. ONE distance call covers every kept survivor (<= 256, the seed list 65) -- the arithmetic of bang_search_exact.hip;
+//   3. ONE distance call covers every kept survivor (<= 256, the seed list 65) -- the routines of bang_search_exact.hip (bang_exact_dist.h);
 //   4. the rows are sorted and merged into the worklist one after the other (sort_and_merge of bang_worklist.h, unchanged, mark = none):
 //      among equal distances a later row's entry stands in front of an earlier row's;
 //   5. the first P = min(W, room in the candidate log, unvisited entries) unvisited worklist entries are marked and logged; P == 0 ends
@@ -27,14 +27,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
 
 #include "bang_c.h"
 #include "bang_internal.h"
 #include "bang_device.h"
 #include "bang_worklist.h"
+#include "bang_exact_dist.h"
 
-#define BEAM_SCRATCH_WORDS 144u      // sd/ti [72] + td [72]: the sort of one row
-#define BEAM_MAX_LDS (160u * 1024u)
 #define BEAM_MAX 4                   // rows per iteration the kernel is compiled for
 #define BEAM_NO_MARK 0xFFFFFFFFu     // the merge marks nothing: parents are taken behind it
 
@@ -46,98 +46,14 @@ struct BeamArgs {
   uint32_t beam;
 };
 
-static __host__ __device__ inline uint32_t beam_wl_words(uint32_t L) { return (2u * L + (L + 3u) / 4u + 3u) & ~3u; }
 static __host__ __device__ inline uint32_t beam_row_words(uint32_t beam) { return 64u * beam + 4u; }
 
 typedef uint32_t u32x4b __attribute__((ext_vector_type(4)));     // 16-byte aligned: ds_read_b128
-
-template <bool SIGNED>
-__device__ __forceinline__ int xdot4(uint32_t a, uint32_t b, int c) {
-  if (SIGNED) return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
-  return (int)__builtin_amdgcn_udot4(a, b, (uint32_t)c, false);
-}
-
-// exact distances of the n survivors (ids in LDS: sid[0, n)) -> dist[0, n) in LDS, 8-bit vectors (exact_dist8 of bang_search_exact.hip).
-// qw: this lane's 16-byte piece of the query (piece lane % G), qq: the sum of its squares.  Every lane of the wave executes.
-template <bool SIGNED>
-__device__ __forceinline__ void beam_dist8(const uint8_t GAS* graph, uint64_t entry_len, uint32_t G, const uint32_t* sid, uint32_t n,
-                                           float* dist, u32x4a qw, int qq, int lane) {
-  constexpr int U = 4;                                            // vector fetches in flight per lane
-  const uint32_t per = 64u / G;                                   // survivors per wave instruction
-  const uint32_t sub = (uint32_t)lane & (G - 1u), slot = (uint32_t)lane / G;
-  for (uint32_t i0 = 0; i0 < n; i0 += per * U) {                  // (uniform)
-    u32x4a v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const uint32_t i = i0 + (uint32_t)u * per + slot;
-      const uint32_t id = sid[i < n ? i : 0u];
-      v[u] = *(const u32x4a GAS*)(graph + (uint64_t)id * entry_len + 16u * sub);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const uint32_t i = i0 + (uint32_t)u * per + slot;
-      int vv = xdot4<SIGNED>(v[u].x, v[u].x, xdot4<SIGNED>(v[u].y, v[u].y, xdot4<SIGNED>(v[u].z, v[u].z, xdot4<SIGNED>(v[u].w, v[u].w, qq))));
-      const int vq = xdot4<SIGNED>(v[u].x, qw.x, xdot4<SIGNED>(v[u].y, qw.y, xdot4<SIGNED>(v[u].z, qw.z, xdot4<SIGNED>(v[u].w, qw.w, 0))));
-      vv -= 2 * vq;
-      for (uint32_t off = 1; off < G; off <<= 1) vv += __shfl_xor(vv, (int)off);
-      if (i < n && sub == 0u) dist[i] = (float)vv;
-    }
-  }
-}
-
-// the same for float vectors (exact_dist_f32 of bang_search_exact.hip): lane i evaluates survivor i0 + i, the ascending fmaf chain over the
-// D dimensions (D % 4 == 0, <= 256), four 16-byte loads in flight; qr[t]: lane l holds query element 64 t + l
-__device__ __forceinline__ void beam_dist_f32(const uint8_t GAS* graph, uint64_t entry_len, uint32_t D, const uint32_t* sid, uint32_t n,
-                                              float* dist, const float (&qr)[4], int lane) {
-  constexpr int RF = 4;                                           // 16-byte loads in flight per lane
-  for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform)
-    const uint32_t i = i0 + (uint32_t)lane;
-    const uint32_t id = sid[i < n ? i : 0u];
-    const uint8_t GAS* v = graph + (uint64_t)id * entry_len;
-    float acc = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint32_t jt = (uint32_t)t * 64u;
-      if (jt >= D) break;                                         // (uniform)
-      const uint32_t dt = D - jt < 64u ? D - jt : 64u;
-      for (uint32_t jl = 0; jl < dt; jl += 4u * RF) {             // (uniform)
-        u32x4a w[RF];
-#pragma unroll
-        for (int u = 0; u < RF; ++u) {
-          const uint32_t j = jl + 4u * (uint32_t)u;
-          w[u] = *(const u32x4a GAS*)(v + 4u * (jt + (j < dt ? j : 0u)));
-        }
-#pragma unroll
-        for (int u = 0; u < RF; ++u) {
-          const uint32_t j = jl + 4u * (uint32_t)u;
-          if (j < dt) {                                           // (uniform)
-            const uint32_t ww[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-              const float qv = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qr[t]), (int)(j + (uint32_t)d)));
-              const float diff = __uint_as_float(ww[d]) - qv;     // orc_exact_dist: vector - query
-              acc = __builtin_fmaf(diff, diff, acc);              // ascending dimension
-            }
-          }
-        }
-      }
-    }
-    if (i < n) dist[i] = acc;
-  }
-}
 
 #ifdef BANG_EXACT_PULL
 #define BEAM_PULL 1
 #define BEAM_KERNEL search_exact_beam_pull_kernel
 #define BEAM_GEOMETRY bang_search_exact_beam_pull_geometry
-// the slice table's entry idx (biased base addresses, 0 = that slice is not there), through the scalar cache
-__device__ __forceinline__ uint64_t slice_base(const uint64_t* tab, uint32_t idx) {
-  uint64_t v;
-  const uint64_t a = (uint64_t)(uintptr_t)tab + 8ull * idx;     // (uniform, but not provably so: made so)
-  const uint64_t at = ((uint64_t)uni((uint32_t)(a >> 32)) << 32) | uni((uint32_t)a);
-  asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(at) : "memory");
-  return v;
-}
 #else
 #define BEAM_PULL 0
 #define BEAM_KERNEL search_exact_beam_kernel
@@ -167,7 +83,7 @@ __global__ __launch_bounds__(1024) void BEAM_KERNEL(const BeamArgs a) {
   WaveLds s;
   s.wd = (float*)wbase; s.wi = wbase + L; s.wv = (uint8_t*)(wbase + 2 * L);
   s.sd = (float*)scratch; s.ti = scratch; s.td = (float*)(scratch + 72);
-  uint32_t* bid = scratch + BEAM_SCRATCH_WORDS;   // the kept survivors' ids, row after row, input order (16-byte aligned)
+  uint32_t* bid = scratch + WAVE_SCRATCH_WORDS;   // the kept survivors' ids, row after row, input order (16-byte aligned)
   float* bdist = (float*)(bid + a.row_words);     // ... and their distances
   uint32_t* psel = scratch;                       // the parents picked by the selection (the sort scratch is dead there)
   if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -299,10 +215,10 @@ __global__ __launch_bounds__(1024) void BEAM_KERNEL(const BeamArgs a) {
       }
       evals += tot;
 
-      // ---------------- step 3: exact distances, one call over every kept survivor
+      // ---------------- step 3: exact distances (bang_exact_dist.h), one call over every kept survivor
       if (tot > 0u) {
-        if (DT == BANG_F32) beam_dist_f32(graph, entry_len, D, bid, tot, bdist, qr, lane);
-        else beam_dist8<DT == BANG_I8>(graph, entry_len, G, bid, tot, bdist, qw, qq, lane);
+        if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, bid, tot, bdist, qr, lane);
+        else exact_dist8<DT == BANG_I8>(graph, entry_len, G, bid, tot, bdist, qw, qq, lane);
       }
       wave_sync();
 
@@ -408,53 +324,18 @@ static const void* beam_instance(int dtype) {
   return nullptr;
 }
 
-static uint32_t beam_wave_bytes(uint32_t L, uint32_t beam) { return (beam_wl_words(L) + BEAM_SCRATCH_WORDS + 2u * beam_row_words(beam)) * 4u; }
+static uint32_t beam_wave_words(uint32_t L, uint32_t beam) { return wave_wl_words(L) + WAVE_SCRATCH_WORDS + 2u * beam_row_words(beam); }
 
-// Waves per CU as bang_search_exact_geometry: what the instance's registers allow (512 per SIMD lane, allocated in granules of 8, four SIMDs,
-// at most 8 waves per SIMD) and what 160 KB of LDS hold -- 2L + L/4 + 144 + 2 (64 beam + 4) words per wave --, at most 32; one workgroup of at
-// most 16 waves; a batch of fewer than a workgroup-full of queries per CU is spread over all CUs with fewer waves each.
+// The grid of a launch (bang_wave_geometry on the instance's own figures); LDS per wave: 2L + L/4 + 144 + 2 (64 beam + 4) words
 extern "C" int BEAM_GEOMETRY(int dtype, uint32_t L, uint32_t beam, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   if (beam == 0 || beam > BEAM_MAX) { bang_set_error("distance = 1: beam = %u is outside [1, %d]", beam, BEAM_MAX); return BANG_ERR_ARG; }
   const void* k = beam_instance(dtype);
   if (!k || L == 0 || L > BANG_MAX_L) { bang_set_error("distance = 1, beam = %u: bad dtype / L", beam); return BANG_ERR_ARG; }
-  static int regs[3][BANG_MAX_DEVICES] = {}, max_waves_wg[3][BANG_MAX_DEVICES] = {};   // per instance and device, read once
-  const int dev = current_device();
-  if (regs[dtype][dev] == 0) {
-    hipFuncAttributes at;
-    HIP_TRY(hipFuncGetAttributes(&at, k));
-    max_waves_wg[dtype][dev] = at.maxThreadsPerBlock >= WAVE ? at.maxThreadsPerBlock / WAVE : 16;
-    regs[dtype][dev] = at.numRegs > 0 ? at.numRegs : 128;
-  }
-  const uint32_t vg = (uint32_t)regs[dtype][dev];
-  const uint32_t alloc = (vg + 7u) & ~7u;
-  uint32_t per_simd = 512u / alloc;
-  if (per_simd > 8u) per_simd = 8u;
-  uint32_t per_cu = 4u * per_simd;
-  const uint32_t by_lds = BEAM_MAX_LDS / beam_wave_bytes(L, beam);
-  if (by_lds < per_cu) per_cu = by_lds;
-  if (per_cu > 32u) per_cu = 32u;
-  if (per_cu == 0) { bang_set_error("distance = 1, beam = %u: one wave's worklist does not fit LDS at L=%u", beam, L); return BANG_ERR_UNSUPPORTED; }
-  uint32_t W = per_cu < 16u ? per_cu : 16u;
-  if (W > (uint32_t)max_waves_wg[dtype][dev]) W = (uint32_t)max_waves_wg[dtype][dev];     // (the instance's launch bound)
-  const uint32_t wgs_per_cu = per_cu / W;
-  if (max_waves && max_waves < W) W = max_waves;
-  const uint32_t cus = (uint32_t)num_cus();
-  uint32_t grid_n;
-  if (Q <= cus * W) {                                             // fewer queries than a wave-full per CU: all CUs, fewer waves each
-    grid_n = Q < cus ? Q : cus;
-    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
-    const uint32_t share = (Q + grid_n - 1) / grid_n;
-    if (share < W) W = share;
-  } else {
-    const uint32_t want = (Q + W - 1) / W;
-    grid_n = cus * wgs_per_cu;
-    if (want < grid_n) grid_n = want;
-    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
-  }
-  *workgroups = grid_n;
-  *waves = W;
-  return BANG_OK;
+  static WaveKernelAttr attr[3];                                  // per instance
+  const int rc = wave_kernel_geometry(k, attr[dtype], beam_wave_words(L, beam) * 4u, Q, max_wgs, max_waves, workgroups, waves);
+  if (rc == BANG_ERR_UNSUPPORTED) bang_set_error("distance = 1, beam = %u: one wave's worklist does not fit LDS at L=%u", beam, L);
+  return rc;
 }
 
 // one launch of this translation unit's instances (the arguments are checked: bang_k_search_exact_beam)
@@ -465,15 +346,15 @@ static int beam_launch(const bang_search_params* p, uint32_t beam, void* stream)
   BeamArgs a;
   a.p = *p;
   a.beam = beam;
-  a.wl_words = beam_wl_words(p->L);
+  a.wl_words = wave_wl_words(p->L);
   a.row_words = beam_row_words(beam);
-  a.wave_words = a.wl_words + BEAM_SCRATCH_WORDS + 2u * a.row_words;
+  a.wave_words = beam_wave_words(p->L, beam);
   const size_t lds = (size_t)waves * a.wave_words * 4u;
   const void* k = beam_instance((int)p->rr_dtype);
   static bool attr_done[3][BANG_MAX_DEVICES] = {};
   const int dev = current_device();
   if (!attr_done[p->rr_dtype][dev]) {
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BEAM_MAX_LDS));
+    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_MAX_LDS));
     attr_done[p->rr_dtype][dev] = true;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -499,52 +380,24 @@ extern "C" int bang_search_exact_beam_supported(int dtype, uint32_t D, uint64_t 
   return bang_search_exact_supported(dtype, D, stride) != 0 && bang_search_can_rerank(dtype, D, stride, 0) != 0 ? 1 : 0;
 }
 
+// the checks of bang_k_search_exact (bang_exact_check_args / _layout), in its order and with its texts behind "distance = 1, beam = W"; what has no
+// beam instance -- an fp16 vector table, the wide layouts -- is refused where bang_k_search_exact looks at it
 extern "C" int bang_k_search_exact_beam(const bang_search_params* p, uint32_t beam, void* stream) {
   if (!p) return BANG_ERR_ARG;
   if (beam == 0 || beam > BEAM_MAX) { bang_set_error("distance = 1: beam = %u is outside [1, %d]", beam, BEAM_MAX); return BANG_ERR_ARG; }
   if (p->Q == 0) return BANG_OK;
-  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("distance = 1, beam = %u: bad R/L", beam); return BANG_ERR_ARG; }
-  if (p->row_layout > 1u) { bang_set_error("distance = 1, beam = %u: row_layout = %u: the adjacency lists are graph entries in HBM (0) or 256-byte rows (1)", beam, p->row_layout); return BANG_ERR_UNSUPPORTED; }
-  if (p->row_layout == 0u && !p->d_graph) { bang_set_error("distance = 1, beam = %u: the kernel needs the graph entries in HBM (d_graph, row_layout = 0)", beam); return BANG_ERR_UNSUPPORTED; }
-  if (!p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt || !p->d_next_query || !p->rr_queries || !p->rr_ids_out || !p->rr_dists_out) {
-    bang_set_error("distance = 1, beam = %u: null buffer", beam); return BANG_ERR_ARG;
-  }
-  if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("distance = 1, beam = %u: bad iteration cap", beam); return BANG_ERR_ARG; }
-  if (p->rr_k == 0 || p->rr_k > p->L || p->rr_Q_total < p->rr_q0 + p->Q) { bang_set_error("distance = 1, beam = %u: bad k / result rows", beam); return BANG_ERR_ARG; }
-  if (p->rr_vec_f16 > 1u) { bang_set_error("distance = 1, beam = %u: rr_vec_f16 = %u (0 = float / 8-bit rows, 1 = fp16 rows)", beam, p->rr_vec_f16); return BANG_ERR_ARG; }
-  if (p->rr_vec_f16 == 1u) { bang_set_error("distance = 1, beam = %u: rr_vec_f16 = 1 (an fp16 vector table) has no beam instance", beam); return BANG_ERR_UNSUPPORTED; }
-  if (p->row_layout == 1u) {
-    // the pulled-rows form: adjacency rows in d_graph (pinned host memory; 4-byte aligned), vectors at rr_vec_base + id * rr_vec_stride
-    if (!p->d_graph || (((uintptr_t)p->d_graph) & 3u)) { bang_set_error("distance = 1, beam = %u, row_layout = 1: d_graph (the 256-byte adjacency rows) is null or not 4-byte aligned", beam); return BANG_ERR_ARG; }
-    if (p->R > 64u) { bang_set_error("distance = 1, beam = %u, row_layout = 1: R = %u, a 256-byte row holds 64 ids", beam, p->R); return BANG_ERR_ARG; }
-    if (!p->rr_vec_base || (((uintptr_t)p->rr_vec_base) & 3u)) { bang_set_error("distance = 1, beam = %u, row_layout = 1: rr_vec_base (the vectors) is null or not 4-byte aligned", beam); return BANG_ERR_ARG; }
-    if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
-      bang_set_error("distance = 1, beam = %u, row_layout = 1: rr_vec_stride = %llu does not describe vectors the kernel evaluates (dtype %u, D = %u): 8-bit vectors "
-                     "need D %% 16 == 0, float vectors D %% 4 == 0; a stride divisible by 4 that holds the vector", beam, (unsigned long long)p->rr_vec_stride,
-                     p->rr_dtype, p->rr_D);
-      return BANG_ERR_ARG;
-    }
-    if (p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u)) { bang_set_error("distance = 1, beam = %u, row_layout = 1: vec_bytes = %u is not rr_D * the element size", beam, p->vec_bytes); return BANG_ERR_ARG; }
-    if (((uintptr_t)p->rr_queries) & 3u) { bang_set_error("distance = 1, beam = %u, row_layout = 1: rr_queries is not 4-byte aligned", beam); return BANG_ERR_ARG; }
-    if (p->n_slices > 1u && !p->d_row_slices) { bang_set_error("distance = 1, beam = %u, row_layout = 1: n_slices = %u needs the slice table d_row_slices", beam, p->n_slices); return BANG_ERR_ARG; }
-    if (p->n_slices > 1u && p->slice_rows == 0u) { bang_set_error("distance = 1, beam = %u, row_layout = 1: n_slices = %u needs slice_rows != 0", beam, p->n_slices); return BANG_ERR_ARG; }
-    if (p->n_rows_hbm != 0u && !p->d_rows_hbm) { bang_set_error("distance = 1, beam = %u, row_layout = 1: n_rows_hbm = %u needs d_rows_hbm", beam, p->n_rows_hbm); return BANG_ERR_ARG; }
-    if (!bang_search_exact_beam_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
-      bang_set_error("distance = 1, beam = %u: the wide vector layouts (dtype %u, D = %u) have no beam instance: 8-bit D / 16 a power of two, D <= 256", beam, p->rr_dtype, p->rr_D);
-      return BANG_ERR_UNSUPPORTED;
-    }
-    return bang_k_search_exact_beam_pull(p, beam, stream);
-  }
-  if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
-      (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
-    bang_set_error("distance = 1, beam = %u: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0, float vectors "
-                   "D %% 4 == 0; an entry stride divisible by 4", beam, p->rr_dtype, p->rr_D, (unsigned long long)p->entry_len);
+  char prefix[32];
+  snprintf(prefix, sizeof prefix, "distance = 1, beam = %u", beam);
+  int rc = bang_exact_check_args(p, prefix);
+  if (rc != BANG_OK) return rc;
+  if (p->rr_vec_f16 == 1u) { bang_set_error("%s: rr_vec_f16 = 1 (an fp16 vector table) has no beam instance", prefix); return BANG_ERR_UNSUPPORTED; }
+  rc = bang_exact_check_layout(p, prefix);
+  if (rc != BANG_OK) return rc;
+  if (!bang_search_exact_beam_supported((int)p->rr_dtype, p->rr_D, p->row_layout == 1u ? p->rr_vec_stride : p->entry_len)) {
+    bang_set_error("%s: the wide vector layouts (dtype %u, D = %u) have no beam instance: 8-bit D / 16 a power of two, D <= 256", prefix, p->rr_dtype, p->rr_D);
     return BANG_ERR_UNSUPPORTED;
   }
-  if (!bang_search_exact_beam_supported((int)p->rr_dtype, p->rr_D, p->entry_len)) {
-    bang_set_error("distance = 1, beam = %u: the wide vector layouts (dtype %u, D = %u) have no beam instance: 8-bit D / 16 a power of two, D <= 256", beam, p->rr_dtype, p->rr_D);
-    return BANG_ERR_UNSUPPORTED;
-  }
+  if (p->row_layout == 1u) return bang_k_search_exact_beam_pull(p, beam, stream);
   return beam_launch(p, beam, stream);
 }
 #endif

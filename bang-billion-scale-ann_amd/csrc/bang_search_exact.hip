@@ -10,18 +10,20 @@
 //  * Distances.  8-bit vectors: G = D / 16 adjacent lanes per survivor, one 16-byte piece each, and the v_dot4 identity
 //    sum (a - b)^2 = sum a^2 - 2 sum a b + sum b^2 on integers below 2^24 -- exact, so its float image is what orc_exact_dist's ascending
 //    fmaf chain gives (the arithmetic of wave_rerank8).  Float vectors: one lane per survivor runs the ascending fmaf chain over its
-//    vector, four 16-byte loads in flight (the arithmetic of wave_rerank_f32).  The query sits in registers in both cases.
+//    vector, four 16-byte loads in flight (the arithmetic of wave_rerank_f32).  The query sits in registers in both cases.  Both routines
+//    live in bang_exact_dist.h, which the beam form (bang_search_beam.hip) includes too.
 //  * Filter (CANON 3): every id of the row is probed against the filter state at entry -- both words in one round trip, read past L1 --
 //    and only then are the survivors' bits set, with ATOMIC ORs into the query's private words.  The claim table of bang_search.hip
 //    (plain stores, same-word lanes merged in LDS) is an optimisation for a kernel whose iteration is bound by requests past L2; here an
 //    evaluation already costs 2-6 lines of vector, the atomics are one request per bit and need no LDS, and the next iteration's probes
 //    wait for them (s_waitcnt vmcnt(0) ahead of the probes, behind the adjacency row they need anyway).
 //  * No pivot table: LDS holds 2L + L/4 + 144 words per wave and the launch is bound by VGPRs.  bang_search_exact_geometry reads the
-//    instance's register count and gives every CU as many waves as its registers (512 per SIMD lane, allocated in granules of 8) and
-//    160 KB of LDS hold, at most 32; small batches are spread over all CUs.
+//    instance's register count and launch bound; the grid is bang_wave_geometry's (bang_wave_host.cpp).
 //  * An adjacency id >= n_nodes is never followed: the row counts as empty and *d_abort = 2 (the batch ends with an error).
-//  * WIDE LAYOUTS (this file built a second time with -DBANG_EXACT_WIDE=1 as bang_search_exact_wide.o: the kernel renamed
-//    search_exact_wide_kernel, so that the three instances above stay the code they are).  D up to 1024; 8-bit vectors with any D / 16.
+//  * ONE OBJECT PER FORM.  The Makefile builds this file once per form below, each under the flag named with it; the flags give the build its
+//    tag (EXACT_TAG), and kernel, geometry function and entry point are named after it (search_exact_wide_pull_kernel, ...), so that the
+//    instances of every other build stay the code they are.  The arguments are checked and routed to a build by bang_wave_host.cpp.
+//  * WIDE LAYOUTS (BANG_EXACT_WIDE).  D up to 1024; 8-bit vectors with any D / 16.
 //    The same loop; what changes is the distance stage (exact_dist_wide below): the survivors' rows are fetched COOPERATIVELY, 64 bytes
 //    of 16 rows per wave instruction (four adjacent lanes per row), staged through registers into a 4 KB LDS tile of the wave (64 rows x
 //    64 B, 16-byte slots XOR-swizzled so that the tile's ds_write_b128 and ds_read_b128 are free of bank conflicts), and lane i runs
@@ -31,17 +33,15 @@
 //    a float holds, the chain rounds nowhere and its value is the integer -- and from the first piece that takes a survivor past 2^24 the
 //    wave continues with the float chain, dimension by dimension, from the integer it has (CANON 10).
 //
-//  * PULLED ROWS (this file built a third and fourth time with -DBANG_EXACT_PULL=1, as bang_search_exact_pull.o and -- with BANG_EXACT_WIDE --
-//    bang_search_exact_wide_pull.o; kernels search_exact_pull_kernel / search_exact_wide_pull_kernel; row_layout 1).  The same loop; a node's
-//    vector comes from the packed table rr_vec_base + id * rr_vec_stride and the parent's adjacency row as 256 bytes -- one dword per lane -- from
-//    a slice of the node's HBM-resident rows, from the HBM copy of the first rows or from pinned host memory over PCIe.
-//  * FP16 VECTOR TABLE (a fifth build, -DBANG_EXACT_PULL=1 -DBANG_EXACT_F16=1 as bang_search_exact_pull_f16.o; ONE instance, kernel
-//    search_exact_pull_f16_kernel; rr_vec_f16 = 1).  The pulled-rows loop on a float index whose table holds IEEE fp16 rows (engine option
-//    vectors_fp16): D % 8 == 0, D <= 256, the query float in registers as above; a lane reads its survivor's row eight elements per 16-byte load,
-//    four loads in flight, and runs the same ascending chain on float(h[j]) - q[j] (exact_dist_f16).  Everything it adds sits under BANG_EXACT_F16.
-//  * LABEL FILTERS (a sixth and seventh build, -DBANG_EXACT_LABELS=1 as bang_search_exact_labels.o and -- with BANG_EXACT_PULL --
-//    bang_search_exact_labels_pull.o; kernels search_exact_labels_kernel / search_exact_labels_pull_kernel; the narrow layouts only; entry
-//    bang_k_search_exact_labels).  The same walk, bit for bit; beside its worklist a wave keeps a second sorted list of capacity L in LDS, the RESULT
+//  * PULLED ROWS (BANG_EXACT_PULL, narrow and wide; row_layout 1).  The same loop; a node's vector comes from the packed table
+//    rr_vec_base + id * rr_vec_stride and the parent's adjacency row as 256 bytes -- one dword per lane -- from a slice of the node's
+//    HBM-resident rows, from the HBM copy of the first rows or from pinned host memory over PCIe.
+//  * FP16 VECTOR TABLE (BANG_EXACT_PULL with BANG_EXACT_F16; ONE instance; rr_vec_f16 = 1).  The pulled-rows loop on a float index whose
+//    table holds IEEE fp16 rows (engine option vectors_fp16): D % 8 == 0, D <= 256, the query float in registers as above; a lane reads its
+//    survivor's row eight elements per 16-byte load, four loads in flight, and runs the same ascending chain on float(h[j]) - q[j]
+//    (exact_dist_f16).  Everything it adds sits under BANG_EXACT_F16.
+//  * LABEL FILTERS (BANG_EXACT_LABELS, with and without BANG_EXACT_PULL; the narrow layouts only; entry bang_k_search_exact_labels).
+//    The same walk, bit for bit; beside its worklist a wave keeps a second sorted list of capacity L in LDS, the RESULT
 //    LIST.  Every survivor carries a 32-bit label word (d_labels[id]) and every query two words {any, all}; in every iteration whose survivors are
 //    merged into the worklist, those that match -- and are not in the exclusion bitmap -- are compacted in input order, with the distance bits the
 //    walk computed, and go through the same sort_and_merge into the result list.  The results are the first k entries of that list
@@ -57,9 +57,50 @@
 #include "bang_internal.h"
 #include "bang_device.h"
 #include "bang_worklist.h"
+#include "bang_exact_dist.h"
 
-#define EXACT_SCRATCH_WORDS 144u     // sd/ti [72] + td/compaction [72] (the survivors' distances, then the sort)
-#define EXACT_MAX_LDS (160u * 1024u)
+// ---------------------------------------------------------------------------------------------------------------------
+// this build: one tag from the flags; the kernel, the geometry function and the entry point are named after it
+// ---------------------------------------------------------------------------------------------------------------------
+#if defined(BANG_EXACT_F16) && (!defined(BANG_EXACT_PULL) || defined(BANG_EXACT_WIDE))
+#error "BANG_EXACT_F16 builds the narrow pulled-rows instance only"
+#endif
+#if defined(BANG_EXACT_LABELS) && defined(BANG_EXACT_WIDE)
+#error "BANG_EXACT_LABELS builds the narrow instances only"
+#endif
+#if defined(BANG_EXACT_LABELS) && defined(BANG_EXACT_F16)
+#error "BANG_EXACT_LABELS builds the narrow instances on float / 8-bit rows only"
+#endif
+
+#if defined(BANG_EXACT_WIDE) && defined(BANG_EXACT_PULL)
+#define EXACT_TAG _wide_pull
+#elif defined(BANG_EXACT_WIDE)
+#define EXACT_TAG _wide
+#elif defined(BANG_EXACT_LABELS) && defined(BANG_EXACT_PULL)
+#define EXACT_TAG _labels_pull
+#elif defined(BANG_EXACT_LABELS)
+#define EXACT_TAG _labels
+#define EXACT_ENTRY bang_k_search_exact_labels_hbm
+#elif defined(BANG_EXACT_F16)
+#define EXACT_TAG _pull_f16
+#elif defined(BANG_EXACT_PULL)
+#define EXACT_TAG _pull
+#else
+#define EXACT_TAG
+#define EXACT_ENTRY bang_k_search_exact_hbm
+#endif
+#define EXACT_PASTE_(a, b, c) a##b##c
+#define EXACT_PASTE(a, b, c) EXACT_PASTE_(a, b, c)
+#define EXACT_KERNEL EXACT_PASTE(search_exact, EXACT_TAG, _kernel)
+#define EXACT_GEOMETRY EXACT_PASTE(bang_search_exact, EXACT_TAG, _geometry)
+#ifndef EXACT_ENTRY                                                // (the two graph-entry builds of the narrow layouts: _hbm behind the tag)
+#define EXACT_ENTRY EXACT_PASTE(bang_k_search_exact, EXACT_TAG, )
+#endif
+#ifdef BANG_EXACT_PULL
+#define EXACT_PULL 1
+#else
+#define EXACT_PULL 0
+#endif
 
 struct ExactArgs {
   bang_search_params p;
@@ -70,87 +111,7 @@ struct ExactArgs {
 #endif
 };
 
-static __host__ __device__ inline uint32_t exact_wl_words(uint32_t L) { return (2u * L + (L + 3u) / 4u + 3u) & ~3u; }
-
-template <bool SIGNED>
-__device__ __forceinline__ int xdot4(uint32_t a, uint32_t b, int c) {
-  if (SIGNED) return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
-  return (int)__builtin_amdgcn_udot4(a, b, (uint32_t)c, false);
-}
-
-// exact distances of the n survivors (ids in LDS: sid[0, n)) -> dist[0, n) in LDS, 8-bit vectors.  qw: this lane's 16-byte piece of the
-// query (piece lane % G), qq: the sum of its squares.  Every lane of the wave executes (the G lanes of a survivor reduce by xor-shuffles).
-template <bool SIGNED>
-__device__ __forceinline__ void exact_dist8(const uint8_t GAS* graph, uint64_t entry_len, uint32_t G, const uint32_t* sid, uint32_t n,
-                                            float* dist, u32x4a qw, int qq, int lane) {
-  constexpr int U = 4;                                            // vector fetches in flight per lane
-  const uint32_t per = 64u / G;                                   // survivors per wave instruction
-  const uint32_t sub = (uint32_t)lane & (G - 1u), slot = (uint32_t)lane / G;
-  for (uint32_t i0 = 0; i0 < n; i0 += per * U) {                  // (uniform)
-    u32x4a v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const uint32_t i = i0 + (uint32_t)u * per + slot;
-      const uint32_t id = sid[i < n ? i : 0u];
-      v[u] = *(const u32x4a GAS*)(graph + (uint64_t)id * entry_len + 16u * sub);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const uint32_t i = i0 + (uint32_t)u * per + slot;
-      int vv = xdot4<SIGNED>(v[u].x, v[u].x, xdot4<SIGNED>(v[u].y, v[u].y, xdot4<SIGNED>(v[u].z, v[u].z, xdot4<SIGNED>(v[u].w, v[u].w, qq))));
-      const int vq = xdot4<SIGNED>(v[u].x, qw.x, xdot4<SIGNED>(v[u].y, qw.y, xdot4<SIGNED>(v[u].z, qw.z, xdot4<SIGNED>(v[u].w, qw.w, 0))));
-      vv -= 2 * vq;
-      for (uint32_t off = 1; off < G; off <<= 1) vv += __shfl_xor(vv, (int)off);
-      if (i < n && sub == 0u) dist[i] = (float)vv;
-    }
-  }
-}
-
-// the same for float vectors: lane i evaluates survivor i0 + i, the ascending fmaf chain over the D dimensions (D % 4 == 0, <= 256);
-// qr[t]: lane l holds query element 64 t + l, read with v_readlane (the dimension index is uniform)
-__device__ __forceinline__ void exact_dist_f32(const uint8_t GAS* graph, uint64_t entry_len, uint32_t D, const uint32_t* sid, uint32_t n,
-                                               float* dist, const float (&qr)[4], int lane) {
-  constexpr int RF = 4;                                           // 16-byte loads in flight per lane
-  for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform)
-    const uint32_t i = i0 + (uint32_t)lane;
-    const uint32_t id = sid[i < n ? i : 0u];
-    const uint8_t GAS* v = graph + (uint64_t)id * entry_len;
-    float acc = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint32_t jt = (uint32_t)t * 64u;
-      if (jt >= D) break;                                         // (uniform)
-      const uint32_t dt = D - jt < 64u ? D - jt : 64u;
-      for (uint32_t jl = 0; jl < dt; jl += 4u * RF) {             // (uniform)
-        u32x4a w[RF];
-#pragma unroll
-        for (int u = 0; u < RF; ++u) {
-          const uint32_t j = jl + 4u * (uint32_t)u;
-          w[u] = *(const u32x4a GAS*)(v + 4u * (jt + (j < dt ? j : 0u)));
-        }
-#pragma unroll
-        for (int u = 0; u < RF; ++u) {
-          const uint32_t j = jl + 4u * (uint32_t)u;
-          if (j < dt) {                                           // (uniform)
-            const uint32_t ww[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-              const float qv = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qr[t]), (int)(j + (uint32_t)d)));
-              const float diff = __uint_as_float(ww[d]) - qv;     // parANN.cu:1139-1179 / orc_exact_dist: vector - query
-              acc = __builtin_fmaf(diff, diff, acc);              // ascending dimension
-            }
-          }
-        }
-      }
-    }
-    if (i < n) dist[i] = acc;
-  }
-}
-
 #ifdef BANG_EXACT_F16
-#if !defined(BANG_EXACT_PULL) || defined(BANG_EXACT_WIDE)
-#error "BANG_EXACT_F16 builds the narrow pulled-rows instance only"
-#endif
 __device__ __forceinline__ float half_bits_to_float(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }   // exact (v_cvt_f32_f16)
 
 // exact_dist_f32 on rows of IEEE fp16 (D % 8 == 0, <= 256; rows 4-byte aligned): lane i evaluates survivor i0 + i, eight elements per 16-byte
@@ -199,9 +160,6 @@ __device__ __forceinline__ void exact_dist_f16(const uint8_t GAS* tab, uint64_t 
 #endif
 
 #ifdef BANG_EXACT_WIDE
-#ifdef BANG_EXACT_LABELS
-#error "BANG_EXACT_LABELS builds the narrow instances only"
-#endif
 // ---------------------------------------------------------------------------------------------------------------------
 // wide layouts: rows fetched cooperatively through an LDS tile (one per wave: 64 rows x 64 bytes)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -309,52 +267,18 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
     if ((uint32_t)lane < np) dist[i0 + (uint32_t)lane] = acc;
   }
 }
-#ifdef BANG_EXACT_PULL
-#define EXACT_KERNEL search_exact_wide_pull_kernel
-#else
-#define EXACT_KERNEL search_exact_wide_kernel
-#endif
 // the float instance keeps 16 query registers across the whole loop and needs a few registers more than the 128 that 16 waves per CU leave a
 // wave: 12 waves per CU, no scratch (bang_search_exact_wide_geometry reads both figures off the instance)
 #define EXACT_MAX_THREADS(DT) ((DT) == BANG_F32 ? 768 : 1024)
+#define EXACT_EXTRA_WORDS EXACT_TILE_WORDS                        // the wave's row tile, behind its scratch
 #else
-#if defined(BANG_EXACT_LABELS)
-#if defined(BANG_EXACT_F16)
-#error "BANG_EXACT_LABELS builds the narrow instances on float / 8-bit rows only"
-#endif
-#if defined(BANG_EXACT_PULL)
-#define EXACT_KERNEL search_exact_labels_pull_kernel
-#else
-#define EXACT_KERNEL search_exact_labels_kernel
-#endif
-#elif defined(BANG_EXACT_F16)
-#define EXACT_KERNEL search_exact_pull_f16_kernel
-#elif defined(BANG_EXACT_PULL)
-#define EXACT_KERNEL search_exact_pull_kernel
-#else
-#define EXACT_KERNEL search_exact_kernel
-#endif
 #define EXACT_MAX_THREADS(DT) 1024
+#define EXACT_EXTRA_WORDS 0u
 #endif
 
-// PULLED ROWS (this file built with -DBANG_EXACT_PULL=1 as bang_search_exact_pull.o, and with -DBANG_EXACT_WIDE=1 as well as
-// bang_search_exact_wide_pull.o: the kernels renamed search_exact_pull_kernel / search_exact_wide_pull_kernel, so that the six instances of the
-// other two builds stay the code they are).  row_layout 1: the vectors in the packed table rr_vec_base (stride rr_vec_stride), the adjacency
-// lists as 256-byte rows of 64 ids (ids first, BANG_ADJ_PAD behind them) in pinned host memory (d_graph), in the HBM copy of the first rows
-// (d_rows_hbm) or in a slice of the node's HBM-resident rows (d_row_slices), read as bang_search.hip's self-paced form reads them.
-#ifdef BANG_EXACT_PULL
-#define EXACT_PULL 1
-// the slice table's entry idx (biased base addresses, 0 = that slice is not there), through the scalar cache
-__device__ __forceinline__ uint64_t slice_base(const uint64_t* tab, uint32_t idx) {
-  uint64_t v;
-  const uint64_t a = (uint64_t)(uintptr_t)tab + 8ull * idx;     // (uniform, but not provably so: made so)
-  const uint64_t at = ((uint64_t)uni((uint32_t)(a >> 32)) << 32) | uni((uint32_t)a);
-  asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(at) : "memory");
-  return v;
-}
-#else
-#define EXACT_PULL 0
-#endif
+// PULLED ROWS (EXACT_PULL).  row_layout 1: the vectors in the packed table rr_vec_base (stride rr_vec_stride), the adjacency lists as 256-byte
+// rows of 64 ids (ids first, BANG_ADJ_PAD behind them) in pinned host memory (d_graph), in the HBM copy of the first rows (d_rows_hbm) or in a
+// slice of the node's HBM-resident rows (d_row_slices), read as bang_search.hip's self-paced form reads them.
 
 template <int DT>
 __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const ExactArgs a) {
@@ -523,7 +447,7 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       // ---------------- exact distances (CANON 10: replaces K2) ----------------
       if (n > 0) {
 #ifdef BANG_EXACT_WIDE
-        exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, scratch + EXACT_SCRATCH_WORDS, qr, qw, qq, lane);
+        exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, scratch + WAVE_SCRATCH_WORDS, qr, qw, qq, lane);
 #else
 #ifdef BANG_EXACT_F16
         if (DT == BANG_F32) exact_dist_f16(graph, entry_len, D, sc, n, sdist, qr, lane);
@@ -670,28 +594,6 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 // ---------------------------------------------------------------------------------------------------------------------
 // launcher
 // ---------------------------------------------------------------------------------------------------------------------
-#ifdef BANG_EXACT_WIDE
-#define EXACT_EXTRA_WORDS EXACT_TILE_WORDS                        // the wave's row tile, behind its scratch
-#if EXACT_PULL
-#define EXACT_GEOMETRY bang_search_exact_wide_pull_geometry
-#else
-#define EXACT_GEOMETRY bang_search_exact_wide_geometry
-#endif
-#else
-#define EXACT_EXTRA_WORDS 0u
-#if defined(BANG_EXACT_LABELS) && EXACT_PULL
-#define EXACT_GEOMETRY bang_search_exact_labels_pull_geometry
-#elif defined(BANG_EXACT_LABELS)
-#define EXACT_GEOMETRY bang_search_exact_labels_geometry
-#elif defined(BANG_EXACT_F16)
-#define EXACT_GEOMETRY bang_search_exact_pull_f16_geometry
-#elif EXACT_PULL
-#define EXACT_GEOMETRY bang_search_exact_pull_geometry
-#else
-#define EXACT_GEOMETRY bang_search_exact_geometry
-#endif
-#endif
-
 static const void* exact_instance(int dtype) {
 #ifndef BANG_EXACT_F16                                             // (float queries on fp16 rows: the one instance of that build)
   if (dtype == BANG_U8) return (const void*)EXACT_KERNEL<BANG_U8>;
@@ -701,63 +603,28 @@ static const void* exact_instance(int dtype) {
   return nullptr;
 }
 
+// LDS words per wave: worklist + scratch (+ the row tile of the wide builds); the label-filter builds hold a second list, the result list --
+// 2 (2L + L/4) + 144 words, 16 waves per CU up to L = 512
 #ifdef BANG_EXACT_LABELS
-// worklist + result list + scratch: 2 (2L + L/4) + 144 words per wave -- 16 waves per CU up to L = 512
-static uint32_t exact_wave_bytes(uint32_t L) { return (2u * exact_wl_words(L) + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS) * 4u; }
+#define EXACT_LISTS 2u
 #else
-static uint32_t exact_wave_bytes(uint32_t L) { return (exact_wl_words(L) + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS) * 4u; }
+#define EXACT_LISTS 1u
 #endif
+static uint32_t exact_wave_words(uint32_t L) { return EXACT_LISTS * wave_wl_words(L) + WAVE_SCRATCH_WORDS + EXACT_EXTRA_WORDS; }
 
-// Waves per CU: what the instance's registers allow (512 per SIMD lane, allocated in granules of 8, four SIMDs, at most 8 waves per SIMD),
-// what 160 KB of LDS hold (2L + L/4 + 144 words per wave; the wide instances 1024 more), at most 32.  The three narrow instances compile to
-// 97-98 VGPRs and no scratch (the merge of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves
-// per SIMD, 16 per CU -- one workgroup of 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  The wide instances (at most 128
-// VGPRs, no scratch: DESIGN.md section 4.6) run 16 waves per CU as well, up to L = 704.  The label-filter builds (BANG_EXACT_LABELS: this function
-// as bang_search_exact_labels_geometry / _pull_geometry) hold a second list per wave -- 2 (2L + L/4) + 144 words -- and compile to 114-118 VGPRs, no
-// scratch: 120 allocated, 16 waves per CU again, whose lists fit LDS up to L = 512.  A batch of fewer than 16 queries per CU is spread
-// over all CUs with fewer waves each (a wave's iteration is latency bound, as in bang_search_geometry).  The pulled-rows builds: 99-100 VGPRs
-// narrow, 108-109 / 134 wide, no scratch -- the same waves per CU, read off the pulled instance.
+// The grid of a launch (bang_wave_geometry on the instance's own figures).  The three narrow instances compile to 97-98 VGPRs and no scratch (the
+// merge of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves per SIMD, 16 per CU -- one workgroup of
+// 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  The wide instances (at most 128 VGPRs, no scratch: DESIGN.md section 4.6) run 16
+// waves per CU as well, up to L = 704.  The label-filter builds compile to 114-118 VGPRs, no scratch: 120 allocated, 16 waves per CU again.  The
+// pulled-rows builds: 99-100 VGPRs narrow, 108-109 / 134 wide, no scratch -- the same waves per CU, read off the pulled instance.
 extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   const void* k = exact_instance(dtype);
   if (!k || L == 0 || L > BANG_MAX_L) { bang_set_error("distance = 1: bad dtype / L"); return BANG_ERR_ARG; }
-  static int regs[3][BANG_MAX_DEVICES] = {}, max_waves_wg[3][BANG_MAX_DEVICES] = {};   // per instance and device, read once
-  const int dev = current_device();
-  if (regs[dtype][dev] == 0) {
-    hipFuncAttributes at;
-    HIP_TRY(hipFuncGetAttributes(&at, k));
-    max_waves_wg[dtype][dev] = at.maxThreadsPerBlock >= WAVE ? at.maxThreadsPerBlock / WAVE : 16;
-    regs[dtype][dev] = at.numRegs > 0 ? at.numRegs : 128;
-  }
-  const uint32_t vg = (uint32_t)regs[dtype][dev];
-  const uint32_t alloc = (vg + 7u) & ~7u;
-  uint32_t per_simd = 512u / alloc;
-  if (per_simd > 8u) per_simd = 8u;
-  uint32_t per_cu = 4u * per_simd;
-  const uint32_t by_lds = EXACT_MAX_LDS / exact_wave_bytes(L);
-  if (by_lds < per_cu) per_cu = by_lds;
-  if (per_cu > 32u) per_cu = 32u;
-  if (per_cu == 0) { bang_set_error("distance = 1: one wave's worklist does not fit LDS at L=%u", L); return BANG_ERR_UNSUPPORTED; }
-  uint32_t W = per_cu < 16u ? per_cu : 16u;
-  if (W > (uint32_t)max_waves_wg[dtype][dev]) W = (uint32_t)max_waves_wg[dtype][dev];     // (the instance's launch bound)
-  const uint32_t wgs_per_cu = per_cu / W;
-  if (max_waves && max_waves < W) W = max_waves;
-  const uint32_t cus = (uint32_t)num_cus();
-  uint32_t grid_n;
-  if (Q <= cus * W) {                                             // fewer queries than a wave-full per CU: all CUs, fewer waves each
-    grid_n = Q < cus ? Q : cus;
-    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
-    const uint32_t share = (Q + grid_n - 1) / grid_n;
-    if (share < W) W = share;
-  } else {
-    const uint32_t want = (Q + W - 1) / W;
-    grid_n = cus * wgs_per_cu;
-    if (want < grid_n) grid_n = want;
-    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
-  }
-  *workgroups = grid_n;
-  *waves = W;
-  return BANG_OK;
+  static WaveKernelAttr attr[3];                                  // per instance
+  const int rc = wave_kernel_geometry(k, attr[dtype], exact_wave_words(L) * 4u, Q, max_wgs, max_waves, workgroups, waves);
+  if (rc == BANG_ERR_UNSUPPORTED) bang_set_error("distance = 1: one wave's worklist does not fit LDS at L=%u", L);
+  return rc;
 }
 
 // one launch of this translation unit's instances (the arguments are checked: bang_k_search_exact)
@@ -771,19 +638,17 @@ static int exact_launch(const bang_search_params* p, void* stream) {
   if (rc != BANG_OK) return rc;
   ExactArgs a;
   a.p = *p;
-  a.wl_words = exact_wl_words(p->L);
+  a.wl_words = wave_wl_words(p->L);
+  a.wave_words = exact_wave_words(p->L);
 #ifdef BANG_EXACT_LABELS
-  a.wave_words = 2u * a.wl_words + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS;
   a.f = *f;
-#else
-  a.wave_words = a.wl_words + EXACT_SCRATCH_WORDS + EXACT_EXTRA_WORDS;
 #endif
   const size_t lds = (size_t)waves * a.wave_words * 4u;
   const void* k = exact_instance((int)p->rr_dtype);
   static bool attr_done[3][BANG_MAX_DEVICES] = {};
   const int dev = current_device();
   if (!attr_done[p->rr_dtype][dev]) {
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXACT_MAX_LDS));
+    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_MAX_LDS));
     attr_done[p->rr_dtype][dev] = true;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -797,135 +662,26 @@ static int exact_launch(const bang_search_params* p, void* stream) {
   return BANG_OK;
 }
 
-#if defined(BANG_EXACT_LABELS)
-// the label-filter instances, called by bang_k_search_exact_labels with its arguments checked: graph entries in HBM (row_layout 0) / pulled rows (1)
-#if EXACT_PULL
-extern "C" int bang_k_search_exact_labels_pull(const bang_search_params* p, const bang_label_filter* f, void* stream) {
-  if (!p || !f || p->row_layout != 1u || !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return BANG_ERR_ARG;
-#else
-extern "C" int bang_k_search_exact_labels_hbm(const bang_search_params* p, const bang_label_filter* f, void* stream) {
-  if (!p || !f || p->row_layout != 0u || !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->entry_len, 0)) return BANG_ERR_ARG;
-#endif
+// This build's entry point (EXACT_ENTRY: bang_internal.h), called by bang_k_search_exact / bang_k_search_exact_labels (bang_wave_host.cpp) with
+// the arguments checked; what the kernel's own addressing rests on is looked at once more.
+#ifdef BANG_EXACT_LABELS
+extern "C" int EXACT_ENTRY(const bang_search_params* p, const bang_label_filter* f, void* stream) {
+  if (!p || !f || p->row_layout != (uint32_t)EXACT_PULL ||
+      !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, EXACT_PULL ? p->rr_vec_stride : p->entry_len, 0)) return BANG_ERR_ARG;
   if (!f->d_labels || !f->d_filters || p->n_nodes == 0u) return BANG_ERR_ARG;
   return exact_launch(p, f, stream);
 }
-#elif defined(BANG_EXACT_F16)
-// the pulled-rows instance on an fp16 vector table, called by bang_k_search_exact with its arguments checked
-extern "C" int bang_k_search_exact_pull_f16(const bang_search_params* p, void* stream) {
-  if (!p || p->row_layout != 1u || p->rr_vec_f16 != 1u || p->rr_dtype != BANG_F32 || p->rr_D % 8u != 0u || p->rr_D > 256u || (p->rr_vec_stride & 3u) ||
+#else
+extern "C" int EXACT_ENTRY(const bang_search_params* p, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+#if defined(BANG_EXACT_F16)
+  if (p->row_layout != 1u || p->rr_vec_f16 != 1u || p->rr_dtype != BANG_F32 || p->rr_D % 8u != 0u || p->rr_D > 256u || (p->rr_vec_stride & 3u) ||
       p->rr_vec_stride < 2ull * p->rr_D) return BANG_ERR_ARG;
-  return exact_launch(p, stream);
-}
 #elif EXACT_PULL
-// the pulled-rows instances (row_layout 1), called by bang_k_search_exact with its arguments checked: the layouts of the fused re-rank on the
-// narrow instances, the others on the wide ones
-#ifdef BANG_EXACT_WIDE
-extern "C" int bang_k_search_exact_wide_pull(const bang_search_params* p, void* stream) {
+  if (p->row_layout != 1u || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) return BANG_ERR_ARG;
 #else
-extern "C" int bang_k_search_exact_pull(const bang_search_params* p, void* stream) {
+  if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len)) return BANG_ERR_ARG;
 #endif
-  if (!p || p->row_layout != 1u || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) return BANG_ERR_ARG;
   return exact_launch(p, stream);
-}
-#elif defined(BANG_EXACT_WIDE)
-// called by bang_k_search_exact with its arguments checked, for the layouts the narrow instances do not evaluate
-extern "C" int bang_k_search_exact_wide(const bang_search_params* p, void* stream) {
-  if (!p || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len)) return BANG_ERR_ARG;
-  return exact_launch(p, stream);
-}
-#else
-// Vector layouts the kernels evaluate.  8-bit: D % 16 == 0; float: D % 4 == 0; D <= 1024; a 4-byte-aligned entry stride; no MIPS padding.
-// Those of the fused re-rank (bang_search_can_rerank: D <= 256, 8-bit D / 16 a power of two) run on the narrow instances, the others on the
-// wide ones.
-extern "C" int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry_len) {
-  if (D == 0 || D > BANG_EXACT_MAX_D || (entry_len & 3u)) return 0;
-  if (dtype == BANG_F32) return D % 4u == 0 && entry_len >= 4ull * D;
-  if (dtype == BANG_U8 || dtype == BANG_I8) return D % 16u == 0 && entry_len >= D;
-  return 0;
-}
-
-// every check of a launch's arguments, before any HIP call (shared by bang_k_search_exact and bang_k_search_exact_labels)
-static int exact_check(const bang_search_params* p) {
-  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("distance = 1: bad R/L"); return BANG_ERR_ARG; }
-  if (p->row_layout > 1u) { bang_set_error("distance = 1: row_layout = %u: the adjacency lists are graph entries in HBM (0) or 256-byte rows (1)", p->row_layout); return BANG_ERR_UNSUPPORTED; }
-  if (p->row_layout == 0u && !p->d_graph) { bang_set_error("distance = 1: the exact-distance kernel needs the graph entries in HBM (d_graph, row_layout = 0)"); return BANG_ERR_UNSUPPORTED; }
-  if (!p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt || !p->d_next_query || !p->rr_queries || !p->rr_ids_out || !p->rr_dists_out) {
-    bang_set_error("distance = 1: null buffer"); return BANG_ERR_ARG;
-  }
-  if (p->cap_iter == 0 || p->cap_iter > p->L + BANG_EXTRA_ITERS - 1) { bang_set_error("distance = 1: bad iteration cap"); return BANG_ERR_ARG; }
-  if (p->rr_k == 0 || p->rr_k > p->L || p->rr_Q_total < p->rr_q0 + p->Q) { bang_set_error("distance = 1: bad k / result rows"); return BANG_ERR_ARG; }
-  if (p->rr_vec_f16 > 1u) { bang_set_error("distance = 1: rr_vec_f16 = %u (0 = float / 8-bit rows, 1 = fp16 rows)", p->rr_vec_f16); return BANG_ERR_ARG; }
-  if (p->rr_vec_f16 == 1u) {
-    // fp16 rows in the vector table: the pulled-rows form, float queries, the one layout family that has an instance
-    if (p->row_layout != 1u) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs row_layout = 1 (graph entries in HBM hold float vectors)"); return BANG_ERR_ARG; }
-    if (p->rr_dtype != BANG_F32) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs rr_dtype = BANG_F32 (rr_dtype = %u)", p->rr_dtype); return BANG_ERR_ARG; }
-    if (p->rr_D == 0u || p->rr_D % 8u != 0u || p->rr_D > 256u) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs rr_D %% 8 == 0 and rr_D <= 256 (rr_D = %u)", p->rr_D); return BANG_ERR_ARG; }
-  }
-  if (p->row_layout == 1u) {
-    // the pulled-rows form: adjacency rows in d_graph (pinned host memory; 4-byte aligned), vectors at rr_vec_base + id * rr_vec_stride
-    if (!p->d_graph || (((uintptr_t)p->d_graph) & 3u)) { bang_set_error("distance = 1, row_layout = 1: d_graph (the 256-byte adjacency rows) is null or not 4-byte aligned"); return BANG_ERR_ARG; }
-    if (p->R > 64u) { bang_set_error("distance = 1, row_layout = 1: R = %u, a 256-byte row holds 64 ids", p->R); return BANG_ERR_ARG; }
-    if (!p->rr_vec_base || (((uintptr_t)p->rr_vec_base) & 3u)) { bang_set_error("distance = 1, row_layout = 1: rr_vec_base (the vectors) is null or not 4-byte aligned"); return BANG_ERR_ARG; }
-    if (p->rr_vec_f16 == 1u && ((p->rr_vec_stride & 3u) || p->rr_vec_stride < 2ull * p->rr_D)) {
-      bang_set_error("distance = 1, row_layout = 1, rr_vec_f16 = 1: rr_vec_stride = %llu is not divisible by 4 or does not hold rr_D = %u halves",
-                     (unsigned long long)p->rr_vec_stride, p->rr_D);
-      return BANG_ERR_ARG;
-    }
-    if (p->rr_vec_f16 != 1u && !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
-      bang_set_error("distance = 1, row_layout = 1: rr_vec_stride = %llu does not describe vectors the kernel evaluates (dtype %u, D = %u): 8-bit vectors need "
-                     "D %% 16 == 0, float vectors D %% 4 == 0; D <= %u; a stride divisible by 4 that holds the vector", (unsigned long long)p->rr_vec_stride,
-                     p->rr_dtype, p->rr_D, BANG_EXACT_MAX_D);
-      return BANG_ERR_ARG;
-    }
-    if (p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u)) { bang_set_error("distance = 1, row_layout = 1: vec_bytes = %u is not rr_D * the element size", p->vec_bytes); return BANG_ERR_ARG; }
-    if (((uintptr_t)p->rr_queries) & 3u) { bang_set_error("distance = 1, row_layout = 1: rr_queries is not 4-byte aligned"); return BANG_ERR_ARG; }
-    if (p->n_slices > 1u && !p->d_row_slices) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs the slice table d_row_slices", p->n_slices); return BANG_ERR_ARG; }
-    if (p->n_slices > 1u && p->slice_rows == 0u) { bang_set_error("distance = 1, row_layout = 1: n_slices = %u needs slice_rows != 0", p->n_slices); return BANG_ERR_ARG; }
-    if (p->n_rows_hbm != 0u && !p->d_rows_hbm) { bang_set_error("distance = 1, row_layout = 1: n_rows_hbm = %u needs d_rows_hbm", p->n_rows_hbm); return BANG_ERR_ARG; }
-    return BANG_OK;
-  }
-  if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
-      (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
-    bang_set_error("distance = 1: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0, float vectors "
-                   "D %% 4 == 0; D <= %u; an entry stride divisible by 4", p->rr_dtype, p->rr_D, (unsigned long long)p->entry_len, BANG_EXACT_MAX_D);
-    return BANG_ERR_UNSUPPORTED;
-  }
-  return BANG_OK;
-}
-
-extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
-  if (!p) return BANG_ERR_ARG;
-  if (p->Q == 0) return BANG_OK;
-  const int rc = exact_check(p);
-  if (rc != BANG_OK) return rc;
-  if (p->row_layout == 1u) {
-    if (p->rr_vec_f16 == 1u) return bang_k_search_exact_pull_f16(p, stream);
-    if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return bang_k_search_exact_pull(p, stream);
-    return bang_k_search_exact_wide_pull(p, stream);
-  }
-  if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->entry_len, 0)) return exact_launch(p, stream);
-  return bang_k_search_exact_wide(p, stream);
-}
-
-// The walk of bang_k_search_exact with per-query label filters (CANON 18): the narrow layouts only, routed on row_layout to the
-// instances of bang_search_exact_labels.o / bang_search_exact_labels_pull.o
-extern "C" int bang_k_search_exact_labels(const bang_search_params* p, const bang_label_filter* f, void* stream) {
-  if (!p) return BANG_ERR_ARG;
-  if (!f) { bang_set_error("distance = 1, labels: the filter arguments f (bang_label_filter) are null"); return BANG_ERR_ARG; }
-  if (!f->d_labels) { bang_set_error("distance = 1, labels: d_labels (one label word per node) is null"); return BANG_ERR_ARG; }
-  if (!f->d_filters) { bang_set_error("distance = 1, labels: d_filters (the queries' {any, all} words) is null"); return BANG_ERR_ARG; }
-  if (p->n_nodes == 0u) { bang_set_error("distance = 1, labels: n_nodes = 0: d_labels and d_excluded are indexed by node id and need the number of nodes"); return BANG_ERR_ARG; }
-  if (p->Q == 0) return BANG_OK;
-  const int rc = exact_check(p);
-  if (rc != BANG_OK) return rc;
-  if (p->rr_vec_f16 == 1u) { bang_set_error("distance = 1, labels: rr_vec_f16 = 1 (fp16 rows) has no label-filter instance"); return BANG_ERR_UNSUPPORTED; }
-  const uint64_t stride = p->row_layout == 1u ? p->rr_vec_stride : p->entry_len;
-  if (!bang_search_can_rerank((int)p->rr_dtype, p->rr_D, stride, 0)) {
-    bang_set_error("distance = 1, labels: the vector layout (dtype %u, rr_D = %u, stride %llu) runs on the wide instances, which have no label-filter form "
-                   "(8-bit vectors need D / 16 a power of two; D <= 256)", p->rr_dtype, p->rr_D, (unsigned long long)stride);
-    return BANG_ERR_UNSUPPORTED;
-  }
-  if (p->row_layout == 1u) return bang_k_search_exact_labels_pull(p, f, stream);
-  return bang_k_search_exact_labels_hbm(p, f, stream);
 }
 #endif

@@ -27,9 +27,7 @@
 #include "bang_internal.h"
 #include "bang_device.h"
 #include "bang_worklist.h"
-
-#define LUT_SCRATCH_WORDS 144u       // sd/ti [72] + td/compaction [72] (the survivors' distances, then the sort)
-#define LUT_MAX_LDS (160u * 1024u)
+#include "bang_exact_dist.h"
 
 struct LutArgs {
   bang_search_params p;
@@ -37,8 +35,7 @@ struct LutArgs {
   uint32_t wl_words;                 // LDS words of the worklist (2L + ceil(L/4), rounded to 4)
 };
 
-static inline uint32_t lut_wl_words(uint32_t L) { return (2u * L + (L + 3u) / 4u + 3u) & ~3u; }
-static inline uint32_t lut_wave_bytes(uint32_t L) { return (lut_wl_words(L) + LUT_SCRATCH_WORDS) * 4u; }
+static inline uint32_t lut_wave_bytes(uint32_t L) { return (wave_wl_words(L) + WAVE_SCRATCH_WORDS) * 4u; }
 
 __device__ __forceinline__ uint32_t code_byte(const uint32_t (&b)[4], int l) { return (b[l >> 2] >> (8 * (l & 3))) & 255u; }
 
@@ -269,51 +266,17 @@ __global__ __launch_bounds__(1024) void search_lut_kernel(const LutArgs a) {
 // 1 if one wave's state (2L + L/4 + 144 words) fits LDS; the table stays in HBM / the caches, so m only has to be a chunk count
 extern "C" int bang_search_lut_supported(uint32_t m, uint32_t L) {
   if (m == 0 || L == 0 || L > BANG_MAX_L) return 0;
-  return lut_wave_bytes(L) <= LUT_MAX_LDS ? 1 : 0;
+  return lut_wave_bytes(L) <= WAVE_MAX_LDS ? 1 : 0;
 }
 
-// Waves per CU: what the instance's registers allow (512 per SIMD lane, allocated in granules of 8, four SIMDs, at most 8 waves per SIMD), what
-// 160 KB of LDS hold, at most 32 -- as bang_search_exact_geometry.  A batch of fewer than a workgroup-full of queries per CU is spread over all
-// CUs with fewer waves each (a wave's iteration is latency bound).
+// The grid of a launch (bang_wave_geometry on the instance's own figures), as bang_search_exact_geometry
 extern "C" int bang_search_lut_geometry(uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   if (L == 0 || L > BANG_MAX_L) { bang_set_error("LUT search kernel: bad L"); return BANG_ERR_ARG; }
-  static int regs[BANG_MAX_DEVICES] = {}, max_waves_wg[BANG_MAX_DEVICES] = {};   // per device, read once
-  const int dev = current_device();
-  if (regs[dev] == 0) {
-    hipFuncAttributes at;
-    HIP_TRY(hipFuncGetAttributes(&at, (const void*)search_lut_kernel));
-    max_waves_wg[dev] = at.maxThreadsPerBlock >= WAVE ? at.maxThreadsPerBlock / WAVE : 16;
-    regs[dev] = at.numRegs > 0 ? at.numRegs : 128;
-  }
-  const uint32_t alloc = ((uint32_t)regs[dev] + 7u) & ~7u;
-  uint32_t per_simd = 512u / alloc;
-  if (per_simd > 8u) per_simd = 8u;
-  uint32_t per_cu = 4u * per_simd;
-  const uint32_t by_lds = LUT_MAX_LDS / lut_wave_bytes(L);
-  if (by_lds < per_cu) per_cu = by_lds;
-  if (per_cu > 32u) per_cu = 32u;
-  if (per_cu == 0) { bang_set_error("LUT search kernel: one wave's worklist does not fit LDS at L=%u", L); return BANG_ERR_UNSUPPORTED; }
-  uint32_t W = per_cu < 16u ? per_cu : 16u;
-  if (W > (uint32_t)max_waves_wg[dev]) W = (uint32_t)max_waves_wg[dev];                   // (the instance's launch bound)
-  const uint32_t wgs_per_cu = per_cu / W;
-  if (max_waves && max_waves < W) W = max_waves;
-  const uint32_t cus = (uint32_t)num_cus();
-  uint32_t grid_n;
-  if (Q <= cus * W) {                                             // fewer queries than a wave-full per CU: all CUs, fewer waves each
-    grid_n = Q < cus ? Q : cus;
-    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
-    const uint32_t share = (Q + grid_n - 1) / grid_n;
-    if (share < W) W = share;
-  } else {
-    const uint32_t want = (Q + W - 1) / W;
-    grid_n = cus * wgs_per_cu;
-    if (want < grid_n) grid_n = want;
-    if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
-  }
-  *workgroups = grid_n;
-  *waves = W;
-  return BANG_OK;
+  static WaveKernelAttr attr;
+  const int rc = wave_kernel_geometry((const void*)search_lut_kernel, attr, lut_wave_bytes(L), Q, max_wgs, max_waves, workgroups, waves);
+  if (rc == BANG_ERR_UNSUPPORTED) bang_set_error("LUT search kernel: one wave's worklist does not fit LDS at L=%u", L);
+  return rc;
 }
 
 extern "C" int bang_k_search_lut(const bang_search_params* p, void* stream) {
@@ -338,13 +301,13 @@ extern "C" int bang_k_search_lut(const bang_search_params* p, void* stream) {
   if (rc != BANG_OK) return rc;
   LutArgs a;
   a.p = *p;
-  a.wl_words = lut_wl_words(p->L);
-  a.wave_words = a.wl_words + LUT_SCRATCH_WORDS;
+  a.wl_words = wave_wl_words(p->L);
+  a.wave_words = a.wl_words + WAVE_SCRATCH_WORDS;
   const size_t lds = (size_t)waves * a.wave_words * 4u;
   static bool attr_done[BANG_MAX_DEVICES] = {};
   const int dev = current_device();
   if (!attr_done[dev]) {
-    HIP_TRY(hipFuncSetAttribute((const void*)search_lut_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LUT_MAX_LDS));
+    HIP_TRY(hipFuncSetAttribute((const void*)search_lut_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_MAX_LDS));
     attr_done[dev] = true;
   }
   hipLaunchKernelGGL(search_lut_kernel, dim3(grid_n), dim3(waves * WAVE), lds, (hipStream_t)stream, a);

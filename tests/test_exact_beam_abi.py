@@ -1,6 +1,7 @@
 """C-ABI of the beam form of the exact-distance search kernel (bang_k_search_exact_beam, csrc/bang_search_beam.hip), without a GPU: a broken
 contract is refused with the right code and a message naming the member -- or `beam` -- BEFORE any HIP call (on a machine without a device a
-launcher that reached the runtime would return BANG_ERR_HIP, not the code asserted here); bang_search_params is what it was."""
+launcher that reached the runtime would return BANG_ERR_HIP, not the code asserted here), and with the code and the text bang_k_search_exact
+gives for the same arguments; bang_search_params is what it was."""
 import ctypes as C
 import os
 import re
@@ -32,6 +33,18 @@ def _call(libbang, sp, beam=2):
     f.restype = C.c_int
     rc = f(C.byref(sp), beam, None)
     return rc, libbang.bang_last_error().decode()
+
+
+def _same_as_the_exact_entry(libbang, B, over, rc, err, beam):
+    """bang_k_search_exact on the same arguments: its code, and its message behind the prefix that names the beam"""
+    f = libbang.bang_k_search_exact
+    f.argtypes = [C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    rc_exact = f(C.byref(_params(B, **over)), None)
+    err_exact = libbang.bang_last_error().decode()
+    assert rc_exact != OK and err_exact.startswith("distance = 1"), (rc_exact, err_exact)
+    assert rc == rc_exact, (rc, rc_exact, err)
+    assert err == "distance = 1, beam = %d" % beam + err_exact[len("distance = 1"):], (err, err_exact)
 
 
 @pytest.mark.parametrize("beam", [0, 5, 64, 0xFFFFFFFF])
@@ -74,6 +87,7 @@ def test_pulled_form_refuses_a_broken_contract(libbang, over, message):
         rc, err = _call(libbang, _params(B, **over), beam)
         assert rc == ERR_ARG, (rc, err)
         assert message in err and "beam" in err, err
+        _same_as_the_exact_entry(libbang, B, over, rc, err, beam)
 
 
 @pytest.mark.parametrize("over", [
@@ -101,6 +115,11 @@ def test_row_layouts_and_the_graph_entry_form(libbang):
     assert rc == ERR_UNSUPPORTED and "unsupported vector layout" in err
     rc, err = _call(libbang, _params(B, row_layout=0, entry_len=128 + 4 * 33, rr_queries=0x1001))
     assert rc == ERR_UNSUPPORTED and "unsupported vector layout" in err
+    for over in (dict(row_layout=2), dict(row_layout=7), dict(row_layout=0, d_graph=None, entry_len=128 + 4 * 33),
+                 dict(row_layout=0, entry_len=130, rr_vec_base=None, rr_vec_stride=0), dict(row_layout=0, entry_len=128 + 4 * 33, rr_queries=0x1001)):
+        for beam in (1, 4):
+            rc, err = _call(libbang, _params(B, **over), beam)
+            _same_as_the_exact_entry(libbang, B, over, rc, err, beam)
 
 
 def test_null_and_empty(libbang):
