@@ -103,6 +103,18 @@ class StatsExt3(C.Structure):
     _fields_ = StatsExt2._fields_ + [("labelled", C.c_uint64), ("filtered_queries", C.c_uint64), ("label_launches", C.c_uint64)]
 
 
+class StatsExt4(C.Structure):
+    """bang_stats_ext4: bang_stats_ext3 with the range-search fields behind it (bang_get_stats_ext4)."""
+    _fields_ = StatsExt3._fields_ + [("range_hits", C.c_uint64), ("range_queries", C.c_uint64), ("range_launches", C.c_uint64),
+                                     ("range_truncated", C.c_uint64)]
+
+
+class RangeOut(C.Structure):
+    """bang_range_out: what bang_k_search_exact_range takes beside bang_search_params (device addresses)."""
+    _fields_ = [("d_radius", C.c_void_p), ("d_excluded", C.c_void_p), ("d_hit_ids", C.c_void_p), ("d_hit_dists", C.c_void_p),
+                ("d_offered", C.c_void_p), ("cap", C.c_uint32)]
+
+
 class LabelFilter(C.Structure):
     """bang_label_filter: what bang_k_search_exact_labels takes beside bang_search_params (device addresses)."""
     _fields_ = [("d_labels", C.c_void_p), ("d_filters", C.c_void_p), ("d_excluded", C.c_void_p), ("d_matched", C.c_void_p)]
@@ -335,6 +347,7 @@ class Engine:
 
     def alloc(self, num_queries: int):
         _check(lib().bang_alloc_e(self._h, num_queries), "bang_alloc")
+        self._Qcap = int(num_queries)
 
     def init(self, num_queries: int):
         _check(lib().bang_init_e(self._h, num_queries), "bang_init")
@@ -422,10 +435,47 @@ class Engine:
         _check(fn(self._h, _vp(out), C.c_uint32(Q)), "bang_get_matched_counts")
         return out
 
+    def set_radii(self, r, Q: int | None = None):
+        """bang_set_query_radii_e: the radii (squared L2) of the batches to come -- an array gives one radius per query, a scalar is broadcast
+        to Q queries (default: the allocated batch).  After alloc, with option range_hits > 0; kept until replaced, cleared or free."""
+        a = np.asarray(r, dtype=np.float32)
+        if a.ndim == 0:
+            a = np.full(getattr(self, "_Qcap", 0) if Q is None else int(Q), a, dtype=np.float32)
+        a = np.ascontiguousarray(a.reshape(-1))
+        fn = lib().bang_set_query_radii_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _check(fn(self._h, _vp(a) if a.size else None, int(a.size)), "bang_set_query_radii")
+
+    def clear_radii(self):
+        fn = lib().bang_clear_query_radii_e
+        fn.argtypes = [C.c_void_p]
+        _check(fn(self._h), "bang_clear_query_radii")
+
+    def range_counts(self, Q: int):
+        """(count [Q], offered [Q]) of the last batch with radii: hits in each query's answer, and all hits its walk met (offered > range_hits:
+        the answer was truncated)."""
+        cnt, off = np.zeros(Q, np.uint32), np.zeros(Q, np.uint32)
+        fn = lib().bang_get_range_counts
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        _check(fn(self._h, _vp(cnt), _vp(off), C.c_uint32(Q)), "bang_get_range_counts")
+        return cnt, off
+
+    def range_results(self, Q: int):
+        """(lims [Q + 1] u64, ids u64, dists f32) of the last batch with radii (Q = its size): query q's hits, ascending by distance then id, at
+        [lims[q], lims[q + 1])."""
+        cnt, _ = self.range_counts(Q)
+        total = int(cnt.astype(np.uint64).sum())
+        lims = np.zeros(Q + 1, np.uint64)
+        ids, dists = np.zeros(max(total, 1), np.uint64), np.zeros(max(total, 1), np.float32)
+        fn = lib().bang_get_range_results
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        _check(fn(self._h, _vp(lims), _vp(ids), _vp(dists), C.c_uint64(total)), "bang_get_range_results")
+        return lims, ids[:total], dists[:total]
+
     def stats(self) -> dict:
-        s = StatsExt3()
-        _check(lib().bang_get_stats_ext3(self._h, C.byref(s)), "bang_get_stats_ext3")
-        return {f: getattr(s, f) for f, _ in StatsExt3._fields_}
+        s = StatsExt4()
+        _check(lib().bang_get_stats_ext4(self._h, C.byref(s)), "bang_get_stats_ext4")
+        return {f: getattr(s, f) for f, _ in StatsExt4._fields_}
 
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the

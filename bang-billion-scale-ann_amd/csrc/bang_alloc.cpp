@@ -31,6 +31,9 @@ void free_batch(bang_engine* e) {
   if (e->h_results) { (void)hipHostFree(e->h_results); e->h_results = nullptr; e->h_results_dev = nullptr; }
   dfree(e->d_live_ids); dfree(e->d_live_cnt); dfree(e->d_wl_ids_full); dfree(e->d_wl_dists_full);      // (excluded ids)
   dfree(e->d_qfilters); dfree(e->d_matched); e->n_qfilters = 0; e->n_filtered = 0;                      // (query filters)
+  dfree(e->d_hit_ids); dfree(e->d_hit_dists); dfree(e->d_radius); dfree(e->d_offered); dfree(e->d_range_count);   // (range search)
+  e->n_radii = 0; e->range_counts_valid = false;
+  e->stat_range_queries = 0; e->stat_range_launches = 0; e->stat_range_truncated = 0;   // (the counts of a freed batch are gone with its buffers)
   e->qfilter_file_rows.clear(); e->qfilters_from_file = false;
   dfree(e->d_done_count); dfree(e->d_stage); dfree(e->d_srows); dfree(e->d_sctl);
   if (e->h_parents) (void)hipHostFree(e->h_parents);
@@ -178,6 +181,18 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     e->search_v2 = false;
     e->pq_nhi = 0;
   }
+  // range_hits > 0: range search (bang_k_search_exact_range) -- the narrow layouts of the exact-distance walk on float / 8-bit rows.  What it cannot
+  // run is refused: there is no fallback
+  if (e->range_hits > 0) {
+    if (e->distance != 1) { bang_set_error("option range_hits = %d (range search) needs distance = 1 (exact): the PQ walks have no exact distance when a node is evaluated", e->range_hits); return BANG_ERR_UNSUPPORTED; }
+    if (e->beam > 1) { bang_set_error("option range_hits = %d (range search) is not available with beam = %d: the beam kernel keeps no hit log", e->range_hits, e->beam); return BANG_ERR_UNSUPPORTED; }
+    if (e->vecs_f16 && !dev_graph) { bang_set_error("option range_hits = %d (range search) is not available with vectors_fp16 = 1: the range kernel reads float / 8-bit rows", e->range_hits); return BANG_ERR_UNSUPPORTED; }
+    if (!bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e), 0)) {
+      bang_set_error("option range_hits = %d: the wide vector layouts have no range kernel (dtype %d, D = %u): 8-bit vectors need D / 16 a power of two, D <= 256",
+                     e->range_hits, e->dtype, e->D);
+      return BANG_ERR_UNSUPPORTED;
+    }
+  }
   // semantics = 1: the BANG_Inmemory walk on the self-paced search kernel (bang_k_search_inmem).  What it cannot run is refused: there is no
   // fallback to the BANG_Base walk
   e->search_inmem = false;
@@ -281,6 +296,13 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       BANG_TRY(dmalloc(&e->d_live_ids, nq * rows));
       BANG_TRY(dmalloc(&e->d_live_cnt, nq));
     }
+  }
+  if (e->range_hits > 0) {                                                   // range search: the hit log and what travels with it
+    BANG_TRY(dmalloc(&e->d_hit_ids, nq * (size_t)e->range_hits));
+    BANG_TRY(dmalloc(&e->d_hit_dists, nq * (size_t)e->range_hits));
+    BANG_TRY(dmalloc(&e->d_radius, nq));
+    BANG_TRY(dmalloc(&e->d_offered, nq));
+    BANG_TRY(dmalloc(&e->d_range_count, nq));
   }
   BANG_TRY(dmalloc(&e->d_parents_dev, nq));
   if (dev_graph) {

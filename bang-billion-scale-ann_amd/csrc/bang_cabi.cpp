@@ -167,6 +167,7 @@ extern "C" int bang_set_query_filters_e(bang_engine_t* e, const uint32_t* any, c
   if (nq == 0) { (void)hipSetDevice(e->device); drop_query_filters(e); return BANG_OK; }
   if (!any || !all) { bang_set_error("%s: any / all is null", what); return BANG_ERR_ARG; }
   if (!e->d_labels) { bang_set_error("%s: no labels are set (bang_set_labels_e or BANG_LABEL_FILE, before bang_alloc)", what); return BANG_ERR_UNSUPPORTED; }
+  if (e->n_radii != 0) { bang_set_error("%s: filters on labels and radii (bang_set_query_radii_e) do not combine: clear the radii first (bang_clear_query_radii_e)", what); return BANG_ERR_UNSUPPORTED; }
   // the forms without a label-filter kernel are refused: there is no unfiltered fallback
   const bool dev_graph = (e->graph_mode == BANG_GRAPH_DEVICE);
   if (!e->search_exact) {
@@ -233,6 +234,85 @@ extern "C" int bang_get_matched_counts(bang_engine_t* e, uint32_t* out, uint32_t
   }
   if (num_queries > (uint32_t)e->Qcur) { bang_set_error("bang_get_matched_counts: %u counts asked for, the last batch had %d queries", num_queries, e->Qcur); return BANG_ERR_ARG; }
   HIP_TRY(hipMemcpy(out, e->d_matched, (size_t)num_queries * 4, hipMemcpyDeviceToHost));
+  return BANG_OK;
+}
+
+// ------------------------------------------------------------------ range search: per-query radii and the batch's hits
+extern "C" int bang_set_query_radii_e(bang_engine_t* e, const float* radii, int nq) {
+  if (!e) return BANG_ERR_ARG;
+  const char* what = "bang_set_query_radii";
+  if (!e->allocated) { bang_set_error("%s: the radii of a batch live in its allocation: call bang_alloc first", what); return BANG_ERR_ARG; }
+  if (e->range_hits <= 0 || !e->d_radius) { bang_set_error("%s: range search is off: option range_hits = 0 (set it before bang_alloc)", what); return BANG_ERR_UNSUPPORTED; }
+  if (nq < 0 || nq > e->Qcap) { bang_set_error("%s: %d radii exceed the allocation of %d queries", what, nq, e->Qcap); return BANG_ERR_ARG; }
+  if (nq == 0) { e->n_radii = 0; return BANG_OK; }
+  if (!radii) { bang_set_error("%s: radii is null", what); return BANG_ERR_ARG; }
+  if (e->n_qfilters != 0) { bang_set_error("%s: radii and filters on labels (bang_set_query_filters_e) do not combine: clear the filters first (bang_clear_query_filters_e)", what); return BANG_ERR_UNSUPPORTED; }
+  BANG_TRY(ensure_device(e));
+  const hipError_t err = hipMemcpy(e->d_radius, radii, (size_t)nq * 4, hipMemcpyHostToDevice);
+  if (err != hipSuccess) { e->n_radii = 0; HIP_TRY(err); }
+  e->n_radii = (uint32_t)nq;
+  return BANG_OK;
+}
+
+extern "C" int bang_clear_query_radii_e(bang_engine_t* e) {
+  if (!e) return BANG_ERR_ARG;
+  e->n_radii = 0;
+  return BANG_OK;
+}
+
+// the counts of the last range batch, fetched once per batch: count and offered of its Qcur queries
+static int range_counts(bang_engine* e, const char* what) {
+  if (!e->allocated || e->Qcur <= 0 || e->stat_range_launches == 0 || !e->d_range_count) {
+    bang_set_error("%s: the last query on this allocation did not run with radii (bang_set_query_radii_e)", what);
+    return BANG_ERR_ARG;
+  }
+  if (e->range_counts_valid) return BANG_OK;
+  const size_t nq = (size_t)e->Qcur;
+  e->h_range_count.resize(nq); e->h_range_offered.resize(nq);
+  (void)hipSetDevice(e->device);
+  HIP_TRY(hipMemcpy(e->h_range_count.data(), e->d_range_count, nq * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(e->h_range_offered.data(), e->d_offered, nq * 4, hipMemcpyDeviceToHost));
+  uint64_t trunc = 0;
+  for (size_t i = 0; i < nq; ++i) trunc += e->h_range_offered[i] > (uint32_t)e->range_hits;
+  e->stat_range_truncated = trunc;
+  e->range_counts_valid = true;
+  return BANG_OK;
+}
+
+extern "C" int bang_get_range_counts(bang_engine_t* e, uint32_t* counts, uint32_t* offered, uint32_t num_queries) {
+  if (!e) return BANG_ERR_ARG;
+  BANG_TRY(range_counts(e, "bang_get_range_counts"));
+  if (num_queries > (uint32_t)e->Qcur) { bang_set_error("bang_get_range_counts: %u counts asked for, the last batch had %d queries", num_queries, e->Qcur); return BANG_ERR_ARG; }
+  if (counts) memcpy(counts, e->h_range_count.data(), (size_t)num_queries * 4);
+  if (offered) memcpy(offered, e->h_range_offered.data(), (size_t)num_queries * 4);
+  return BANG_OK;
+}
+
+extern "C" int bang_get_range_results(bang_engine_t* e, uint64_t* lims, uint64_t* ids, float* dists, uint64_t capacity) {
+  if (!e || !lims) return BANG_ERR_ARG;
+  BANG_TRY(range_counts(e, "bang_get_range_results"));
+  const size_t nq = (size_t)e->Qcur;
+  uint64_t total = 0;
+  uint32_t width = 0;
+  for (size_t i = 0; i < nq; ++i) { total += e->h_range_count[i]; width = std::max(width, e->h_range_count[i]); }
+  if (capacity < total) { bang_set_error("bang_get_range_results: capacity = %llu, the last batch has %llu hits", (unsigned long long)capacity, (unsigned long long)total); return BANG_ERR_ARG; }
+  if (total != 0 && (!ids || !dists)) { bang_set_error("bang_get_range_results: ids / dists is null"); return BANG_ERR_ARG; }
+  if (width != 0) {
+    // ONE strided copy per array: the first `width` columns -- the largest count -- of the batch's rows, then packed on the host
+    const size_t pitch = (size_t)e->range_hits * 4;
+    std::vector<uint32_t> hid(nq * width), hd(nq * width);
+    HIP_TRY(hipMemcpy2D(hid.data(), (size_t)width * 4, e->d_hit_ids, pitch, (size_t)width * 4, nq, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(hd.data(), (size_t)width * 4, e->d_hit_dists, pitch, (size_t)width * 4, nq, hipMemcpyDeviceToHost));
+    uint64_t at = 0;
+    for (size_t i = 0; i < nq; ++i) {
+      const uint32_t c = e->h_range_count[i];
+      for (uint32_t j = 0; j < c; ++j) ids[at + j] = (uint64_t)hid[i * width + j];
+      memcpy(dists + at, hd.data() + i * width, (size_t)c * 4);
+      at += c;
+    }
+  }
+  lims[0] = 0;
+  for (size_t i = 0; i < nq; ++i) lims[i + 1] = lims[i] + e->h_range_count[i];
   return BANG_OK;
 }
 
@@ -424,6 +504,10 @@ extern "C" int bang_query_dev_e(bang_engine_t* e, const void* h_queries, int Q, 
 static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* h_ids, float* h_dists, uint64_t* d_ids_user, float* d_dists_user) {
   if (!e->allocated || !e->inited) { bang_set_error("bang_query: bang_alloc + bang_init must precede every query"); return BANG_ERR_ARG; }
   if (Q <= 0 || Q > e->Qcap) { bang_set_error("bang_query: numQueries %d exceeds allocation %d", Q, e->Qcap); return BANG_ERR_ARG; }
+  if (e->n_radii != 0 && (uint32_t)Q != e->n_radii) {
+    bang_set_error("bang_query: a batch of %d queries, but the radii were set for %u (bang_set_query_radii_e; bang_clear_query_radii_e drops them)", Q, e->n_radii);
+    return BANG_ERR_ARG;
+  }
   if (e->n_qfilters != 0 && (uint32_t)Q != e->n_qfilters) {
     bang_set_error("bang_query: a batch of %d queries, but the filters were set for %u (bang_set_query_filters_e; bang_clear_query_filters_e drops them)", Q, e->n_qfilters);
     return BANG_ERR_ARG;
@@ -496,6 +580,10 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   e->stat_label_launches = 0;
   for (auto& lp : e->lanes) e->stat_label_launches += lp->label_launches;
   e->stat_filtered_queries = e->stat_label_launches != 0 ? e->n_filtered : 0;
+  e->stat_range_launches = 0;
+  for (auto& lp : e->lanes) e->stat_range_launches += lp->range_launches;
+  e->stat_range_queries = e->stat_range_launches != 0 ? (uint64_t)Q : 0;
+  e->stat_range_truncated = 0; e->range_counts_valid = false;       // (counted when the batch's counts are fetched: bang_get_stats_ext4)
   s.persistent = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
   s.vectors_on_device = e->vec_on_device ? 1 : 0;
   s.graph_mode = (uint64_t)e->graph_mode;
@@ -625,6 +713,17 @@ extern "C" int bang_get_stats_ext3(bang_engine_t* e, bang_stats_ext3* out) {
   out->labelled = e->d_labels ? (uint64_t)e->N : 0;
   out->filtered_queries = e->stat_filtered_queries;
   out->label_launches = e->stat_label_launches;
+  return BANG_OK;
+}
+
+extern "C" int bang_get_stats_ext4(bang_engine_t* e, bang_stats_ext4* out) {
+  if (!e || !out) return BANG_ERR_ARG;
+  BANG_TRY(bang_get_stats_ext3(e, &out->ext3));
+  if (e->allocated && e->stat_range_launches != 0) BANG_TRY(range_counts(e, "bang_get_stats_ext4"));     // (range_truncated needs the batch's counts)
+  out->range_hits = e->range_hits > 0 ? (uint64_t)e->range_hits : 0;
+  out->range_queries = e->stat_range_queries;
+  out->range_launches = e->stat_range_launches;
+  out->range_truncated = e->stat_range_launches != 0 ? e->stat_range_truncated : 0;
   return BANG_OK;
 }
 

@@ -96,6 +96,7 @@ struct Lane {
   uint64_t front_launches = 0;
   uint64_t exclude_launches = 0;      // bang_k_cand_live / bang_k_worklist_pick launches of the last run
   uint64_t label_launches = 0;        // bang_k_search_exact_labels launches of the last run
+  uint64_t range_launches = 0;        // bang_k_search_exact_range launches of the last run
   double walker_ms = 0, front_ms = 0, back_ms = 0, rerank_ms = 0, sync_ms = 0, enqueue_ms = 0;
 };
 
@@ -315,6 +316,18 @@ struct bang_engine {
   std::vector<uint32_t> qfilter_file_rows;   // BANG_QUERY_FILTER_FILE as read for this allocation ({any, all} per row); empty = not read yet
   bool qfilters_from_file = false;     // the filters in HBM are the file's first n_qfilters rows
   uint64_t stat_filtered_queries = 0, stat_label_launches = 0;   // bang_stats_ext3 of the last bang_query
+  // range search (option range_hits + bang_set_query_radii_e): the hit buffers live from bang_alloc to bang_free, the radii from
+  // bang_set_query_radii_e to bang_free
+  int range_hits = 0;                  // option "range_hits": capacity of a query's hit log, 0 = off
+  uint32_t* d_hit_ids = nullptr;       // [Qcap][range_hits] the hit log's ids; sorted and de-duplicated in place by bang_k_range_sort
+  float* d_hit_dists = nullptr;        // [Qcap][range_hits] ... and distances
+  float* d_radius = nullptr;           // [Qcap] the batch's radii
+  uint32_t* d_offered = nullptr;       // [Qcap] hits offered to each query's log
+  uint32_t* d_range_count = nullptr;   // [Qcap] hits that remain behind the sort
+  uint32_t n_radii = 0;                // queries the radii were set for; 0 = no radii: today's launches
+  uint64_t stat_range_queries = 0, stat_range_launches = 0, stat_range_truncated = 0;   // bang_stats_ext4 of the last bang_query
+  std::vector<uint32_t> h_range_count, h_range_offered;   // the last range batch's counts, fetched once (bang_get_range_counts / _results)
+  bool range_counts_valid = false;
 };
 
 // bang_search.hip, part 2 (semantics = 1): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride

@@ -94,6 +94,10 @@ int bang_k_search_exact_beam_pull(const bang_search_params* p, uint32_t beam, vo
 // BANG_EXACT_PULL, bang_search_exact_labels_pull.o), handed bang_k_search_exact_labels' checked arguments
 int bang_k_search_exact_labels_hbm(const bang_search_params* p, const bang_label_filter* f, void* stream);
 int bang_k_search_exact_labels_pull(const bang_search_params* p, const bang_label_filter* f, void* stream);
+// the range-search instances (the same source built with BANG_EXACT_RANGE as bang_search_exact_range.o and, with BANG_EXACT_PULL,
+// bang_search_exact_range_pull.o), handed bang_k_search_exact_range's checked arguments
+int bang_k_search_exact_range_hbm(const bang_search_params* p, const bang_range_out* r, void* stream);
+int bang_k_search_exact_range_pull(const bang_search_params* p, const bang_range_out* r, void* stream);
 // BANG_QUERY_FILTER_FILE (bang_cabi.cpp), for the bang.h class alone: applies the file's first num_queries rows as the filters of the batch about to
 // run (bang_set_query_filters_e); no-op without the variable.  The file is read once per allocation
 int bang_apply_query_filter_file_e(bang_engine_t* e, int num_queries);

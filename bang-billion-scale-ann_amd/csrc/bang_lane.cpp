@@ -79,7 +79,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
   const uint32_t cap_iter = (uint32_t)e->L + (e->search_inmem ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS) - 1;   // :950 (semantics = 1: L + 119)
   if (ln.kt_used) { (void)hipMemset(ln.d_ktime, 0, ln.kt_used * KT_WGS * 16); ln.kt_used = 0; }   // stats not collected
   if (e->h_fin.size() >= (size_t)ln.q0 + ln.nq) memset(e->h_fin.data() + ln.q0, 0, ln.nq);
-  ln.h2d_bytes.store(0); ln.iterations = 0; ln.front_launches = 0; ln.exclude_launches = 0; ln.label_launches = 0; ln.walker_ms = 0; ln.sync_ms = 0; ln.enqueue_ms = 0;
+  ln.h2d_bytes.store(0); ln.iterations = 0; ln.front_launches = 0; ln.exclude_launches = 0; ln.label_launches = 0; ln.range_launches = 0; ln.walker_ms = 0; ln.sync_ms = 0; ln.enqueue_ms = 0;
   auto t_enq = Clock::now();
 #define ENQ_BEGIN() (t_enq = Clock::now())
 #define ENQ_END() (ln.enqueue_ms += ms_since(t_enq))
@@ -210,7 +210,16 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
     sp.max_waves = (uint32_t)std::max(0L, env_long("BANG_SEARCH_MAX_WAVES", 0));
     e->rerank_fused = false;
     ENQ_BEGIN();
-    if (filtered) {
+    // per-query radii (bang_set_query_radii_e): the same walk and the same results -- the pick behind the launch included -- and the
+    // hit log beside them, sorted and de-duplicated behind the launch
+    const bool ranged = e->n_radii != 0;
+    if (ranged) {
+      bang_range_out ro;
+      ro.d_radius = e->d_radius; ro.d_excluded = masked ? e->d_excl : nullptr; ro.d_hit_ids = e->d_hit_ids; ro.d_hit_dists = e->d_hit_dists;
+      ro.d_offered = e->d_offered; ro.cap = (uint32_t)e->range_hits;
+      BANG_TRY(bang_k_search_exact_range(&sp, &ro, ln.s_main));
+      ++ln.range_launches;
+    } else if (filtered) {
       bang_label_filter lf;
       lf.d_labels = e->d_labels; lf.d_filters = e->d_qfilters; lf.d_excluded = masked ? e->d_excl : nullptr; lf.d_matched = e->d_matched;
       BANG_TRY(bang_k_search_exact_labels(&sp, &lf, ln.s_main));
@@ -222,6 +231,7 @@ int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, f
                                     pick_ids, pick_dists, ln.s_main));
       ++ln.exclude_launches;
     }
+    if (ranged) BANG_TRY(bang_k_range_sort(e->d_hit_ids, e->d_hit_dists, e->d_offered, (uint32_t)e->range_hits, ln.q0, ln.nq, (uint32_t)Q, e->d_range_count, ln.s_main));
     ENQ_END();
     ++ln.front_launches;
     iter = cap_iter;                                                         // refined from the per-query counts below

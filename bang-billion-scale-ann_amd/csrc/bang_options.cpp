@@ -67,6 +67,11 @@ static const OptionDef kOptions[] = {
      "distance = 1 only: parents expanded per iteration.  1 = one, today's walk (default).  2..4: the rows of up to beam parents are filtered against the "
      "filter state at the iteration's entry, ids that survive in two rows are kept once, the rows are merged one by one, then the first beam unvisited "
      "worklist entries are expanded together.  Refused: distance = 0, semantics = 1, vectors_fp16 = 1 and the wide layouts (D > 256, 8-bit D / 16 not a power of two)"},
+    {"range_hits", "BANG_RANGE_HITS", &bang_engine::range_hits, 0, 4096, INT, BEFORE_ALLOC,
+     "distance = 1 only: range search.  > 0 = bang_alloc holds a hit log of this many entries per query; a batch with radii (bang_set_query_radii_e) runs "
+     "the same walk and returns, beside its k results, every evaluated node within the query's radius (squared L2), sorted by distance then id "
+     "(bang_get_range_results); the first range_hits hits in evaluation order are kept, bang_get_range_counts tells when there were more.  Refused: "
+     "distance = 0, beam > 1, vectors_fp16 = 1 and the wide layouts (D > 256, 8-bit D / 16 not a power of two).  0 = off (default)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

@@ -46,6 +46,12 @@
 //    merged into the worklist, those that match -- and are not in the exclusion bitmap -- are compacted in input order, with the distance bits the
 //    walk computed, and go through the same sort_and_merge into the result list.  The results are the first k entries of that list
 //    (CANON 18).  Everything it adds sits under BANG_EXACT_LABELS.
+//  * RANGE SEARCH (BANG_EXACT_RANGE, with and without BANG_EXACT_PULL; the narrow layouts only; entry bang_k_search_exact_range).  The same walk,
+//    bit for bit, and the same results; beside them every query collects a HIT LOG in HBM: in EVERY iteration -- the first with its seed list and the
+//    cap iteration, whose survivors are not merged, included -- the survivors with distance <= d_radius[query] that are not in the exclusion bitmap are
+//    compacted in input order (__ballot + lanes_below, element 64 behind the first 64) and written, id and distance bits, to the query's row of
+//    d_hit_ids / d_hit_dists while positions < cap last; d_offered counts them all.  Two plain vector stores per hit, nothing waits for them, no
+//    LDS (CANON 19; bang_range.hip sorts the rows behind the launch).  Everything it adds sits under BANG_EXACT_RANGE.
 //
 // Reference line numbers: the reference's BANG_Base/bang_search.cu unless a file is named.
 
@@ -72,6 +78,16 @@
 #error "BANG_EXACT_LABELS builds the narrow instances on float / 8-bit rows only"
 #endif
 
+#if defined(BANG_EXACT_RANGE) && defined(BANG_EXACT_WIDE)
+#error "BANG_EXACT_RANGE builds the narrow instances only"
+#endif
+#if defined(BANG_EXACT_RANGE) && defined(BANG_EXACT_F16)
+#error "BANG_EXACT_RANGE builds the narrow instances on float / 8-bit rows only"
+#endif
+#if defined(BANG_EXACT_RANGE) && defined(BANG_EXACT_LABELS)
+#error "BANG_EXACT_RANGE and BANG_EXACT_LABELS are builds of their own: radii and label filters do not combine"
+#endif
+
 #if defined(BANG_EXACT_WIDE) && defined(BANG_EXACT_PULL)
 #define EXACT_TAG _wide_pull
 #elif defined(BANG_EXACT_WIDE)
@@ -81,6 +97,11 @@
 #elif defined(BANG_EXACT_LABELS)
 #define EXACT_TAG _labels
 #define EXACT_ENTRY bang_k_search_exact_labels_hbm
+#elif defined(BANG_EXACT_RANGE) && defined(BANG_EXACT_PULL)
+#define EXACT_TAG _range_pull
+#elif defined(BANG_EXACT_RANGE)
+#define EXACT_TAG _range
+#define EXACT_ENTRY bang_k_search_exact_range_hbm
 #elif defined(BANG_EXACT_F16)
 #define EXACT_TAG _pull_f16
 #elif defined(BANG_EXACT_PULL)
@@ -108,6 +129,9 @@ struct ExactArgs {
   uint32_t wl_words;                 // LDS words of the worklist (2L + ceil(L/4), rounded to 4)
 #ifdef BANG_EXACT_LABELS
   bang_label_filter f;               // labels, the batch's filters, the exclusion bitmap, the matched counts
+#endif
+#ifdef BANG_EXACT_RANGE
+  bang_range_out r;                  // the batch's radii, the exclusion bitmap, the hit log and its counts
 #endif
 };
 
@@ -316,6 +340,10 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
   const uint32_t GAS* labels = (const uint32_t GAS*)a.f.d_labels;
   const uint32_t GAS* excluded = (const uint32_t GAS*)a.f.d_excluded;    // or null
 #endif
+#ifdef BANG_EXACT_RANGE
+  const uint32_t GAS* excluded = (const uint32_t GAS*)a.r.d_excluded;    // or null
+  const uint32_t hit_cap = a.r.cap;
+#endif
   if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
   const uint32_t total_waves = gridDim.x * nwaves;
   const uint32_t gw = blockIdx.x * nwaves + wave;
@@ -369,6 +397,13 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
     const uint32_t f_any = uni(((const uint32_t GAS*)a.f.d_filters)[2u * qabs]), f_all = uni(((const uint32_t GAS*)a.f.d_filters)[2u * qabs + 1u]);
     uint32_t r_n = 0, matched = 0;
     float r_tail = 0.0f;                          // the result list's last distance (read while r_n > 0 only)
+#endif
+#ifdef BANG_EXACT_RANGE
+    // CANON 19: the query's radius (wave-uniform), its row of the hit log (64-bit address arithmetic) and the running count of hits offered to it
+    const float radius = __uint_as_float(uni(__float_as_uint(((const float GAS*)a.r.d_radius)[qabs])));
+    uint32_t GAS* hit_ids = (uint32_t GAS*)a.r.d_hit_ids + (uint64_t)qabs * hit_cap;
+    float GAS* hit_dists = (float GAS*)a.r.d_hit_dists + (uint64_t)qabs * hit_cap;
+    uint32_t offered = 0;
 #endif
     WlHead head;
     head.found = false; head.idx = 0; head.id = 0; head.d = 0.0f; head.tail = 0.0f;
@@ -443,6 +478,15 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       if ((uint32_t)lane < n) { lab0 = labels[sid0]; if (excluded) ex0 = excluded[sid0 >> 5]; }
       if (lane == 0 && n > 64) { lab1 = labels[sid1]; if (excluded) ex1 = excluded[sid1 >> 5]; }
 #endif
+#ifdef BANG_EXACT_RANGE
+      // the survivors' words of the exclusion bitmap: requested here, so that they travel with the vectors (with a bitmap n_nodes != 0 -- refused
+      // otherwise by bang_k_search_exact_range -- and every survivor id is < n_nodes: the check above)
+      uint32_t ex0 = 0, ex1 = 0;
+      if (excluded) {                                             // (uniform)
+        if ((uint32_t)lane < n) ex0 = excluded[sid0 >> 5];
+        if (lane == 0 && n > 64) ex1 = excluded[sid1 >> 5];
+      }
+#endif
 
       // ---------------- exact distances (CANON 10: replaces K2) ----------------
       if (n > 0) {
@@ -461,6 +505,20 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       const float d0 = ((uint32_t)lane < n) ? sdist[lane] : BIG_DIST;
       const float d1 = (lane == 0 && n > 64) ? sdist[64] : BIG_DIST;
       wave_sync();
+#ifdef BANG_EXACT_RANGE
+      // ---------------- CANON 19: the hits of this iteration (every iteration: the cap iteration too), in input order, to the query's hit log.  A plain
+      // float compare on the distance bits the walk computed (a NaN or negative radius admits nothing); fire-and-forget stores below the cap
+      {
+        const bool ht0 = (uint32_t)lane < n && d0 <= radius && ((ex0 >> (sid0 & 31u)) & 1u) == 0u;
+        const bool ht1 = lane == 0 && n > 64 && d1 <= radius && ((ex1 >> (sid1 & 31u)) & 1u) == 0u;
+        const uint64_t hm0 = __ballot(ht0), hm1 = __ballot(ht1);
+        const uint32_t nh0 = (uint32_t)__popcll(hm0);
+        const uint32_t at0 = offered + lanes_below(hm0), at1 = offered + nh0;             // (element 64 behind the first 64)
+        if (ht0 && at0 < hit_cap) { hit_ids[at0] = sid0; hit_dists[at0] = d0; }
+        if (ht1 && at1 < hit_cap) { hit_ids[at1] = sid1; hit_dists[at1] = d1; }
+        offered += nh0 + (uint32_t)__popcll(hm1);
+      }
+#endif
 
       // ---------------- K4: parent (compute_parent1 :1464-1521 / compute_parent2 :1384-1459), as bang_search.hip ----------------
       uint32_t parent = 0;
@@ -569,6 +627,9 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
     const uint32_t k = p.rr_k, Qt = p.rr_Q_total;
     uint64_t GAS* ids_out = (uint64_t GAS*)p.rr_ids_out;
     float GAS* dists_out = (float GAS*)p.rr_dists_out;
+#ifdef BANG_EXACT_RANGE
+    if (lane == 0) ((uint32_t GAS*)a.r.d_offered)[qabs] = offered;
+#endif
 #ifdef BANG_EXACT_LABELS
     if (lane == 0 && a.f.d_matched) ((uint32_t GAS*)a.f.d_matched)[qabs] = matched;
     for (uint32_t r = (uint32_t)lane; r < k; r += WAVE) {         // CANON 18: the result list where the loop below reads the worklist
@@ -616,7 +677,9 @@ static uint32_t exact_wave_words(uint32_t L) { return EXACT_LISTS * wave_wl_word
 // merge of bang_worklist.h keeps up to 8 worklist entries per lane in registers): 104 allocated, 4 waves per SIMD, 16 per CU -- one workgroup of
 // 16 waves per CU; LDS holds 16 waves' worklists up to L = 512.  The wide instances (at most 128 VGPRs, no scratch: DESIGN.md section 4.6) run 16
 // waves per CU as well, up to L = 704.  The label-filter builds compile to 114-118 VGPRs, no scratch: 120 allocated, 16 waves per CU again.  The
-// pulled-rows builds: 99-100 VGPRs narrow, 108-109 / 134 wide, no scratch -- the same waves per CU, read off the pulled instance.
+// pulled-rows builds: 99-100 VGPRs narrow, 108-109 / 134 wide, no scratch -- the same waves per CU, read off the pulled instance.  The range builds
+// (hit log in HBM, no LDS added): 97-99 VGPRs with graph entries, 99-100 with pulled rows, no scratch -- 104 allocated, 16 waves per CU, LDS as
+// the plain builds.
 extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   const void* k = exact_instance(dtype);
@@ -628,8 +691,10 @@ extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wg
 }
 
 // one launch of this translation unit's instances (the arguments are checked: bang_k_search_exact)
-#ifdef BANG_EXACT_LABELS
+#if defined(BANG_EXACT_LABELS)
 static int exact_launch(const bang_search_params* p, const bang_label_filter* f, void* stream) {
+#elif defined(BANG_EXACT_RANGE)
+static int exact_launch(const bang_search_params* p, const bang_range_out* r, void* stream) {
 #else
 static int exact_launch(const bang_search_params* p, void* stream) {
 #endif
@@ -642,6 +707,9 @@ static int exact_launch(const bang_search_params* p, void* stream) {
   a.wave_words = exact_wave_words(p->L);
 #ifdef BANG_EXACT_LABELS
   a.f = *f;
+#endif
+#ifdef BANG_EXACT_RANGE
+  a.r = *r;
 #endif
   const size_t lds = (size_t)waves * a.wave_words * 4u;
   const void* k = exact_instance((int)p->rr_dtype);
@@ -664,7 +732,15 @@ static int exact_launch(const bang_search_params* p, void* stream) {
 
 // This build's entry point (EXACT_ENTRY: bang_internal.h), called by bang_k_search_exact / bang_k_search_exact_labels (bang_wave_host.cpp) with
 // the arguments checked; what the kernel's own addressing rests on is looked at once more.
-#ifdef BANG_EXACT_LABELS
+#if defined(BANG_EXACT_RANGE)
+extern "C" int EXACT_ENTRY(const bang_search_params* p, const bang_range_out* r, void* stream) {
+  if (!p || !r || p->row_layout != (uint32_t)EXACT_PULL ||
+      !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, EXACT_PULL ? p->rr_vec_stride : p->entry_len, 0)) return BANG_ERR_ARG;
+  if (!r->d_radius || !r->d_hit_ids || !r->d_hit_dists || !r->d_offered || r->cap == 0u || r->cap > BANG_RANGE_MAX_HITS ||
+      (r->d_excluded && p->n_nodes == 0u)) return BANG_ERR_ARG;
+  return exact_launch(p, r, stream);
+}
+#elif defined(BANG_EXACT_LABELS)
 extern "C" int EXACT_ENTRY(const bang_search_params* p, const bang_label_filter* f, void* stream) {
   if (!p || !f || p->row_layout != (uint32_t)EXACT_PULL ||
       !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, EXACT_PULL ? p->rr_vec_stride : p->entry_len, 0)) return BANG_ERR_ARG;

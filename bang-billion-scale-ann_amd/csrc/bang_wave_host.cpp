@@ -97,7 +97,7 @@ extern "C" int bang_exact_check_layout(const bang_search_params* p, const char* 
   return BANG_OK;
 }
 
-// every check of a bang_k_search_exact launch (bang_k_search_exact_labels makes them too)
+// every check of a bang_k_search_exact launch (bang_k_search_exact_labels and _range make them too)
 static int exact_check(const bang_search_params* p) {
   static const char* const prefix = "distance = 1";
   int rc = bang_exact_check_args(p, prefix);
@@ -145,4 +145,30 @@ extern "C" int bang_k_search_exact_labels(const bang_search_params* p, const ban
   }
   if (p->row_layout == 1u) return bang_k_search_exact_labels_pull(p, f, stream);
   return bang_k_search_exact_labels_hbm(p, f, stream);
+}
+
+// The walk of bang_k_search_exact with a per-query radius (CANON 19): the same results, and beside them every evaluated node
+// within the radius in the query's row of the hit log.  The narrow layouts only, routed on row_layout to the instances of
+// bang_search_exact_range.o / bang_search_exact_range_pull.o
+extern "C" int bang_k_search_exact_range(const bang_search_params* p, const bang_range_out* r, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (!r) { bang_set_error("distance = 1, range: the range arguments r (bang_range_out) are null"); return BANG_ERR_ARG; }
+  if (!r->d_radius) { bang_set_error("distance = 1, range: d_radius (one radius per query) is null"); return BANG_ERR_ARG; }
+  if (!r->d_hit_ids) { bang_set_error("distance = 1, range: d_hit_ids (the hit log's ids) is null"); return BANG_ERR_ARG; }
+  if (!r->d_hit_dists) { bang_set_error("distance = 1, range: d_hit_dists (the hit log's distances) is null"); return BANG_ERR_ARG; }
+  if (!r->d_offered) { bang_set_error("distance = 1, range: d_offered (the hit counts) is null"); return BANG_ERR_ARG; }
+  if (r->cap == 0u || r->cap > BANG_RANGE_MAX_HITS) { bang_set_error("distance = 1, range: cap = %u is outside [1, %u]", r->cap, BANG_RANGE_MAX_HITS); return BANG_ERR_ARG; }
+  if (r->d_excluded && p->n_nodes == 0u) { bang_set_error("distance = 1, range: n_nodes = 0 with d_excluded set: the bitmap is indexed by node id and needs the number of nodes"); return BANG_ERR_ARG; }
+  if (p->Q == 0) return BANG_OK;
+  const int rc = exact_check(p);
+  if (rc != BANG_OK) return rc;
+  if (p->rr_vec_f16 == 1u) { bang_set_error("distance = 1, range: rr_vec_f16 = 1 (fp16 rows) has no range instance"); return BANG_ERR_UNSUPPORTED; }
+  const uint64_t stride = p->row_layout == 1u ? p->rr_vec_stride : p->entry_len;
+  if (!bang_search_can_rerank((int)p->rr_dtype, p->rr_D, stride, 0)) {
+    bang_set_error("distance = 1, range: the vector layout (dtype %u, rr_D = %u, stride %llu) runs on the wide instances, which have no range form "
+                   "(8-bit vectors need D / 16 a power of two; D <= 256)", p->rr_dtype, p->rr_D, (unsigned long long)stride);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  if (p->row_layout == 1u) return bang_k_search_exact_range_pull(p, r, stream);
+  return bang_k_search_exact_range_hbm(p, r, stream);
 }

@@ -204,6 +204,30 @@ int bang_clear_labels_e(bang_engine_t* e);
 int bang_set_query_filters_e(bang_engine_t* e, const uint32_t* any, const uint32_t* all, int nq);
 int bang_clear_query_filters_e(bang_engine_t* e);
 int bang_get_matched_counts(bang_engine_t* e, uint32_t* out, uint32_t num_queries);
+
+/* RANGE SEARCH (DESIGN.md section 2 CANON 19, section 4.14; option range_hits, distance = 1): "every point within distance r of the query", a variable
+ * number of results per query.  With option range_hits = cap (1 .. 4096) bang_alloc_e holds a hit log of cap entries per query, and a batch that
+ * runs with RADII collects, beside its k results, every node its walk EVALUATES whose squared L2 distance is <= the query's radius and that is not in
+ * the engine's exclusion set.  The walk is the one without radii, bit for bit: the k ids and distance bits, the four per-query counters and the
+ * candidate log are those of the same batch without radii.  Hits are taken in every iteration, the first (seed list) and the cap iteration (evaluated,
+ * not merged) included; the compare is a plain float compare on the distance bits the walk computed, so a NaN or negative radius gives a query with
+ * no range and +inf takes every evaluated node.  The first cap hits in evaluation order are kept; behind the launch each query's kept hits are sorted
+ * ascending by (distance bits, id) and adjacent equal entries -- an id that an adjacency row lists twice -- dropped (bang_k_search_exact_range +
+ * bang_k_range_sort).  Recall of the answer depends on L, as for top-k; nothing grows L automatically: offered / count tell a caller when to.
+ * bang_set_query_radii_e sets the radii of the batches to come, nq of them (row i for query i): valid while an allocation is live, refused with
+ * range_hits = 0, nq <= the allocated batch size, nq = 0 clears; copied to HBM and kept until replaced, cleared or bang_free_e.  bang_query_e /
+ * bang_query_dev_e refuse a batch whose size differs from nq ("radii" in the message).  Radii and label filters together are refused, at whichever
+ * of the two setters comes second.  An allocation with range_hits set and no radii runs today's launches unchanged.  bang_alloc_e refuses
+ * range_hits > 0, with "range" in the message and no fallback, with distance = 0, beam > 1, vectors_fp16 = 1 or a vector layout of the wide instances.
+ * bang_get_range_counts: per query of the last batch with radii, count = the hits in its answer and offered = all hits its walk met
+ * (offered > cap: the answer was truncated to the first cap in evaluation order); either pointer may be NULL.
+ * bang_get_range_results: the answers of that batch packed CSR in query order: lims[0] = 0, query q's hits at [lims[q], lims[q + 1]) of ids (u64, as
+ * the top-k ids) and dists; lims has (queries of the batch) + 1 entries.  capacity = the entries ids / dists hold: below lims[nq] is BANG_ERR_ARG
+ * and nothing is written. */
+int bang_set_query_radii_e(bang_engine_t* e, const float* radii, int nq);
+int bang_clear_query_radii_e(bang_engine_t* e);
+int bang_get_range_counts(bang_engine_t* e, uint32_t* counts, uint32_t* offered, uint32_t num_queries);
+int bang_get_range_results(bang_engine_t* e, uint64_t* lims, uint64_t* ids, float* dists, uint64_t capacity);
 int bang_unload_e(bang_engine_t* e);                                                        /* bang.h:82 */
 
 /* statistics of the last bang_query_e */
@@ -279,6 +303,15 @@ typedef struct {
   uint64_t label_launches;    /* launches of bang_k_search_exact_labels of the last bang_query_e (0 without filters) */
 } bang_stats_ext3;
 int bang_get_stats_ext3(bang_engine_t* e, bang_stats_ext3* out);
+/* ... and once more for range search (option range_hits + bang_set_query_radii_e): the earlier structs keep size and offsets */
+typedef struct {
+  bang_stats_ext3 ext3;
+  uint64_t range_hits;        /* option range_hits: the capacity of a query's hit log, 0 = off */
+  uint64_t range_queries;     /* queries of the last bang_query_e that ran with a radius */
+  uint64_t range_launches;    /* launches of bang_k_search_exact_range of the last bang_query_e (0 without radii) */
+  uint64_t range_truncated;   /* ... of those queries, how many met more hits than the log holds (offered > range_hits) */
+} bang_stats_ext4;
+int bang_get_stats_ext4(bang_engine_t* e, bang_stats_ext4* out);
 /* Per-query counters of the last bang_query_e (arrays of num_queries words; any pointer may be NULL): PQ distance evaluations,
  * adjacency ids offered to the filter, expanded nodes (candidate-log length) and -- search kernel only, else zeros -- the number
  * of iterations the query ran.  Test hook: the oracle reports the same four numbers per query. */
@@ -673,6 +706,44 @@ int bang_k_search_exact_labels(const bang_search_params* p, const bang_label_fil
  * register count that of the label-filter instance; the second one for the pulled-rows form (row_layout = 1) */
 int bang_search_exact_labels_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 int bang_search_exact_labels_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+
+/* RANGE SEARCH on the exact-distance walk (csrc/bang_search_exact.hip built as bang_search_exact_range.o / bang_search_exact_range_pull.o; engine:
+ * option range_hits + bang_set_query_radii_e; DESIGN.md section 2, CANON 19).  The walk and the results are bang_k_search_exact's, bit for bit --
+ * filter, parent, worklist, the L + 49 cap, candidate log, counters, the k results (rr_k = L with bang_k_worklist_pick behind the launch works as
+ * ever).  Beside them query q collects a HIT LOG: in EVERY iteration, the first with its up-to-65-id seed list and the cap iteration (whose
+ * survivors are evaluated but not merged) included, each survivor x with dist(x) <= d_radius[rr_q0 + q] -- a plain float compare on the squared-L2
+ * bits the walk computed, so a NaN or negative radius admits nothing and +inf every evaluated node -- that is not in d_excluded is appended in
+ * input order (element 64 of the seed list behind the first 64): id to d_hit_ids[(rr_q0 + q) * cap + i], distance bits to d_hit_dists at the same
+ * place, for the first `cap` hits in evaluation order; d_offered[rr_q0 + q] counts ALL hits (offered > cap: the row was truncated).  An id that a
+ * row lists twice is evaluated twice and logged twice; bang_k_range_sort drops the copy.  Row positions at and behind min(offered, cap) are not
+ * written.
+ * bang_search_params is what it is for bang_k_search_exact (no member added or moved); the new arguments travel beside it.  Routed on row_layout to
+ * search_exact_range_kernel (0) / search_exact_range_pull_kernel (1).  Every check of bang_k_search_exact is made, before any HIP call; refused in
+ * addition, with the member named: r, d_radius, d_hit_ids, d_hit_dists or d_offered null, cap = 0 or cap > BANG_RANGE_MAX_HITS, d_excluded set
+ * with n_nodes == 0 -- the bitmap is indexed by node id -- (BANG_ERR_ARG); rr_vec_f16 = 1 and the layouts of the wide instances, i.e. those
+ * bang_search_can_rerank refuses (BANG_ERR_UNSUPPORTED). */
+#define BANG_RANGE_MAX_HITS 4096u
+typedef struct {
+  const float*    d_radius;    /* [rr_Q_total]; row rr_q0 + q is this launch's query q */
+  const uint32_t* d_excluded;  /* bitmap as bang_k_worklist_pick reads it, or NULL */
+  uint32_t*       d_hit_ids;   /* [rr_Q_total][cap] out */
+  float*          d_hit_dists; /* [rr_Q_total][cap] out */
+  uint32_t*       d_offered;   /* [rr_Q_total] out */
+  uint32_t        cap;         /* 1 .. BANG_RANGE_MAX_HITS (4096) */
+} bang_range_out;
+int bang_k_search_exact_range(const bang_search_params* p, const bang_range_out* r, void* stream);
+/* grid of a bang_k_search_exact_range launch, as bang_search_exact_geometry (the hit log lives in HBM: LDS per wave is the plain build's), the
+ * register count that of the range instance; the second one for the pulled-rows form (row_layout = 1) */
+int bang_search_exact_range_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+int bang_search_exact_range_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+/* bang_k_range_sort (csrc/bang_range.hip, range_sort_kernel), behind a bang_k_search_exact_range launch on the same stream: for the queries
+ * q0 .. q0 + nq - 1, the n = min(d_offered[q], cap) hits of row q are sorted ascending by the 64-bit key (distance bits << 32) | id -- squared
+ * distances are non-negative, so their bit patterns order like the floats; equal distances order by id -- adjacent equal keys are dropped, the row
+ * is written back in place and d_count[q] = what remains.  One wave per query; a row of more than 64 keys is sorted in 8 x (n rounded up to a power of two)
+ * bytes of LDS, at most 32 KB.  Checked before any HIP call, with the argument named (BANG_ERR_ARG): a null buffer, cap = 0 or
+ * cap > BANG_RANGE_MAX_HITS, Q_total < q0 + nq.  nq = 0 is no launch. */
+int bang_k_range_sort(uint32_t* d_hit_ids, float* d_hit_dists, const uint32_t* d_offered, uint32_t cap, uint32_t q0, uint32_t nq, uint32_t Q_total,
+                      uint32_t* d_count, void* stream);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
