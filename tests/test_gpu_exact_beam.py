@@ -160,7 +160,8 @@ def test_launch_shape_does_not_change_results(name, W, pulled, request, monkeypa
 
 
 def test_longest_worklist(small_u8):
-    """L = 512 with k = L: sixteen waves' worklists and survivor arrays still fit LDS."""
+    """L = 512 with k = L, the whole worklist compared.  Four queries launch as four workgroups of one wave; sixteen waves' worklists and survivor
+    arrays side by side in one workgroup's LDS run in tests/test_gpu_launch_shapes.py (test_beam_longest_worklist)."""
     ix, q = E.tie_heavy(*small_u8[:2], n_queries=4)
     with _engine(ix, 4) as e:
         _assert_same(_run(e, q, 512, 512), _reference(("tie_heavy", 4), ix, q, 512, 4))

@@ -223,7 +223,10 @@ def test_with_an_exclusion_set(small_u8, form, mask):
 
 @pytest.mark.parametrize("form", list(FORMS))
 def test_one_wave_per_workgroup(small_u8, monkeypatch, form):
+    """One workgroup of one wave runs every query in turn (the wave cap alone repeats the default launch: 32 queries are 32 one-wave workgroups
+    already).  Full workgroups: tests/test_gpu_launch_shapes.py."""
     ix, q, _, _ = small_u8
+    monkeypatch.setenv("BANG_SEARCH_MAX_WGS", "1")
     monkeypatch.setenv("BANG_SEARCH_MAX_WAVES", "1")
     _case("small_u8", ix, np.ascontiguousarray(q[:NQ]), FORMS[form], (37,), _named_cases("small_u8", ("rank100", "rank400", "mixed")))
 
