@@ -1,4 +1,5 @@
-// bang_alloc.cpp -- bang_alloc / bang_free (bang_search.cu:370-425): per-batch buffers, lanes and the choice of the loop form.
+// bang_alloc.cpp -- bang_alloc / bang_free (bang_search.cu:370-425): the choice of the loop form (resolve_form: policy and refusals, no allocation),
+// then the per-batch buffers and lanes (alloc_buffers).
 // Reference line numbers: /root/reference/BANG_Base/bang_search.cu.
 #include "bang_engine.h"
 
@@ -57,33 +58,21 @@ void free_batch(bang_engine* e) {
     HIP_TRY(_a);                                                           \
   } while (0)
 
-int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validated the pull rows)
-  const size_t L = (size_t)e->L, nq = (size_t)Q;
-  const size_t rows = L + (e->semantics == 1 ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS);   // uMAX_PARENTS_PERQUERY :370 (BANG_Inmemory/parANN.cu:30)
-  const size_t vb = vec_bytes(e);
+// The PQ search kernel holds the pivot table in LDS beside its waves' worklists: take whichever table (padded / exact-size) leaves room for
+// more waves (-> e->pq_nhi).  False, e->pq_nhi untouched, where neither leaves enough: one wave where search = 1 was given, four on "auto"
+static bool pick_pivot_table(bang_engine* e) {
+  const int w_pad = bang_search_supported(e->psz, e->mp, 0, (uint32_t)e->L);
+  const int w_rag = e->pq_nhi_avail ? bang_search_supported(e->psz, e->mp, e->pq_nhi_avail, (uint32_t)e->L) : 0;
+  if (std::max(w_pad, w_rag) < (e->search_opt == 1 ? 1 : 4)) return false;
+  e->pq_nhi = (w_rag > w_pad) ? e->pq_nhi_avail : 0;
+  return true;
+}
+
+// The loop form of this allocation: e->form with its modifiers search_inmem / search_wordfilter, the pivot table (pq_nhi) and walker_rows.
+// Decides and refuses, allocates nothing; the checks run in a fixed order and the caller sees the first refusal that applies.  Reads
+// stage_mode_eff, which alloc_buffers resolves first (BAR mode needs fine-grained device memory)
+static int resolve_form(bang_engine* e) {
   const bool dev_graph = (e->graph_mode == BANG_GRAPH_DEVICE);
-  const size_t slots_cap = std::max<size_t>(nq, 8 * 16 * KT_WGS);   // rows / parent words: one per query, or one per context slot of the search kernel
-  if (e->stage_zero_copy < 0) {                          // CPU-writable device memory (large BAR)?
-    int large_bar = 0;
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev_id) != hipSuccess) large_bar = 0;
-    e->stage_mode_eff = large_bar ? 2 : 1;
-  } else e->stage_mode_eff = e->stage_zero_copy;
-  // BAR mode: the CPU writes the staged rows into device memory while kernels read them.  That is only sound on FINE-GRAINED
-  // (host-coherent) device memory: on ordinary coarse-grained memory PCIe writes do not probe the per-XCD L2, so a persistent
-  // launch (no kernel boundary between two reads of a row) could be served a stale line.  No fine-grained memory -> no BAR mode.
-  e->stage_local = false;
-  if (!dev_graph && e->stage_mode_eff == 2) {
-    if (hipExtMallocWithFlags((void**)&e->d_stage, slots_cap * BANG_STAGE_STRIDE * 4, hipDeviceMallocFinegrained) == hipSuccess) {
-      e->stage_local = true;
-    } else {
-      (void)hipGetLastError();
-      e->d_stage = nullptr;
-      e->stage_mode_eff = 1;
-      fprintf(stderr, "[bang] fine-grained device memory unavailable: staged rows stay in mapped host memory (stage_zero_copy=1)\n");
-    }
-  }
   // persistent search kernel: host graph, in-kernel completion flags, rows readable in place (BAR or zero-copy), and room in
   // LDS for the pivot table plus the merge scratch of all waves (otherwise: the launch-per-iteration loop)
   // (mapped-host rows need cache-bypassing loads, which are issued per lane: measured 2x slower than the per-iteration loop,
@@ -91,16 +80,10 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   const bool persist_want = e->persistent < 0 ? (e->stage_mode_eff == 2) : (e->persistent != 0);   // host graph: one launch per batch?
   e->pq_nhi = 0;
   // graph in HBM: the query-resident search kernel, with whichever pivot table (padded / exact-size) leaves LDS for more waves
-  e->search_v2 = false;
+  e->form = LoopForm::PerIteration;
   const bool walk_rows_want = !dev_graph && e->pull && e->walker_opt == 1;          // rows exist, but the walker team is to serve them
-  if ((dev_graph || (e->pull && !walk_rows_want)) && e->persistent != 0 && e->search_opt != 0 && e->psz != 0) {
-    const int w_pad = bang_search_supported(e->psz, e->mp, 0, (uint32_t)e->L);
-    const int w_rag = e->pq_nhi_avail ? bang_search_supported(e->psz, e->mp, e->pq_nhi_avail, (uint32_t)e->L) : 0;
-    if (std::max(w_pad, w_rag) >= (e->search_opt == 1 ? 1 : 4)) {
-      e->search_v2 = true;
-      e->pq_nhi = (w_rag > w_pad) ? e->pq_nhi_avail : 0;
-    }
-  }
+  if ((dev_graph || (e->pull && !walk_rows_want)) && e->persistent != 0 && e->search_opt != 0 && e->psz != 0 && pick_pivot_table(e))
+    e->form = LoopForm::SelfPaced;
   // filter_layout = 1: the word-local visited filter on the self-paced search kernel (bang_k_search_wf).  Every configuration that does not end
   // on that kernel is refused: there is no fallback to the split layout
   e->search_wordfilter = false;
@@ -123,7 +106,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       bang_set_error("option filter_layout = 1 (word): no kernel instance for the pivot layout psz = %u, mp = %u", e->psz, e->mp);
       return BANG_ERR_UNSUPPORTED;
     }
-    if (!e->search_v2) {
+    if (e->form != LoopForm::SelfPaced) {
       bang_set_error("option filter_layout = 1 (word): the pivot table and %s worklist do not fit LDS at L = %d", e->search_opt == 1 ? "one wave's" : "four waves'", e->L);
       return BANG_ERR_UNSUPPORTED;
     }
@@ -132,7 +115,6 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   // distance = 1: the exact-distance search kernel (bang_search_exact.hip) -- self-paced, one launch per batch; graph entries in HBM, or, where
   // pull = 1 was asked for explicitly, the pulled-rows form: adjacency rows from pinned host memory / the HBM row copy / a peer's slice, vectors
   // from the packed table in HBM.  What it cannot run is refused: there is no PQ fallback
-  e->search_exact = false;
   if (e->beam > 1) {                                                                 // (a beam belongs to the exact-distance walk alone)
     if (e->distance != 1) { bang_set_error("option beam = %d needs distance = 1 (exact): the PQ walks expand one parent per iteration", e->beam); return BANG_ERR_UNSUPPORTED; }
     if (e->semantics == 1) { bang_set_error("option beam = %d is not available with semantics = 1 (inmemory): it belongs to distance = 1 (exact)", e->beam); return BANG_ERR_UNSUPPORTED; }
@@ -177,8 +159,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
         return BANG_ERR_UNSUPPORTED;
       }
     }
-    e->search_exact = true;
-    e->search_v2 = false;
+    e->form = LoopForm::Exact;                                                       // (whatever the PQ kernel could have run)
     e->pq_nhi = 0;
   }
   // range_hits > 0: range search (bang_k_search_exact_range) -- the narrow layouts of the exact-distance walk on float / 8-bit rows.  What it cannot
@@ -208,7 +189,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     if (e->distance != 0) { bang_set_error("option semantics = 1 (inmemory) is not available with distance = 1 (exact)"); return BANG_ERR_UNSUPPORTED; }
     if (e->distfn != BANG_DIST_L2) { bang_set_error("option semantics = 1 (inmemory) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
     if (e->psz == 0) { bang_set_error("option semantics = 1 (inmemory) needs the LDS-resident pivot table (the LUT path, pq = 1, has no such kernel)"); return BANG_ERR_UNSUPPORTED; }
-    if (!e->search_v2) {
+    if (e->form != LoopForm::SelfPaced) {
       bang_set_error("option semantics = 1 (inmemory): the pivot table and one wave's worklist do not fit LDS at L = %d", e->L);
       return BANG_ERR_UNSUPPORTED;
     }
@@ -221,36 +202,64 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   }
   // LUT path (psz == 0: wide chunks, a pivot table too large for LDS, pq = 1) with the graph in HBM: the query-resident kernel of
   // bang_search_lut.hip, where search = 1 was asked for explicitly -- "auto" keeps the launch-per-iteration loop on these layouts
-  e->search_lut = dev_graph && e->persistent != 0 && e->search_opt == 1 && e->psz == 0 && !e->search_exact &&
-                  bang_search_lut_supported(e->m, (uint32_t)e->L) != 0;
+  // (psz == 0: the self-paced PQ form, which needs a pivot table in LDS, was not chosen above)
+  if (dev_graph && e->persistent != 0 && e->search_opt == 1 && e->psz == 0 && e->form != LoopForm::Exact && bang_search_lut_supported(e->m, (uint32_t)e->L) != 0)
+    e->form = LoopForm::Lut;
   // graph in host RAM: the host-paced form of the same kernel, where the walker can write device memory (BAR mode)
-  e->search_host = false;
-  if (!dev_graph && !e->search_v2 && !e->search_exact && persist_want && e->use_flag && e->stage_mode_eff == 2 && e->search_opt != 0 && e->psz != 0) {
-    const int w_pad = bang_search_supported(e->psz, e->mp, 0, (uint32_t)e->L);
-    const int w_rag = e->pq_nhi_avail ? bang_search_supported(e->psz, e->mp, e->pq_nhi_avail, (uint32_t)e->L) : 0;
-    if (std::max(w_pad, w_rag) >= (e->search_opt == 1 ? 1 : 4)) {
-      e->search_host = true;
-      e->pq_nhi = (w_rag > w_pad) ? e->pq_nhi_avail : 0;
-    }
-  }
+  // (psz != 0: not the LUT form either -- nothing but the launch-per-iteration loop is replaced here)
+  if (!dev_graph && e->form != LoopForm::SelfPaced && e->form != LoopForm::Exact && persist_want && e->use_flag && e->stage_mode_eff == 2 && e->search_opt != 0 &&
+      e->psz != 0 && pick_pivot_table(e))
+    e->form = LoopForm::HostPaced;
   // the walker team of the host-paced kernel reads the pull rows where they exist (vectors are resident then: nothing else of a graph entry
   // is needed) -- the north-star data flow without a resident graph image
-  e->walker_rows = e->search_host && e->pull && e->h_adj && e->vec_on_device;
+  e->walker_rows = e->form == LoopForm::HostPaced && e->pull && e->h_adj && e->vec_on_device;
   if (walk_rows_want && !e->walker_rows) {
     bang_set_error("option walker = 1: the host-paced search kernel is not available here (needs CPU-writable device memory, persistent != 0, search != 0)");
     return BANG_ERR_UNSUPPORTED;
   }
   // a walker form on an index whose graph entries only passed through at load time: map the graph file now (a streamed load
   // from an entry source has nothing to map: error)
-  if (!dev_graph && !e->search_v2 && !e->search_exact && !e->walker_rows && !e->graph) BANG_TRY(map_graph_file(e));
+  if (!dev_graph && e->form != LoopForm::SelfPaced && e->form != LoopForm::Exact && !e->walker_rows && !e->graph) BANG_TRY(map_graph_file(e));
   // excluded ids (bang_set_excluded_e): the re-rank then reads the candidate log WITHOUT its excluded entries, a compacted list -- which only the
   // forms that find a candidate's vector by its id can take (graph entries or the vector table in HBM).  Where the vectors travel in a log, their
   // rows are found by a candidate's position in the candidate log, which compaction would break: refused, there is no unmasked fallback
-  if (e->n_excl != 0 && !e->search_exact && !dev_graph && !e->vec_on_device) {
+  if (e->n_excl != 0 && e->form != LoopForm::Exact && !dev_graph && !e->vec_on_device) {
     bang_set_error("an engine with excluded ids needs the full-precision vectors resident in HBM (graph = device, or graph = host with vectors = 1): "
-                   "this form re-ranks from a vector log (%s), whose rows are indexed by log position", e->search_host ? "by query" : "by iteration");
+                   "this form re-ranks from a vector log (%s), whose rows are indexed by log position", e->form == LoopForm::HostPaced ? "by query" : "by iteration");
     return BANG_ERR_UNSUPPORTED;
   }
+  return BANG_OK;
+}
+
+int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validated the pull rows)
+  const size_t L = (size_t)e->L, nq = (size_t)Q;
+  const size_t rows = L + (e->semantics == 1 ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS);   // uMAX_PARENTS_PERQUERY :370 (BANG_Inmemory/parANN.cu:30)
+  const size_t vb = vec_bytes(e);
+  const bool dev_graph = (e->graph_mode == BANG_GRAPH_DEVICE);
+  const size_t slots_cap = std::max<size_t>(nq, 8 * 16 * KT_WGS);   // rows / parent words: one per query, or one per context slot of the search kernel
+  if (e->stage_zero_copy < 0) {                          // CPU-writable device memory (large BAR)?
+    int large_bar = 0;
+    int dev_id = 0;
+    (void)hipGetDevice(&dev_id);
+    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev_id) != hipSuccess) large_bar = 0;
+    e->stage_mode_eff = large_bar ? 2 : 1;
+  } else e->stage_mode_eff = e->stage_zero_copy;
+  // BAR mode: the CPU writes the staged rows into device memory while kernels read them.  That is only sound on FINE-GRAINED
+  // (host-coherent) device memory: on ordinary coarse-grained memory PCIe writes do not probe the per-XCD L2, so a persistent
+  // launch (no kernel boundary between two reads of a row) could be served a stale line.  No fine-grained memory -> no BAR mode.
+  e->stage_local = false;
+  if (!dev_graph && e->stage_mode_eff == 2) {
+    if (hipExtMallocWithFlags((void**)&e->d_stage, slots_cap * BANG_STAGE_STRIDE * 4, hipDeviceMallocFinegrained) == hipSuccess) {
+      e->stage_local = true;
+    } else {
+      (void)hipGetLastError();
+      e->d_stage = nullptr;
+      e->stage_mode_eff = 1;
+      fprintf(stderr, "[bang] fine-grained device memory unavailable: staged rows stay in mapped host memory (stage_zero_copy=1)\n");
+    }
+  }
+  BANG_TRY(resolve_form(e));                             // (decides and refuses: nothing but d_stage is allocated yet)
+  const bool host_paced = e->form == LoopForm::HostPaced;
   e->fp_direct = false;
   HIP_TRY_ALLOC(hipMalloc(&e->d_queries, nq * e->D * e->tsize + 16));
   if (e->psz) BANG_TRY(dmalloc(&e->d_qc, nq * e->mp * e->psz));
@@ -289,7 +298,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     e->h_qiters.assign(nq, 0);
   }
   if (e->n_excl != 0) {                                                      // excluded ids: what bang_k_cand_live / bang_k_worklist_pick work on
-    if (e->search_exact) {
+    if (e->form == LoopForm::Exact) {
       BANG_TRY(dmalloc(&e->d_wl_ids_full, nq * L));
       BANG_TRY(dmalloc(&e->d_wl_dists_full, nq * L));
     } else {
@@ -311,7 +320,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     BANG_TRY(dmalloc(&e->d_cand_row, nq * rows));
     if (e->vec_on_device) {
       e->d_fp = nullptr;                                                     // the re-rank reads d_vecs
-    } else if (e->search_host && e->stage_mode_eff == 2 &&
+    } else if (host_paced && e->stage_mode_eff == 2 &&
         hipExtMallocWithFlags((void**)&e->d_fp, rows * nq * vb, hipDeviceMallocFinegrained) == hipSuccess) {
       e->fp_direct = true;                                                   // walker threads write the vector log through the BAR
     } else {
@@ -320,7 +329,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
     }
     HIP_TRY(hipHostMalloc((void**)&e->h_parents, slots_cap * 4, hipHostMallocMapped));       // :419
     HIP_TRY(hipHostGetDevicePointer((void**)&e->d_parents_map, e->h_parents, 0));
-    if (e->search_host) {
+    if (host_paced) {
       if (hipExtMallocWithFlags((void**)&e->d_srows, 8 * KT_WGS * 16 * 64 * 4, hipDeviceMallocFinegrained) != hipSuccess ||
           hipExtMallocWithFlags((void**)&e->d_sctl, 8 * KT_WGS * 64, hipDeviceMallocFinegrained) != hipSuccess) {
         bang_set_error("fine-grained device memory for the search kernel's staging rows: %s", hipGetErrorString(hipGetLastError()));
@@ -329,7 +338,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
       HIP_TRY(hipMemset(e->d_srows, 0, 8 * KT_WGS * 16 * 64 * 4));
       HIP_TRY(hipMemset(e->d_sctl, 0, 8 * KT_WGS * 64));
     }
-    if (e->search_host && !e->vec_on_device) {
+    if (host_paced && !e->vec_on_device) {
       HIP_TRY(hipHostMalloc((void**)&e->h_pub_q, 8 * 16 * KT_WGS * 4, hipHostMallocMapped));
       HIP_TRY(hipHostGetDevicePointer((void**)&e->d_pub_q, e->h_pub_q, 0));
       HIP_TRY(hipHostMalloc((void**)&e->h_pub_c, 8 * 16 * KT_WGS * 4, hipHostMallocMapped));
@@ -346,12 +355,12 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   int nl = e->lanes_opt;
   if (nl <= 0) nl = dev_graph ? 1 : std::max(1, std::min(4, Q / 512));   // measured best on a 16-CPU-quota MI355X box
   nl = std::min(nl, Q);
-  if (e->search_v2 || e->search_host || e->search_exact || e->search_lut) nl = 1;   // the search kernel's waves are the unit of overlap, not lanes
-  if (e->search_host && e->threads_opt <= 0) e->threads_eff = std::max(1, std::min(12, usable_cpus() - 2));
-  else if (e->threads_opt <= 0) e->threads_eff = (dev_graph || e->search_v2 || e->search_exact) ? 1 : std::max(1, std::min(4, (usable_cpus() - 2) / std::max(1, nl)));   // leave 2 CPUs for the caller + HIP runtime threads: a cgroup that exceeds its quota gets throttled for the rest of the period
+  if (one_launch(e)) nl = 1;   // the search kernel's waves are the unit of overlap, not lanes
+  if (host_paced && e->threads_opt <= 0) e->threads_eff = std::max(1, std::min(12, usable_cpus() - 2));
+  else if (e->threads_opt <= 0) e->threads_eff = (dev_graph || e->form == LoopForm::SelfPaced || e->form == LoopForm::Exact) ? 1 : std::max(1, std::min(4, (usable_cpus() - 2) / std::max(1, nl)));   // leave 2 CPUs for the caller + HIP runtime threads: a cgroup that exceeds its quota gets throttled for the rest of the period
   else e->threads_eff = e->threads_opt;
   if (!dev_graph) {
-    const size_t n_flags = std::max<size_t>((size_t)nl, e->search_host ? 8 * KT_WGS : 0);
+    const size_t n_flags = std::max<size_t>((size_t)nl, host_paced ? 8 * KT_WGS : 0);
     HIP_TRY(hipHostMalloc((void**)&e->h_done, n_flags * 16 * 4, hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer((void**)&e->h_done_dev, e->h_done, 0));
     memset(e->h_done, 0, n_flags * 16 * 4);
@@ -387,11 +396,11 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
         HIP_TRY(hipHostGetDevicePointer((void**)&ln.qmap_dev[b], ln.qmap_host[b], 0));
       }
     }
-    if (e->search_v2 || e->search_host || e->search_exact || e->search_lut) {
+    if (one_launch(e)) {
       BANG_TRY(dmalloc(&ln.d_pcnt, 16));
       HIP_TRY(hipMemset(ln.d_pcnt, 0, 64));
     }
-    if (e->search_host) ln.pw_expect.reset(new std::atomic<uint32_t>[8 * KT_WGS]);
+    if (host_paced) ln.pw_expect.reset(new std::atomic<uint32_t>[8 * KT_WGS]);
     if (e->timing) {
       ln.kt_launches = rows + 4;
       HIP_TRY_ALLOC(hipMalloc((void**)&ln.d_ktime, ln.kt_launches * KT_WGS * 16));     // {start, end} stamp per workgroup and launch
@@ -415,7 +424,7 @@ int alloc_buffers(bang_engine* e, int Q) {         // (bang_alloc_e has validate
   }
   if (env_flag("BANG_DEBUG"))
     fprintf(stderr, "[bang] alloc Q=%d lanes=%d threads=%d stage_mode=%d search_kernel=%d/%d/%d/%d semantics=%d filter_layout=%d fp_direct=%d vec_on_device=%d\n", Q, nl,
-            e->threads_eff, e->stage_mode_eff, (int)e->search_v2, (int)e->search_host, (int)e->search_exact, (int)e->search_lut, (int)e->search_inmem, (int)e->search_wordfilter, (int)e->fp_direct, (int)e->vec_on_device);
+            e->threads_eff, e->stage_mode_eff, (int)(e->form == LoopForm::SelfPaced), (int)(e->form == LoopForm::HostPaced), (int)(e->form == LoopForm::Exact), (int)(e->form == LoopForm::Lut), (int)e->search_inmem, (int)e->search_wordfilter, (int)e->fp_direct, (int)e->vec_on_device);
   start_threads(e);
   return BANG_OK;
 }

@@ -170,7 +170,7 @@ extern "C" int bang_set_query_filters_e(bang_engine_t* e, const uint32_t* any, c
   if (e->n_radii != 0) { bang_set_error("%s: filters on labels and radii (bang_set_query_radii_e) do not combine: clear the radii first (bang_clear_query_radii_e)", what); return BANG_ERR_UNSUPPORTED; }
   // the forms without a label-filter kernel are refused: there is no unfiltered fallback
   const bool dev_graph = (e->graph_mode == BANG_GRAPH_DEVICE);
-  if (!e->search_exact) {
+  if (e->form != LoopForm::Exact) {
     bang_set_error("%s: filters on labels need option distance = 1 (exact): the PQ walks have no exact distance when a node is evaluated", what);
     return BANG_ERR_UNSUPPORTED;
   }
@@ -484,7 +484,7 @@ extern "C" int bang_init_e(bang_engine_t* e, int Q) {
   hipStream_t st = e->lanes.empty() ? nullptr : e->lanes[0]->s_main;
   BANG_TRY(bang_k_init_all(&ia, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (e->h_parents && !e->search_v2 && !e->search_exact) for (size_t i = 0; i < nq; ++i) e->h_parents[i] = BANG_NO_PARENT;   // (the walker forms read it)
+  if (e->h_parents && e->form != LoopForm::SelfPaced && e->form != LoopForm::Exact) for (size_t i = 0; i < nq; ++i) e->h_parents[i] = BANG_NO_PARENT;   // (the walker forms read it)
   e->inited = true;
   return BANG_OK;
 }
@@ -584,20 +584,22 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   for (auto& lp : e->lanes) e->stat_range_launches += lp->range_launches;
   e->stat_range_queries = e->stat_range_launches != 0 ? (uint64_t)Q : 0;
   e->stat_range_truncated = 0; e->range_counts_valid = false;       // (counted when the batch's counts are fetched: bang_get_stats_ext4)
-  s.persistent = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
+  const bool host_paced = e->form == LoopForm::HostPaced;
+  const bool self_walk = e->form == LoopForm::SelfPaced || e->form == LoopForm::Exact;      // the kernel finds its adjacency rows itself: nothing walks
+  s.persistent = one_launch(e) ? 1 : 0;
   s.vectors_on_device = e->vec_on_device ? 1 : 0;
   s.graph_mode = (uint64_t)e->graph_mode;
   s.lanes = (uint64_t)nl;
-  s.walker_threads = (e->graph_mode == BANG_GRAPH_DEVICE || e->search_v2 || e->search_exact) ? 0 : (uint64_t)e->threads_eff;   // (pull mode: nothing walks)
-  s.wg_queries = e->search_host ? e->sv_W * e->sv_C : 0;
-  s.pacing_groups = e->search_host ? e->sv_NG : 0;
-  s.graph_pull = (e->pull && (e->search_v2 || e->search_exact) && e->graph_mode != BANG_GRAPH_DEVICE) ? 1 : 0;
-  s.workgroups = e->search_host ? (uint64_t)e->sv_G : (e->search_v2 || e->search_exact || e->search_lut) ? (uint64_t)std::min(Q, bang_num_cus()) : 0;
-  s.search_kernel = (e->search_v2 || e->search_host || e->search_exact || e->search_lut) ? 1 : 0;
+  s.walker_threads = (e->graph_mode == BANG_GRAPH_DEVICE || self_walk) ? 0 : (uint64_t)e->threads_eff;   // (pull mode: nothing walks)
+  s.wg_queries = host_paced ? e->sv_W * e->sv_C : 0;
+  s.pacing_groups = host_paced ? e->sv_NG : 0;
+  s.graph_pull = (e->pull && self_walk && e->graph_mode != BANG_GRAPH_DEVICE) ? 1 : 0;
+  s.workgroups = host_paced ? (uint64_t)e->sv_G : one_launch(e) ? (uint64_t)std::min(Q, bang_num_cus()) : 0;
+  s.search_kernel = one_launch(e) ? 1 : 0;
   s.rerank_fused = e->rerank_fused ? 1 : 0;
   s.vectors_fp16 = e->vecs_f16 ? 1 : 0;
   s.vector_table_bytes = (e->vec_on_device && e->d_vecs) ? (uint64_t)e->N * vec_table_stride(e) + 256 : 0;
-  s.walker_rows = (e->search_host && e->walker_rows) ? 1 : 0;
+  s.walker_rows = (host_paced && e->walker_rows) ? 1 : 0;
   e->stat_filter_layout = e->search_wordfilter ? 1 : 0;          // (reported behind bang_stats: bang_get_stats_ext)
   s.code_stride = e->code_stride;
   // what the kernel was GIVEN (bang_lane.cpp): without a slice table a slice moved off row 0 (bang_rows_slice_e(first > 0)) is not reachable
@@ -654,7 +656,7 @@ extern "C" int bang_get_stats(bang_engine_t* e, bang_stats* out) {
     std::vector<uint32_t> qs((size_t)e->Qcur * 2);
     HIP_TRY(hipMemcpy(qs.data(), e->d_qstats, qs.size() * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < qs.size(); i += 2) { s.dist_evals += qs[i]; s.fetched += qs[i + 1]; }
-    if (e->search_v2) {
+    if (e->form == LoopForm::SelfPaced) {
       std::vector<uint32_t> sk((size_t)e->Qcur);
       HIP_TRY(hipMemcpy(sk.data(), e->d_qskip, sk.size() * 4, hipMemcpyDeviceToHost));
       for (uint32_t v : sk) s.filter_loads_skipped += v;
@@ -738,7 +740,7 @@ extern "C" int bang_get_query_counters(bang_engine_t* e, uint32_t* dist_evals, u
   }
   if (candidates) HIP_TRY(hipMemcpy(candidates, e->d_cand_cnt, Q * 4, hipMemcpyDeviceToHost));
   if (iterations) {
-    if ((e->search_v2 || e->search_host || e->search_exact || e->search_lut) && e->h_qiters.size() >= Q) memcpy(iterations, e->h_qiters.data(), Q * 4);
+    if (one_launch(e) && e->h_qiters.size() >= Q) memcpy(iterations, e->h_qiters.data(), Q * 4);
     else memset(iterations, 0, Q * 4);
   }
   return BANG_OK;

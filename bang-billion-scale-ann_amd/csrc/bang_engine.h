@@ -1,9 +1,10 @@
 // bang_engine.h -- internal state of the host engine, shared by its translation units (not public):
 //   bang_options.cpp  every option / environment switch in ONE table
 //   bang_load.cpp     bang_load: files, entry sources, placement, pull rows, streamed load (bang_search.cu:138-362)
-//   bang_alloc.cpp    bang_alloc / bang_free: per-batch buffers, lanes, loop form (bang_search.cu:370-425)
+//   bang_alloc.cpp    bang_alloc / bang_free: the choice of the loop form (resolve_form), then per-batch buffers and lanes (bang_search.cu:370-425)
 //   bang_walker.cpp   the C++ graph walker (bang_search.cu:771-813) in its three forms + the thread teams
-//   bang_lane.cpp     bang_query of one lane: H2D -> K1 -> search -> re-rank -> D2H (bang_search.cu:569-1068)
+//   bang_lane.cpp     bang_query of one lane: H2D -> K1 -> the search loop, one function per form -> re-rank -> D2H (bang_search.cu:569-1068)
+//   bang_wave_host.cpp  host side of the wave-resident search kernels: launch geometry, argument checks, routing to the kernel builds
 //   bang_cabi.cpp     the engine-level C-ABI of include/bang_c.h
 #ifndef BANG_ENGINE_H_
 #define BANG_ENGINE_H_
@@ -59,6 +60,14 @@ inline double ms_since(Clock::time_point t0) {
 }
 
 constexpr size_t KT_WGS = 256;   // workgroups per front launch never exceed the CU count
+
+// The form of the search loop, resolved at bang_alloc (bang_alloc.cpp resolve_form) and run by bang_lane.cpp, one function per form:
+//   PerIteration  a front + back launch per iteration and lane (graph in HBM or walked on the host)
+//   SelfPaced     ONE launch of the query-resident PQ search kernel: graph in HBM, or the adjacency rows pulled by the kernel itself
+//   HostPaced     ONE launch of the same kernel, graph in host RAM: its workgroups are paced by the walker team (BAR mode)
+//   Exact         ONE launch of the exact-distance search kernel (option distance = 1, bang_search_exact.hip); it writes the results itself
+//   Lut           ONE launch of the LUT-path search kernel (psz == 0, graph in HBM, search = 1 given explicitly) between K1 and the re-rank launch
+enum class LoopForm { PerIteration, SelfPaced, HostPaced, Exact, Lut };
 
 struct Lane {
   uint32_t q0 = 0, nq = 0;
@@ -218,17 +227,13 @@ struct bang_engine {
   int numa_node = -1;
   int search_opt = -1;                 // 1 = the query-resident search kernel (bang_search.hip), 0 = a launch per iteration,
                                        // -1 = auto (1 where the pivot table leaves LDS for at least 4 waves' worklists)
-  bool search_v2 = false;              // resolved at bang_alloc: graph in HBM, self-paced form
-  bool search_host = false;            // resolved at bang_alloc: graph in host RAM, the host-paced form of the same kernel (BAR mode)
+  bang::LoopForm form = bang::LoopForm::PerIteration;   // resolved at bang_alloc: the loop form of this allocation
   int distance = 0;                    // option "distance": 0 = PQ distances + re-rank (BANG_Base), 1 = exact distances, results from the worklist
-  bool search_exact = false;           // resolved at bang_alloc: distance = 1 -- the exact-distance search kernel (bang_search_exact.hip)
   int beam = 1;                        // option "beam": parents expanded per iteration of the exact-distance walk; 1 = not asked for (bang_search_exact.hip), 2..4 = bang_search_beam.hip
   int semantics = 0;                   // option "semantics": 0 = BANG_Base's walk (default), 1 = BANG_Inmemory's (parent after the merge, cap L + 119)
-  bool search_inmem = false;           // resolved at bang_alloc: semantics = 1 -- search_v2 on bang_k_search_inmem; candidate log L + 120
+  bool search_inmem = false;           // resolved at bang_alloc: semantics = 1 -- the self-paced form on bang_k_search_inmem; candidate log L + 120
   int filter_layout = 0;               // option "filter_layout": 0 = split (an id's two filter bits in two unrelated words, default), 1 = word (both in the word of hash1)
-  bool search_wordfilter = false;      // resolved at bang_alloc: filter_layout = 1 -- search_v2 on bang_k_search_wf
-  bool search_lut = false;             // resolved at bang_alloc: LUT path (psz == 0), graph in HBM, search = 1 given explicitly -- K1, then ONE launch of
-                                       // the LUT-path search kernel (bang_search_lut.hip), then the re-rank launch
+  bool search_wordfilter = false;      // resolved at bang_alloc: filter_layout = 1 -- the self-paced form on bang_k_search_wf
   uint32_t sv_G = 0, sv_W = 0, sv_C = 1;   // its grid for the running query: workgroups, waves per workgroup, query contexts per wave
   uint32_t sv_GS = 8, sv_NG = 0;           // waves per pacing group; pacing groups = workgroups x groups per workgroup x contexts
   uint32_t* d_srows = nullptr;         // fine-grained device memory [groups*16][64]: adjacency ids per slot, written through the BAR
@@ -335,6 +340,8 @@ extern "C" int bang_search_inmem_has_instance(uint32_t psz, uint32_t mp, uint32_
 
 namespace bang {
 
+// the whole batch is ONE launch of a search kernel (every form but the launch-per-iteration loop)
+inline bool one_launch(const bang_engine* e) { return e->form != LoopForm::PerIteration; }
 inline size_t vec_bytes(const bang_engine* e) { return (size_t)e->D * e->tsize; }
 // bytes between the rows of the HBM vector table d_vecs: the vector as the index holds it, or its fp16 image padded to whole dwords
 inline size_t vec_table_stride(const bang_engine* e) { return e->vecs_f16 ? (((size_t)2 * e->D + 3) & ~(size_t)3) : vec_bytes(e); }

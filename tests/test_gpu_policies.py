@@ -144,26 +144,59 @@ def test_fused_rerank_short_logs_many_lanes_and_big_k(libbang, small_u8):
         assert np.array_equal(ids, ids_o) and np.array_equal(dists.view(np.uint32), dists_o.view(np.uint32)), (k, L, lanes)
 
 
-@pytest.mark.parametrize("graph", [0, 1])
-@pytest.mark.parametrize("direct", ["1", "0"])
-def test_fused_rerank_results_straight_into_the_pinned_mirror(request, libbang, monkeypatch, small_u8, graph, direct):
+# the loop forms whose results travel back: engine options, what bang_stats reports for them, and the reference (the oracle for the PQ walks,
+# tests/exact_reference.py for distance = 1); the launch-per-iteration loop keeps no per-query iteration counts
+_ROUTE_FORMS = {
+    "fused_host": (dict(graph=0, fuse_rerank=1), dict(search_kernel=1, rerank_fused=1), "pq"),
+    "fused_device": (dict(graph=1, fuse_rerank=1), dict(search_kernel=1, rerank_fused=1), "pq"),
+    "rerank_launch": (dict(graph=1, search=1, fuse_rerank=0), dict(search_kernel=1, rerank_fused=0), "pq"),
+    "exact": (dict(graph=1, distance=1), dict(search_kernel=1, rerank_fused=0), "exact"),
+    "per_iteration": (dict(graph=1, search=0), dict(search_kernel=0, rerank_fused=0), "pq"),
+}
+_ROUTES = {"default": {}, "copied_back": {"BANG_RESULTS_DIRECT": "0"}, "pipelined": {"BANG_MAILBOX_BYTES": "0"}}
+_route_ref = {}
+
+
+def _route_reference(ix, q, mode):
+    if mode not in _route_ref:
+        if mode == "exact":
+            from exact_reference import Reference
+            _route_ref[mode] = Reference(ix).search(q, 10, 48, "exact")
+        else:
+            from oracle import oracle as O
+            ids_o, dists_o, st_o = O.Oracle(ix).search(q, 10, 48, with_stats=True)
+            _route_ref[mode] = (ids_o, dists_o, st_o.astype(np.int64))
+    return _route_ref[mode]
+
+
+# (the ids "0" / "1" are graph = 0 / 1 with the re-rank fused and BANG_RESULTS_DIRECT = 1 / 0: the cases this test had before the other forms and routes joined)
+@pytest.mark.parametrize("form", [pytest.param("fused_host", id="0"), pytest.param("fused_device", id="1"), "rerank_launch", "exact", "per_iteration"])
+@pytest.mark.parametrize("route", [pytest.param("default", id="1"), pytest.param("copied_back", id="0"), "pipelined"])
+def test_fused_rerank_results_straight_into_the_pinned_mirror(request, libbang, monkeypatch, small_u8, form, route):
     """With the re-rank fused, the kernel writes ids [Q][k], distances [rank][Q], the per-query iteration counts and its abort word straight
     into the pinned host mirror of the results (no copy behind the launch); BANG_RESULTS_DIRECT=0 keeps them in device memory and copies
-    them back (compute_NearestNeighbours bang_search.cu:1312-1368 + the D2H at :997-999).  Same bits, same counters, twice in a row."""
+    them back (compute_NearestNeighbours bang_search.cu:1312-1368 + the D2H at :997-999).  Same bits, same counters, twice in a row.
+
+    The three ways back -- the default of the form (the exact-distance kernel writes into the mirror as the fused re-rank does; a form with a
+    re-rank launch behind it returns in one copy of the mirror), BANG_RESULTS_DIRECT=0 (always that one copy) and BANG_MAILBOX_BYTES=0 (ids,
+    distances and iteration counts in copies of their own, straight into the caller's arrays) -- on every form whose results come back."""
     import bang_amd
-    from oracle import oracle as O
     ix, q, _, _ = small_u8
-    monkeypatch.setenv("BANG_RESULTS_DIRECT", direct)
-    ids_o, dists_o, st_o = O.Oracle(ix).search(q, 10, 48, with_stats=True)
-    with bang_amd.Engine(ix.dtype, graph=graph, fuse_rerank=1) as e:
+    opts, want_stats, mode = _ROUTE_FORMS[form]
+    for name, value in _ROUTES[route].items():
+        monkeypatch.setenv(name, value)
+    ids_o, dists_o, st_o = _route_reference(ix, q, mode)
+    with bang_amd.Engine(ix.dtype, **opts) as e:
         e.load_index(ix)
         e.set_searchparams(10, 48)
         e.alloc(q.shape[0])
         for _ in range(2):
             e.init(q.shape[0])
             ids, dists = e.query(q)
-            assert e.stats()["rerank_fused"] == 1
+            st = e.stats()
+            assert {key: st[key] for key in want_stats} == want_stats
             assert np.array_equal(ids, ids_o) and np.array_equal(dists.view(np.uint32), dists_o.view(np.uint32))
-            assert np.array_equal(e.query_counters(q.shape[0]), st_o.astype(np.int64))
+            if want_stats["search_kernel"]:
+                assert np.array_equal(e.query_counters(q.shape[0]), st_o)
         e.free(); e.unload()
 
