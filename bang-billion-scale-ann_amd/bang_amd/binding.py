@@ -7,6 +7,8 @@ import subprocess
 
 import numpy as np
 
+from .formats import check_index_floats
+
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.environ.get("BANG_AMD_LIB") or os.path.join(_PKG, "lib", "libbang.so")    # (override: A/B runs of experimental builds)
 
@@ -269,7 +271,12 @@ class Engine:
 
     def load_index(self, ix, d_codes: int | None = None, code_stride: int = 0):
         """Load from a formats.Index held in memory (graph stays referenced, not copied, in host mode).  d_codes: the PQ codes are
-        already on the device, rows `code_stride` bytes apart (0 = m)."""
+        already on the device, rows `code_stride` bytes apart (0 = m).  The float tables of the index -- pivots, centroid, and the vectors of a
+        float index -- are checked against the input domain first (finite, |x| <= 2^56: formats.check_index_floats); BangError, nothing loaded."""
+        try:
+            check_index_floats(ix, self.dtype)
+        except ValueError as ex:
+            raise BangError(f"load_index: {ex}") from None
         graph = np.ascontiguousarray(ix.graph, dtype=np.uint8)
         codes = np.ascontiguousarray(ix.codes, dtype=np.uint8)
         pivots = np.ascontiguousarray(ix.pivots, dtype=np.float32)

@@ -147,7 +147,36 @@ def read_graph_metadata(path: str) -> dict:
     return dict(medoid=medoid, entry_len=elen, dtype_code=dt, D=D, R=R, N=N)
 
 
+FLOAT_DOMAIN_MAX = float(2.0 ** 56)
+
+
+def check_floats(name: str, a: np.ndarray, row0: int = 0) -> None:
+    """The input domain of float data (CANON 20; bang_check_floats of the library, with numpy): every element finite
+    with |x| <= 2^56.  Raises ValueError naming the table and the first offending element (row0: the table row `a` starts at)."""
+    a = np.asarray(a, dtype=np.float32)
+    bad = ~(np.abs(a) <= np.float32(FLOAT_DOMAIN_MAX))               # (a NaN compares false: it is an offender)
+    if bad.any():
+        at = [int(i) for i in np.unravel_index(int(np.argmax(bad.reshape(-1))), a.shape)]
+        val = float(a[tuple(at)])
+        at[0] += row0
+        raise ValueError(f"{name}: element {tuple(at)} holds {val!r}: the float tables of an index must be finite with |x| <= 2^56")
+
+
+def check_index_floats(ix: Index, dtype: str | None = None) -> None:
+    """check_floats on the pivots and the centroid of an index of any vector type and on the vectors of a float one (read from the graph
+    entries a block of rows at a time: no second copy of the table).  dtype: the vector type where it is not ix.dtype's to say."""
+    check_floats("PQ pivot table", ix.pivots)
+    check_floats("PQ centroid", ix.centroid)
+    if (ix.dtype if dtype is None else dtype) == "float":
+        step = max(1, (1 << 22) // max(int(ix.D), 1))
+        for r0 in range(0, int(ix.N), step):
+            blk = np.ascontiguousarray(ix.graph[r0:r0 + step, : ix.D * 4]).view(np.float32)
+            check_floats("vectors", blk, r0)
+
+
 def write_index(prefix: str, ix: Index) -> None:
+    """Refuses (ValueError, nothing written) an index whose float tables leave the input domain (check_index_floats)."""
+    check_index_floats(ix)
     os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
     write_pq_pivots(prefix + PQ_PIVOTS_SUFFIX, ix.pivots, ix.centroid, ix.chunk_off)
     write_pq_compressed(prefix + PQ_COMPRESSED_SUFFIX, ix.codes)

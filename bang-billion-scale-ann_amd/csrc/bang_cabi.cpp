@@ -512,6 +512,16 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
     bang_set_error("bang_query: a batch of %d queries, but the filters were set for %u (bang_set_query_filters_e; bang_clear_query_filters_e drops them)", Q, e->n_qfilters);
     return BANG_ERR_ARG;
   }
+  if (e->dtype == BANG_F32) {                          // CANON 20: finite, |x| <= 2^56 -- before a lane is started or a copy issued
+    const uint64_t qdim = e->D - (e->distfn == BANG_DIST_MIPS ? 1u : 0u);    // MIPS: the queries come without the padding dimension (bang_lane.cpp)
+    uint64_t bad = 0;
+    if (bang_check_floats((const float*)h_queries, (uint64_t)Q * qdim, &bad) != BANG_OK) {
+      const float v = ((const float*)h_queries)[bad];
+      bang_set_error("bang_query: query %llu, dimension %llu holds %g: float queries must be finite with |x| <= 2^56 (nothing was launched)",
+                     (unsigned long long)(bad / qdim), (unsigned long long)(bad % qdim), (double)v);
+      return BANG_ERR_ARG;
+    }
+  }
   e->inited = false;   // state is consumed
   e->Qcur = Q;
   // the calling thread is lane 0's walker: it joins the GPU's NUMA node for the duration of the query

@@ -770,6 +770,17 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     return BANG_ERR_IO;
   }
   if (e->medoid >= e->N) { bang_set_error("medoid out of range"); return BANG_ERR_IO; }
+  // CANON 20: the float tables every index has, whatever its vector type (the vectors of an index file are the index's contract)
+  uint64_t bad = 0;
+  if (bang_check_floats(pivots, 256ull * D, &bad) != BANG_OK) {
+    bang_set_error("PQ pivot table: pivot %llu, dimension %llu holds %g: the float tables of an index must be finite with |x| <= 2^56",
+                   (unsigned long long)(bad / D), (unsigned long long)(bad % D), (double)pivots[bad]);
+    return BANG_ERR_ARG;
+  }
+  if (bang_check_floats(centroid, D, &bad) != BANG_OK) {
+    bang_set_error("PQ centroid: dimension %llu holds %g: the float tables of an index must be finite with |x| <= 2^56", (unsigned long long)bad, (double)centroid[bad]);
+    return BANG_ERR_ARG;
+  }
   // option vectors_fp16: what it cannot apply to is refused (the table of a device placement IS the graph entries: checked once auto is resolved)
   e->vecs_f16 = false;
   if (e->vectors_fp16 == 1) {

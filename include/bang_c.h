@@ -152,12 +152,25 @@ int bang_rows_close_peers_e(bang_engine_t* e);
 int bang_set_searchparams_e(bang_engine_t* e, int recall, int worklist_length, int distfn); /* bang.h:60 */
 int bang_alloc_e(bang_engine_t* e, int num_queries);                                        /* bang.h:53 */
 int bang_init_e(bang_engine_t* e, int num_queries);                                         /* bang.h:56 */
-/* bang_query, bang.h:75: ids [Q][k] u64, dists [k][Q] f32 (rank-major, bang_search.cu:999) */
+/* THE INPUT DOMAIN OF FLOAT DATA (DESIGN.md section 2 CANON 20): float queries and the float tables of an index (vectors, pivots, centroid) must be
+ * finite with |x| <= 2^56 -- the largest power of two for which no distance of a supported layout reaches the sentinel 3.402823E+38f; inside it no
+ * kernel ever sees an inf or a NaN (a NaN distance breaks a wave's rank sort and ends in a read outside the index).  bang_check_floats is the check:
+ * host code, no device needed, one pass on the bits ((bits & 0x7FFFFFFF) > 0x5B800000: NaN of either sign and any payload, +-inf, finite values
+ * beyond 2^56).  Returns BANG_OK, or BANG_ERR_ARG with the index of the FIRST offending element in *first_bad (may be NULL); n = 0 is BANG_OK.
+ * Every load checks the pivot table and the centroid of the index, whatever its vector type, and fails with BANG_ERR_ARG naming the table and the
+ * element.  NOT checked: the float vectors of an index file (up to 512 GB) -- their range is the index's contract. */
+int bang_check_floats(const float* x, uint64_t n, uint64_t* first_bad);
+
+/* bang_query, bang.h:75: ids [Q][k] u64, dists [k][Q] f32 (rank-major, bang_search.cu:999).  A float engine checks the batch with bang_check_floats
+ * before a lane is started or a copy issued: a query element outside the domain is BANG_ERR_ARG with the query and the dimension in the message;
+ * allocation, bang_init state, radii, filters and exclusion set are untouched and the next clean batch runs on them.  (A MIPS batch is
+ * [Q][D - 1] floats and is checked, and its offender named, at that row length.) */
 int bang_query_e(bang_engine_t* e, const void* h_queries, int num_queries, uint64_t* h_ids, float* h_dists);
 /* The same search with the results LEFT ON THE DEVICE: d_ids [Q][k] u64 and (optional, may be NULL) d_dists [k][Q] f32 are device
  * buffers of the caller on the engine's device; nothing but the per-query iteration counts returns to the host.  For callers that
  * hand the ids on from device memory -- the multi-GPU job all-gathers the shards' id blocks over xGMI straight from here (SURVEY
- * 8(e)) instead of bouncing them through the host.  Complete (stream synchronised) on return. */
+ * 8(e)) instead of bouncing them through the host.  Complete (stream synchronised) on return.  The float domain check of bang_query_e runs here
+ * too, before anything is launched: on a refusal d_ids / d_dists are not written. */
 int bang_query_dev_e(bang_engine_t* e, const void* h_queries, int num_queries, uint64_t* d_ids, float* d_dists);
 int bang_free_e(bang_engine_t* e);                                                          /* bang.h:80 */
 
