@@ -111,6 +111,29 @@ class StatsExt4(C.Structure):
                                      ("range_truncated", C.c_uint64)]
 
 
+class StatsExt5(C.Structure):
+    """bang_stats_ext5: bang_stats_ext4 with the insert fields behind it (bang_get_stats_ext5)."""
+    _fields_ = StatsExt4._fields_ + [("capacity", C.c_uint64), ("inserted", C.c_uint64), ("backedge_appended", C.c_uint64),
+                                     ("backedge_pruned", C.c_uint64), ("backedge_dropped", C.c_uint64)]
+
+
+class PruneParams(C.Structure):
+    """bang_prune_params (include/bang_c.h): device addresses."""
+    _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("n_nodes", C.c_uint32),
+                ("R", C.c_uint32), ("alpha2", C.c_float), ("n_lists", C.c_uint32), ("list_stride", C.c_uint32),
+                ("d_list_ids", C.c_void_p), ("d_list_dists", C.c_void_p), ("d_list_cnt", C.c_void_p), ("d_own", C.c_void_p),
+                ("d_out", C.c_void_p), ("out_stride", C.c_uint64), ("out_by_own", C.c_uint32), ("max_wgs", C.c_uint32), ("max_waves", C.c_uint32),
+                ("d_abort", C.c_void_p)]
+
+
+class BackedgeParams(C.Structure):
+    """bang_backedge_params (include/bang_c.h): device addresses."""
+    _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("R", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("n_old", C.c_uint32), ("n_targets", C.c_uint32),
+                ("d_targets", C.c_void_p), ("d_offs", C.c_void_p), ("d_srcs", C.c_void_p), ("d_cand_ids", C.c_void_p), ("d_cand_dists", C.c_void_p),
+                ("d_offered", C.c_void_p), ("d_own_out", C.c_void_p), ("d_stats", C.c_void_p), ("d_abort", C.c_void_p)]
+
+
 class RangeOut(C.Structure):
     """bang_range_out: what bang_k_search_exact_range takes beside bang_search_params (device addresses)."""
     _fields_ = [("d_radius", C.c_void_p), ("d_excluded", C.c_void_p), ("d_hit_ids", C.c_void_p), ("d_hit_dists", C.c_void_p),
@@ -286,6 +309,7 @@ class Engine:
         d = IndexDesc(ix.medoid, ix.entry_len, ix.D, ix.R, ix.N, ix.m, _vp(graph).value, _vp(codes).value,
                       d_codes, _vp(pivots).value, _vp(centroid).value, _vp(chunk_off).value, code_stride)
         _check(lib().bang_load_mem_e(self._h, C.byref(d)), "bang_load_mem")
+        self._ix_shape = (int(ix.entry_len), int(ix.m))                  # row sizes of entries() / codes()
 
     def load_stream(self, ix, source, ctx=None, d_codes: int | None = None, code_stride: int = 0, d_vectors: int | None = None):
         """Streamed load (bang_load_stream_e): `source` is a C function pointer -- or a Python callable
@@ -483,6 +507,68 @@ class Engine:
         s = StatsExt4()
         _check(lib().bang_get_stats_ext4(self._h, C.byref(s)), "bang_get_stats_ext4")
         return {f: getattr(s, f) for f, _ in StatsExt4._fields_}
+
+    # ---- inserts (option capacity; bang_insert_e)
+    def num_nodes(self) -> int:
+        """N of the loaded index: what the index file held plus every point inserted since."""
+        n = C.c_uint64(0)
+        fn = lib().bang_get_num_nodes
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        _check(fn(self._h, C.byref(n)), "bang_get_num_nodes")
+        return int(n.value)
+
+    def insert(self, vectors: np.ndarray, L_build: int, alpha: float = 1.2) -> int:
+        """bang_insert_e: add the rows of `vectors` ([n][D], the engine's element type) as ONE batch -> the id of the first (the others follow in
+        input order).  Needs Engine(..., graph=GRAPH_DEVICE, capacity=...) and no live allocation."""
+        v = np.ascontiguousarray(vectors, dtype=NP_DTYPE[self.dtype])
+        if v.ndim != 2:
+            raise BangError(f"insert: vectors must be [n][D] (got shape {v.shape})")
+        first = C.c_uint64(0)
+        fn = lib().bang_insert_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
+        _check(fn(self._h, _vp(v) if v.size else None, C.c_uint32(v.shape[0]), C.c_uint32(int(L_build)), C.c_float(alpha), C.byref(first)), "bang_insert")
+        return int(first.value)
+
+    def entries(self, first: int, n: int) -> np.ndarray:
+        """uint8 [n][entry_len]: the graph entries [first, first + n) as they stand in HBM (graph = device)."""
+        fn = lib().bang_get_entries_e
+        fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        out = np.zeros((n, self._entry_len()), np.uint8)
+        _check(fn(self._h, C.c_uint64(first), C.c_uint64(n), _vp(out)), "bang_get_entries")
+        return out
+
+    def codes(self, first: int, n: int) -> np.ndarray:
+        """uint8 [n][m]: the PQ codes of the nodes [first, first + n), packed whatever their stride in HBM."""
+        fn = lib().bang_get_codes_e
+        fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._entry_len()
+        out = np.zeros((n, self._ix_shape[1]), np.uint8)
+        _check(fn(self._h, C.c_uint64(first), C.c_uint64(n), _vp(out)), "bang_get_codes")
+        return out
+
+    def _entry_len(self) -> int:
+        if not getattr(self, "_ix_shape", None):
+            raise BangError("entries / codes: load the index with load_index first")
+        return self._ix_shape[0]
+
+    def export_index(self, ix):
+        """-> formats.Index of the engine's index as it stands: the loaded `ix`'s pivots, centroid, chunk offsets and medoid with the downloaded
+        entries and codes (formats.write_index persists it)."""
+        import dataclasses
+        N = self.num_nodes()
+        return dataclasses.replace(ix, N=N, graph=self.entries(0, N), codes=self.codes(0, N))
+
+    def insert_stats(self) -> dict:
+        """bang_stats_ext5's own fields: capacity, inserted, backedge_appended, backedge_pruned, backedge_dropped (totals since the load)."""
+        s = StatsExt5()
+        _check(lib().bang_get_stats_ext5(self._h, C.byref(s)), "bang_get_stats_ext5")
+        return {f: getattr(s, f) for f, _ in StatsExt5._fields_[len(StatsExt4._fields_):]}
+
+    def insert_times(self) -> dict:
+        """bang_get_insert_times: milliseconds of the last insert per phase (search, prune, group, backedge, encode: see bang_c.h) and in all."""
+        ms = (C.c_double * 6)()
+        _check(lib().bang_get_insert_times(self._h, ms), "bang_get_insert_times")
+        return dict(zip(("search", "prune", "group", "backedge", "encode", "total"), (float(x) for x in ms)))
 
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the

@@ -57,7 +57,8 @@ static int set_excluded(bang_engine* e, const uint32_t* ids, uint64_t n, const c
       return BANG_ERR_ARG;
     }
   if (n == 0) { (void)hipSetDevice(e->device); drop_excluded(e); return BANG_OK; }
-  const size_t words = ((size_t)e->N + 31) / 32 + 1;               // + a word of slack
+  const size_t nodes = std::max<size_t>(e->N, e->capacity > 0 ? (size_t)e->capacity : 0);   // option capacity: the bitmap covers the nodes to come
+  const size_t words = (nodes + 31) / 32 + 1;                      // + a word of slack
   std::vector<uint32_t> bits(words, 0u);
   for (uint64_t i = 0; i < n; ++i) bits[ids[i] >> 5] |= 1u << (ids[i] & 31u);
   uint64_t distinct = 0;
@@ -377,6 +378,7 @@ extern "C" int bang_load_stream_e(bang_engine_t* e, const bang_index_desc* d, ba
     return BANG_ERR_ARG;
   }
   if (e->loaded) { bang_set_error("index already loaded"); return BANG_ERR_ARG; }
+  if (e->capacity > 0) { bang_set_error("option capacity = %d does not apply: a streamed load keeps the adjacency lists on the host (and the vectors, where given, in the caller's buffer)", e->capacity); return BANG_ERR_UNSUPPORTED; }
   BANG_TRY(ensure_device(e));
   e->medoid = d->medoid; e->entry_len = d->entry_len; e->D = d->D; e->R = d->R; e->N = d->N; e->m = d->m;
   e->graph = nullptr;
@@ -401,6 +403,7 @@ extern "C" int bang_load_shared_e(bang_engine_t* e, const bang_index_desc* d) {
     return BANG_ERR_ARG;
   }
   if (e->loaded) { bang_set_error("index already loaded"); return BANG_ERR_ARG; }
+  if (e->capacity > 0) { bang_set_error("option capacity = %d does not apply: a shared load runs on the host placement, its vectors in the caller's buffer", e->capacity); return BANG_ERR_UNSUPPORTED; }
   BANG_TRY(ensure_device(e));
   e->medoid = d->medoid; e->entry_len = d->entry_len; e->D = d->D; e->R = d->R; e->N = d->N; e->m = d->m;
   e->graph = nullptr; e->graph_owned = nullptr; e->graph_path.clear();
@@ -444,6 +447,7 @@ extern "C" int bang_alloc_e(bang_engine_t* e, int Q) {
   if (!e || Q <= 0) return BANG_ERR_ARG;
   if (!e->loaded || !e->params_set) { bang_set_error("bang_alloc: load an index and set search params first"); return BANG_ERR_ARG; }
   if (e->allocated) { bang_set_error("bang_alloc: already allocated (call bang_free)"); return BANG_ERR_ARG; }
+  if (e->insert_broken) { bang_set_error("bang_alloc: an insert failed half-way and old rows may list ids beyond N: unload this engine (bang_unload) and load the index again"); return BANG_ERR_ARG; }
   BANG_TRY(ensure_device(e));
   e->Qcap = Q;
   e->Qcur = 0;

@@ -6,6 +6,8 @@
 //   bang_lane.cpp     bang_query of one lane: H2D -> K1 -> the search loop, one function per form -> re-rank -> D2H (bang_search.cu:569-1068)
 //   bang_wave_host.cpp  host side of the wave-resident search kernels: launch geometry, argument checks, routing to the kernel builds
 //   bang_cabi.cpp     the engine-level C-ABI of include/bang_c.h
+//   bang_insert_host.cpp  bang_insert_e: the launches of an insert (option capacity), the entry / code downloads; bang_insert_group.cpp: its
+//                     host-side grouping of the new rows by target (no HIP call, no engine)
 #ifndef BANG_ENGINE_H_
 #define BANG_ENGINE_H_
 
@@ -333,6 +335,11 @@ struct bang_engine {
   uint64_t stat_range_queries = 0, stat_range_launches = 0, stat_range_truncated = 0;   // bang_stats_ext4 of the last bang_query
   std::vector<uint32_t> h_range_count, h_range_offered;   // the last range batch's counts, fetched once (bang_get_range_counts / _results)
   bool range_counts_valid = false;
+  // inserts (option capacity + bang_insert_e): with capacity > 0 d_graph, d_codes and the exclusion bitmap hold `capacity` nodes
+  int capacity = 0;                    // option "capacity": nodes the device tables are allocated for, 0 = off (N)
+  uint64_t stat_inserted = 0, stat_be_appended = 0, stat_be_pruned = 0, stat_be_dropped = 0;   // bang_stats_ext5: totals since the load
+  bool insert_broken = false;          // a bang_insert_e failed after it had begun to write the tables: bang_insert_e and bang_alloc_e refuse until bang_unload
+  double insert_ms[6] = {0, 0, 0, 0, 0, 0};   // the last bang_insert_e: {search, prune, rows down + host grouping, back-edges, encode} on the stream / host, the whole call
 };
 
 // bang_search.hip, part 2 (semantics = 1): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride

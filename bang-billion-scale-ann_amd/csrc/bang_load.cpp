@@ -761,6 +761,20 @@ int map_graph_file(bang_engine* e) {
 int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext, const float* pivots,
                  const float* centroid, const uint32_t* chunk_off, uint32_t desc_code_stride) {
   const uint32_t D = e->D, m = e->m;
+  // option capacity (inserts): the device tables of a device placement hold `capacity` nodes; what it cannot apply to is refused
+  if (e->capacity > 0) {
+    const char* no = nullptr;
+    if (e->graph_mode != BANG_GRAPH_DEVICE) no = "it needs option graph = device given explicitly (the device tables are the index an insert changes)";
+    else if (d_codes_ext) no = "a caller's code buffer (bang_index_desc.d_codes) cannot grow";
+    // (a caller's vector buffer, bang_index_desc.d_vectors, only exists on streamed and shared loads: bang_load_stream_e / _shared_e refuse the option)
+    else if (e->vectors_fp16 == 1) no = "option vectors_fp16 = 1";
+    else if (e->R > 64) no = "R > 64";
+    if (no) { bang_set_error("option capacity = %d does not apply: %s", e->capacity, no); return BANG_ERR_UNSUPPORTED; }
+    if ((uint64_t)e->capacity < e->N || (uint64_t)e->capacity >= 0xFFFFFFFFull) {
+      bang_set_error("option capacity = %d is smaller than the index (N = %u) or does not leave the 32-bit id space", e->capacity, e->N);
+      return BANG_ERR_ARG;
+    }
+  }
   if (e->R == 0 || e->R > BANG_MAX_R) {             // assert(R == MAX_R), bang_search.cu:190 (relaxed to R <= 64)
     bang_set_error("graph degree bound R=%u unsupported (max %d)", e->R, BANG_MAX_R);
     return BANG_ERR_UNSUPPORTED;
@@ -819,7 +833,8 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     if (pad != m) {
       size_t free_b = 0, total_b = 0;
       (void)hipMemGetInfo(&free_b, &total_b);
-      const size_t N_ = e->N, gbytes = N_ * e->entry_len + 256, vbytes = N_ * vec_table_stride(e);
+      const size_t N_ = std::max<size_t>(e->N, e->capacity > 0 ? (size_t)e->capacity : 0);      // (option capacity: the tables hold that many nodes)
+      const size_t gbytes = N_ * e->entry_len + 256, vbytes = N_ * vec_table_stride(e);
       const bool dev_packed = N_ * m + gbytes + hbm_reserve <= free_b;
       bool ok;
       if (e->graph_mode == BANG_GRAPH_DEVICE || (e->graph_mode == BANG_GRAPH_AUTO && dev_packed)) ok = N_ * pad + gbytes + hbm_reserve <= free_b;   // (never flips auto to host)
@@ -833,8 +848,10 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     e->d_codes = (uint8_t*)d_codes_ext;
     e->codes_owned = false;
   } else {
-    HIP_TRY(hipMalloc((void**)&e->d_codes, code_bytes + 256));
+    const size_t code_room = e->capacity > 0 ? ((size_t)e->capacity - e->N) * stride : 0;      // option capacity: rows for the nodes to come, zeroed
+    HIP_TRY(hipMalloc((void**)&e->d_codes, code_bytes + code_room + 256));
     e->codes_owned = true;
+    if (code_room) HIP_TRY(hipMemset(e->d_codes + code_bytes, 0, code_room + 256));
     if (stride == m) {
       HIP_TRY(hipMemset(e->d_codes + code_bytes, 0, 256));
       const size_t step = (size_t)1 << 30;
@@ -1006,7 +1023,9 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
     (void)madvise(e->graph_map, e->graph_map_len, MADV_DONTNEED);
   if (e->graph_mode == BANG_GRAPH_DEVICE) {
     const size_t gbytes = (size_t)e->N * e->entry_len;
-    HIP_TRY(hipMalloc((void**)&e->d_graph, gbytes + 256));
+    const size_t groom = e->capacity > 0 ? ((size_t)e->capacity - e->N) * e->entry_len : 0;    // option capacity: entries for the nodes to come, zeroed
+    HIP_TRY(hipMalloc((void**)&e->d_graph, gbytes + groom + 256));
+    if (groom) HIP_TRY(hipMemset(e->d_graph + gbytes, 0, groom + 256));
     const size_t step = (size_t)1 << 30;
     for (size_t off = 0; off < gbytes; off += step)
       HIP_TRY(hipMemcpy(e->d_graph + off, e->graph + off, std::min(step, gbytes - off), hipMemcpyHostToDevice));
@@ -1049,6 +1068,8 @@ void unload_index(bang_engine* e) {
   e->graph_map = nullptr; e->graph_map_len = 0;
   e->graph = nullptr;
   e->loaded = false;
+  e->insert_broken = false;
+  e->stat_inserted = e->stat_be_appended = e->stat_be_pruned = e->stat_be_dropped = 0;
   e->graph_mode = e->graph_opt;
 }
 // ---- file loading (bang_search.cu:138-362) ----

@@ -43,6 +43,10 @@ static const OptionDef kOptions[] = {
      "distance = 1 and pull = 1 (D % 8 == 0, D <= 256), the exact-distance kernel read it, and every exact distance is the usual arithmetic on the "
      "ROUNDED vectors; the re-rank is not fused into the search launch.  A load whose vectors hold a finite |x| >= 65520 fails.  Refused for 8-bit "
      "vectors, graph = device, vectors = 0, a caller's vector buffer and shared loads.  0 = float rows (default)"},
+    {"capacity", "BANG_CAPACITY", &bang_engine::capacity, 0, 0x7FFFFFFF, INT, BEFORE_LOAD,
+     "graph = device given explicitly: nodes the graph entries, the PQ codes and the exclusion bitmap are allocated for, so that bang_insert_e can add "
+     "points to the loaded index (capacity >= N).  Refused at load: host placement, streamed and shared loads, a caller's code or vector buffer, "
+     "vectors_fp16, R > 64.  0 = off (default): the tables hold the N nodes of the index"},
     {"pull", "BANG_PULL", &bang_engine::pull_opt, -1, 1, INT, BEFORE_LOAD,
      "host graph: 1 = the search kernel pulls 256-byte adjacency rows from pinned host memory over PCIe, 0 = C++ walker threads serve them, -1 = auto"},
     {"rows_hbm", "BANG_ROWS_HBM", &bang_engine::rows_hbm_opt, -1, 1 << 22, INT, BEFORE_LOAD,

@@ -241,6 +241,27 @@ int bang_set_query_radii_e(bang_engine_t* e, const float* radii, int nq);
 int bang_clear_query_radii_e(bang_engine_t* e);
 int bang_get_range_counts(bang_engine_t* e, uint32_t* counts, uint32_t* offered, uint32_t num_queries);
 int bang_get_range_results(bang_engine_t* e, uint64_t* lims, uint64_t* ids, float* dists, uint64_t capacity);
+/* INSERTS (DESIGN.md section 2 CANON 21, section 4.15; option capacity): new points go into a loaded index without a rebuild.  With option
+ * capacity = C > N and graph = device given explicitly, bang_load_mem_e / bang_load_e allocate the graph entries, the PQ codes (256-byte slack kept)
+ * and the exclusion bitmap for C nodes.  Refused at load, with "capacity" in the message: host placement (auto included), streamed and shared loads,
+ * a caller's code or vector buffer, vectors_fp16, capacity < N, R > 64.
+ * bang_insert_e adds the n vectors ([n][D], the engine's element type) as ONE batch; their ids are N .. N + n - 1 in input order, *first_id = N (may
+ * be NULL).  All n searches run on the graph as it was before the call: points of one batch do not see each other, a second call sees the first.
+ * Per point: the candidates are its final worklist of the exact-distance walk (bang_k_search_exact at L = k = L_build, cap L_build + 49; the
+ * exclusion set is NOT consulted -- a deleted node stays a graph node and may become a neighbour), RobustPrune(alpha) gives its row, every old node
+ * in a new row receives the back-edge (appended while the row has room, else the row is re-pruned from old row ++ new ids), the PQ code of chunk c is
+ * the lowest k minimising K1's table, and the seed list is rebuilt.  Valid after a load, refused while an allocation is live (bang_free_e first).
+ * Refused with a message and no side effect: no capacity or N + n > capacity; n = 0 or n > 16384; L_build < 1 or > BANG_MAX_L; alpha not finite or
+ * outside [1, 8]; MIPS search parameters; a layout outside bang_search_can_rerank; a label table set (clear it, insert, set one for the new N);
+ * float vectors that bang_check_floats refuses.  N moves only after the last kernel of the call succeeded; a call that fails behind its checks
+ * (a HIP error, an abort word) leaves N where it was; if it had reached the back-edge launches, old rows may already list ids >= N: the engine then
+ * refuses every further bang_insert_e and bang_alloc_e with a message that says so, until bang_unload_e. */
+#define BANG_INSERT_MAX_BATCH 16384u
+int bang_insert_e(bang_engine_t* e, const void* h_vectors, uint32_t n, uint32_t L_build, float alpha, uint64_t* first_id);
+/* graph entries [first, first + n) of the loaded index (graph in HBM) as the index file holds them, n * entry_len bytes; and the packed PQ codes
+ * (n * m bytes, whatever the stride in HBM).  first + n <= N. */
+int bang_get_entries_e(bang_engine_t* e, uint64_t first, uint64_t n, void* out);
+int bang_get_codes_e(bang_engine_t* e, uint64_t first, uint64_t n, void* out);
 int bang_unload_e(bang_engine_t* e);                                                        /* bang.h:82 */
 
 /* statistics of the last bang_query_e */
@@ -325,6 +346,21 @@ typedef struct {
   uint64_t range_truncated;   /* ... of those queries, how many met more hits than the log holds (offered > range_hits) */
 } bang_stats_ext4;
 int bang_get_stats_ext4(bang_engine_t* e, bang_stats_ext4* out);
+/* ... and once more for inserts (option capacity + bang_insert_e): the earlier structs keep size and offsets.  The four counters are totals since
+ * the load */
+typedef struct {
+  bang_stats_ext4 ext4;
+  uint64_t capacity;          /* option capacity: nodes the tables hold, 0 = off */
+  uint64_t inserted;          /* points inserted */
+  uint64_t backedge_appended; /* old rows that took their new ids by appending */
+  uint64_t backedge_pruned;   /* old rows re-pruned from old row ++ new ids */
+  uint64_t backedge_dropped;  /* incoming ids dropped because a target's candidates exceeded BANG_PRUNE_MAX_LIST */
+} bang_stats_ext5;
+int bang_get_stats_ext5(bang_engine_t* e, bang_stats_ext5* out);
+/* Where the last bang_insert_e spent its time, milliseconds: ms6[0] the candidate searches, [1] worklist -> lists + prune of the new rows, [3] the
+ * back-edge launches (CSR upload included), [4] the PQ encode -- stream time between event stamps --, [2] the new rows' download + the host-side
+ * grouping and [5] the whole call, host wall time (allocations and copies included). */
+int bang_get_insert_times(bang_engine_t* e, double* ms6);
 /* Per-query counters of the last bang_query_e (arrays of num_queries words; any pointer may be NULL): PQ distance evaluations,
  * adjacency ids offered to the filter, expanded nodes (candidate-log length) and -- search kernel only, else zeros -- the number
  * of iterations the query ran.  Test hook: the oracle reports the same four numbers per query. */
@@ -757,6 +793,76 @@ int bang_search_exact_range_pull_geometry(int dtype, uint32_t L, uint32_t Q, uin
  * cap > BANG_RANGE_MAX_HITS, Q_total < q0 + nq.  nq = 0 is no launch. */
 int bang_k_range_sort(uint32_t* d_hit_ids, float* d_hit_dists, const uint32_t* d_offered, uint32_t cap, uint32_t q0, uint32_t nq, uint32_t Q_total,
                       uint32_t* d_count, void* stream);
+
+/* INSERTS, device side (csrc/bang_insert.hip; engine: bang_insert_e; DESIGN.md section 2 CANON 21, section 4.15).  Layouts are those of
+ * bang_search_can_rerank with the entry stride as the vector stride (8-bit: D % 16 == 0, D / 16 a power of two; float: D % 4 == 0; D <= 256); the
+ * wide layouts are BANG_ERR_UNSUPPORTED.  Every entry checks its arguments before any HIP call and names the offending one.
+ *
+ * bang_k_prune (prune_kernel): RobustPrune of n_lists ordered candidate lists on squared distances.  List i is the first
+ * min(d_list_cnt[i], list_stride, BANG_PRUNE_MAX_LIST) entries (c_j, d_j) of row i of d_list_ids / d_list_dists.  An entry whose id is d_own[i] is
+ * dropped.  Walking j ascending: an alive c_j is appended to the row, and the walk stops once the row holds R ids; otherwise every alive c_t, t > j,
+ * gets e = the exact distance of vector(c_t) to the query vector(c_j) -- exact_dist8 / exact_dist_f32, the arithmetic of bang_k_search_exact -- and
+ * dies if alpha2 * e <= d_t (one float32 multiply, one float32 compare).  The row goes to d_out + (out_by_own ? d_own[i] : i) * out_stride as
+ * [u32 degree][u32 id x R], unused slots 0.  d_own[i] == BANG_PRUNE_SKIP: list i is skipped and nothing is written for it.  An id >= n_nodes in a
+ * list is never dereferenced: the list counts as ended in front of it and *d_abort = 2 (out_by_own with d_own[i] >= n_nodes: skipped, *d_abort = 2).
+ * Wave-resident, one list per wave at a time, full workgroups sized by bang_wave_geometry (max_wgs / max_waves: caps if nonzero); wave w of the
+ * launch takes the lists w, w + waves, ... */
+#define BANG_PRUNE_MAX_LIST 512u
+#define BANG_PRUNE_SKIP 0xFFFFFFFFu
+typedef struct {
+  const uint8_t* d_graph;      /* [n_nodes][entry_len]: a node's vector opens its entry */
+  uint64_t entry_len;
+  uint32_t dtype, D, n_nodes, R;
+  float alpha2;                /* fl32(alpha) * fl32(alpha) rounded to float32, in [1, 64] */
+  uint32_t n_lists, list_stride;
+  const uint32_t* d_list_ids;  /* [n_lists][list_stride] */
+  const float* d_list_dists;   /* [n_lists][list_stride] */
+  const uint32_t* d_list_cnt;  /* [n_lists] */
+  const uint32_t* d_own;       /* [n_lists] */
+  void* d_out;
+  uint64_t out_stride;         /* bytes, divisible by 4, >= 4 (R + 1) */
+  uint32_t out_by_own;
+  uint32_t max_wgs, max_waves;
+  uint32_t* d_abort;           /* [1] or NULL */
+} bang_prune_params;
+int bang_k_prune(const bang_prune_params* p, void* stream);
+/* bang_k_worklist_lists: what bang_k_search_exact wrote at rr_k = L (d_wl_ids [Q_total][L] u64, d_wl_dists [L][Q_total]) as candidate lists for
+ * bang_k_prune, for the queries q0 .. q0 + nq - 1: row q of d_list_ids / d_list_dists ([Q_total][list_stride], list_stride >= L) holds the worklist
+ * entries in worklist order, d_list_cnt[q] the number in front of the first pad entry. */
+int bang_k_worklist_lists(const uint64_t* d_wl_ids, const float* d_wl_dists, uint32_t L, uint32_t q0, uint32_t nq, uint32_t Q_total,
+                          uint32_t* d_list_ids, float* d_list_dists, uint32_t list_stride, uint32_t* d_list_cnt, void* stream);
+/* bang_k_backedge: one wave per target.  Target i is the old node t = d_targets[i] (t < n_old, else it is skipped and *d_abort = 2) and
+ * I_t = d_srcs[d_offs[i] .. d_offs[i + 1]) the new ids that list it.  deg_t + |I_t| <= R: I_t is appended to t's row in its graph entry,
+ * d_offered[i] = 0, d_own_out[i] = BANG_PRUNE_SKIP.  Otherwise row i of d_cand_ids / d_cand_dists ([n_targets][BANG_PRUNE_MAX_LIST]) receives the
+ * old row followed by I_t, cut at BANG_PRUNE_MAX_LIST entries, and each one's exact distance to the query vector(t); d_offered[i] = their number,
+ * d_own_out[i] = t.  bang_k_range_sort (cap = BANG_PRUNE_MAX_LIST) and bang_k_prune (out_by_own) then write t's row.  d_stats[0..2] are incremented
+ * by the rows appended, the rows handed to the prune and the incoming ids the cut dropped. */
+typedef struct {
+  uint8_t* d_graph;
+  uint64_t entry_len;
+  uint32_t dtype, D, R, n_nodes, n_old, n_targets;
+  const uint32_t* d_targets;   /* [n_targets] */
+  const uint32_t* d_offs;      /* [n_targets + 1] */
+  const uint32_t* d_srcs;
+  uint32_t* d_cand_ids;
+  float* d_cand_dists;
+  uint32_t* d_offered;         /* [n_targets] */
+  uint32_t* d_own_out;         /* [n_targets] */
+  uint32_t* d_stats;           /* [3] */
+  uint32_t* d_abort;           /* [1] or NULL */
+} bang_backedge_params;
+int bang_k_backedge(const bang_backedge_params* p, void* stream);
+/* bang_k_pq_encode (pq_argmin_kernel behind bang_k_lut_build): the PQ codes of n vectors ([n][D], packed).  code[c] of a vector is the lowest k
+ * that minimises lut[c][k], K1's table with the vector as the query.  Row i goes to d_codes + i * code_stride (>= m), its bytes behind m written 0.
+ * d_lut holds the tables of lut_points vectors (lut_points * m * 256 floats): the batch runs in chunks of that many. */
+int bang_k_pq_encode(const float* d_pivots_T, const void* d_vectors, int dtype, const float* d_centroid, const uint32_t* d_chunk_off,
+                     float* d_lut, uint32_t lut_points, uint32_t n, uint32_t D, uint32_t m, uint8_t* d_codes, uint64_t code_stride, void* stream);
+/* Host side of an insert, no HIP call in it (csrc/bang_insert_group.cpp): the new rows of a batch grouped by target.  rows: n rows of row_stride
+ * words {degree, ids...} (row i belongs to the new node first_id + i).  Every (target, source) pair is sorted and the CSR written: targets
+ * ascending, offs, srcs (the new ids that list a target, ascending); the three arrays hold n * R, n * R + 1 and n * R words, R = row_stride - 1.
+ * BANG_ERR_ARG (no message) on a null argument, row_stride < 2, a degree > R or an id >= n_old. */
+int bang_insert_group(const uint32_t* rows, uint32_t n, uint32_t row_stride, uint32_t first_id, uint32_t n_old, uint32_t* targets, uint32_t* offs,
+                      uint32_t* srcs, uint32_t* n_targets);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
