@@ -18,6 +18,9 @@ constexpr uint32_t SEARCH_CHUNK = 1024;     // points per search launch: 1024 vi
 constexpr uint32_t TARGET_CHUNK = 8192;     // back-edge targets per launch: 8192 x 512 candidates x 8 B = 32 MB
 constexpr uint32_t ENCODE_CHUNK = 256;      // points per K1 launch: 256 x m x 1 KB of tables
 
+// test hooks: a chunk size from the environment is clamped to [1, the size above]; unset = the size above
+uint32_t chunk_of(long asked, uint32_t dflt) { return (uint32_t)std::min((long)dflt, std::max(1L, asked)); }
+
 // device temporaries of one call, freed on every way out
 struct Scratch {
   std::vector<void*> ptrs;
@@ -64,7 +67,10 @@ int insert_batch(bang_engine* e, const uint8_t* h_vectors, uint32_t n, uint32_t 
   const uint64_t el = e->entry_len;
   hipStream_t s = nullptr;
   Scratch sc;
-  const uint32_t QC = std::min(n, SEARCH_CHUNK);
+  const uint32_t search_chunk = chunk_of(env_long("BANG_INSERT_SEARCH_CHUNK", SEARCH_CHUNK), SEARCH_CHUNK);
+  const uint32_t target_chunk = chunk_of(env_long("BANG_INSERT_TARGET_CHUNK", TARGET_CHUNK), TARGET_CHUNK);
+  const uint32_t encode_chunk = chunk_of(env_long("BANG_INSERT_ENCODE_CHUNK", ENCODE_CHUNK), ENCODE_CHUNK);
+  const uint32_t QC = std::min(n, search_chunk);
   uint8_t* d_vecs = nullptr;
   uint32_t *d_bloom = nullptr, *d_cand_ids = nullptr, *d_cand_cnt = nullptr, *d_ctl = nullptr, *d_list_ids = nullptr, *d_list_cnt = nullptr, *d_own = nullptr;
   uint64_t* d_wl_ids = nullptr;
@@ -139,7 +145,7 @@ int insert_batch(bang_engine* e, const uint8_t* h_vectors, uint32_t n, uint32_t 
   ms[2] = ms_since(t_group);
   HIP_TRY(hipEventRecord(sc.ev[0], s));
   if (nt != 0) {
-    const uint32_t TC = std::min(nt, TARGET_CHUNK);
+    const uint32_t TC = std::min(nt, target_chunk);
     uint32_t *d_targets = nullptr, *d_offs = nullptr, *d_srcs = nullptr, *d_cids = nullptr, *d_offered = nullptr, *d_count = nullptr, *d_own_out = nullptr;
     float* d_cdists = nullptr;
     BANG_TRY(sc.get(&d_targets, nt));
@@ -177,7 +183,7 @@ int insert_batch(bang_engine* e, const uint8_t* h_vectors, uint32_t n, uint32_t 
   // step 5: PQ codes at the engine's stride
   {
     float* d_lut = nullptr;
-    const uint32_t EC = std::min(n, ENCODE_CHUNK);
+    const uint32_t EC = std::min(n, encode_chunk);
     BANG_TRY(sc.get(&d_lut, (size_t)EC * e->m * 256));
     BANG_TRY(bang_k_pq_encode(e->d_pivots_T, d_vecs, e->dtype, e->d_centroid, e->d_chunk_off, d_lut, EC, n, D, e->m,
                               e->d_codes + (uint64_t)N * e->code_stride, e->code_stride, s));

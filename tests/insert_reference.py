@@ -13,7 +13,9 @@ numpy:
 5. ``code[c]`` = the lowest k minimising ``orc_lut_build``'s table entry ``lut[c][k]`` with the new vector as the query;
 6. N grows by n; the medoid stays.
 
-stats: dict(inserted, appended, pruned, dropped, medoid_row_changed, max_incoming).
+stats: dict(inserted, appended, pruned, dropped, medoid_row_changed, max_incoming, targets, target_pruned) -- ``targets`` are the old nodes the
+new rows list, ascending (the order of bang_insert_group's CSR, so a chunk of the back-edge step is a slice of it), ``target_pruned[i]`` says
+whether targets[i] overflowed (pruned) or took its ids by appending.
 """
 from __future__ import annotations
 
@@ -40,8 +42,12 @@ def vector_of(ref: Reference, node: int) -> np.ndarray:
     return np.ascontiguousarray(ref.graph[node, :vb]).view(NP_DTYPE[ix.dtype]).copy()
 
 
-def prune(ref: Reference, own: int, ids, dists, R: int, alpha2) -> np.ndarray:
-    """RobustPrune of the ordered list (ids[j], dists[j]) -> the row's ids (uint32, at most R)."""
+def prune(ref: Reference, own: int, ids, dists, R: int, alpha2, strict: bool = False, wide: bool = False, ties: list | None = None) -> np.ndarray:
+    """RobustPrune of the ordered list (ids[j], dists[j]) -> the row's ids (uint32, at most R).
+
+    The rule is the default.  Two WRONG variants exist so that tests/test_insert_reference.py can show that an input tells them apart:
+    ``strict`` kills on ``<`` instead of ``<=``; ``wide`` forms ``alpha2 * e`` in float64 instead of rounding the product to float32.
+    ``ties`` (a list) receives, per picked candidate, the number of kills decided at ``alpha2 * e == d_t`` exactly."""
     ids = np.asarray(ids, dtype=np.uint32)
     dists = np.asarray(dists, dtype=np.float32)
     keep = ids != np.uint32(own)
@@ -59,7 +65,10 @@ def prune(ref: Reference, own: int, ids, dists, R: int, alpha2) -> np.ndarray:
         if len(t) == 0:
             break
         e = ref.exact(ids[t], vector_of(ref, int(ids[j])))
-        dead = (alpha2 * e).astype(np.float32) <= dists[t]
+        scaled = np.float64(alpha2) * e.astype(np.float64) if wide else (alpha2 * e).astype(np.float32)
+        dead = scaled < dists[t] if strict else scaled <= dists[t]
+        if ties is not None:
+            ties.append(int((dead & (scaled == dists[t])).sum()))
         alive[t[dead]] = False
     return np.array(out, dtype=np.uint32)
 
@@ -105,10 +114,11 @@ def insert(ix, vectors: np.ndarray, L_build: int, alpha: float):
         for t in r:
             incoming.setdefault(int(t), []).append(N + i)
     st = dict(inserted=n, appended=0, pruned=0, dropped=0, medoid_row_changed=int(ix.medoid) in incoming,
-              max_incoming=max((len(v) for v in incoming.values()), default=0))
+              max_incoming=max((len(v) for v in incoming.values()), default=0),
+              targets=np.array(sorted(incoming), dtype=np.uint32), target_pruned=np.zeros(len(incoming), dtype=bool))
     vb = ix.D * old.tsize
     g = ref.graph
-    for t in sorted(incoming):
+    for ti, t in enumerate(sorted(incoming)):
         assert t < N
         new = np.array(sorted(incoming[t]), dtype=np.uint32)
         row = g[t, vb:].view(np.uint32)                                  # [degree][id x R], a view: edits land in the graph
@@ -129,4 +139,5 @@ def insert(ix, vectors: np.ndarray, L_build: int, alpha: float):
         row[1: 1 + len(out)] = out
         row[0] = len(out)
         st["pruned"] += 1
+        st["target_pruned"][ti] = True
     return dataclasses.replace(grown, graph=g), st

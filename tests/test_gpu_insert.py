@@ -1,6 +1,9 @@
 """Inserts on a GPU (csrc/bang_insert.hip, bang_insert_e), bit for bit against tests/insert_reference.py: bang_k_prune on lists of 0 .. 512
-entries, bang_k_pq_encode on the four pivot layouts, and the engine -- entries and codes after one and two batches, an engine loaded from the
-export against the engine that inserted, an excluded inserted id, and the refusals."""
+entries, at every vector layout, at the edges of its kill rule (lattice points: alpha2 * e == d_t, the float32 rounding of the product), at R = 1
+and 5, with count words beyond the stride and beyond 512, and into a copy of the graph table; bang_k_backedge at every layout and on its edge
+targets; bang_k_pq_encode on the four pivot layouts and at m = 1 .. 129 with ties; and the engine -- entries and codes after one and two batches,
+with the three chunk seams crossed (test hooks BANG_INSERT_*_CHUNK), an engine loaded from the export against the engine that inserted in
+every search form, an excluded inserted id, and the refusals."""
 import ctypes as C
 import dataclasses
 
@@ -33,15 +36,11 @@ def _ref(name):
 # ---------------------------------------------------------------------------------------------------------------------
 def _make_list(ref, rng, node, length, pool=None):
     """An ordered candidate list of `length` distinct ids around `node`: ascending exact distance to its vector, as a worklist is."""
-    pool = ref.ix.N if pool is None else pool
-    ids = rng.choice(pool, length, replace=False).astype(np.uint32)
-    d = ref.exact(ids, IR.vector_of(ref, node))
-    o = np.argsort(d, kind="stable")
-    return ids[o], d[o]
+    return I.make_list(ref, rng, node, length, pool)
 
 
-def _prune_gpu(ix, lists, owns, R, alpha, graph_ptr=None, entry_len=None, n_nodes=None, max_wgs=0, max_waves=0, stride=None):
-    """-> (rows u32 [n_lists][R + 1], abort word)"""
+def _prune_gpu(ix, lists, owns, R, alpha, graph_ptr=None, entry_len=None, n_nodes=None, max_wgs=0, max_waves=0, stride=None, cnt_words=None):
+    """-> (rows u32 [n_lists][R + 1], abort word); cnt_words: the count words as the kernel reads them (default: the lists' lengths)"""
     from bang_amd import binding as B
     n = len(lists)
     stride = stride or max(1, max(len(l[0]) for l in lists))
@@ -50,6 +49,8 @@ def _prune_gpu(ix, lists, owns, R, alpha, graph_ptr=None, entry_len=None, n_node
     cnt = np.zeros(n, np.uint32)
     for i, (a, b) in enumerate(lists):
         ids[i, :len(a)], d[i, :len(a)], cnt[i] = a, b, len(a)
+    if cnt_words is not None:
+        cnt[:] = cnt_words
     keep = []
     if graph_ptr is None:
         g = B.DeviceBuffer.from_numpy(ix.graph, slack=256)
@@ -83,13 +84,7 @@ def _want_rows(ref, lists, owns, R, alpha):
     return rows
 
 
-@pytest.mark.parametrize("alpha", [1.2, 8.0])
-@pytest.mark.parametrize("R", [32, 64])
-@pytest.mark.parametrize("name", ["i8", "u8", "deep", "f32"])
-def test_prune_every_length(name, R, alpha):
-    """lists of 0, 1, 63, 64, 65 and 512 entries, three of each, one with its own id inside; 8 waves in 4 workgroups of two take 19 lists:
-    every wave takes a second list and the last round leaves workgroups partly idle"""
-    ref = _ref(name)
+def _nineteen_lists(ref, R, alpha):
     ix = ref.ix
     rng = np.random.default_rng(R + int(alpha * 10) + ix.D)
     lists, owns = [], []
@@ -101,6 +96,18 @@ def test_prune_every_length(name, R, alpha):
     lists.append(_make_list(ref, rng, 5, 100))
     owns.append(int(lists[-1][0][3]))                                      # its own id inside the list
     assert len(lists) == 19
+    return lists, owns
+
+
+@pytest.mark.parametrize("alpha", [1.2, 8.0])
+@pytest.mark.parametrize("R", [32, 64])
+@pytest.mark.parametrize("name", ["i8", "u8", "deep", "f32"])
+def test_prune_every_length(name, R, alpha):
+    """lists of 0, 1, 63, 64, 65 and 512 entries, three of each, one with its own id inside; 8 waves in 4 workgroups of two take 19 lists:
+    every wave takes a second list and the last round leaves workgroups partly idle"""
+    ref = _ref(name)
+    ix = ref.ix
+    lists, owns = _nineteen_lists(ref, R, alpha)
     want = _want_rows(ref, lists, owns, R, alpha)
     assert (want[:, 0] == R).any() or alpha < 8.0
     got, abort = _prune_gpu(ix, lists, owns, R, alpha, max_wgs=4, max_waves=2)
@@ -162,6 +169,113 @@ def test_prune_row_addressing_beyond_4_gib(name):
     assert abort == 0 and np.array_equal(got, want)
     picked = np.concatenate([want[i, 1:1 + want[i, 0]] for i in range(len(lists))])
     assert (picked >= 128).any(), "no picked candidate lies beyond 4 GiB: its vector is what a wrapped offset would miss"
+
+
+@pytest.mark.parametrize("name", sorted(I.LAYOUTS))
+def test_prune_every_layout(name):
+    """the picked candidate's vector as the wave's query at the layouts the four indexes leave out: G = 1, 2 and 16 pieces (8-bit D = 16, 32, 256),
+    float D = 4, D = 160 (a partly filled third register), D = 200 (a partly filled fourth) and D = 256 (four full registers); lists of 1, 64, 65 and 200 entries"""
+    ix = I.layout(name)
+    ref = Reference(ix)
+    rng = np.random.default_rng(ix.D)
+    owns = [int(t) for t in rng.integers(ix.N, size=4)]
+    lists = [_make_list(ref, rng, t, n) for t, n in zip(owns, (1, 64, 65, 200))]
+    want = _want_rows(ref, lists, owns, ix.R, 1.2)
+    assert (want[1:, 0] >= 2).all(), "a list with one pick computes no distance"
+    got, abort = _prune_gpu(ix, lists, owns, ix.R, 1.2, max_wgs=2, max_waves=2)
+    assert abort == 0 and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("alpha", [1.0, 1.2])
+@pytest.mark.parametrize("kind", sorted(I.LATTICES))
+@pytest.mark.parametrize("iname", ["i8", "u8"])
+def test_prune_kill_rule_on_lattice_points(iname, kind, alpha):
+    """integer lattice points: at alpha = 1 kills are decided at alpha2 * e == d_t ('<=', not '<'), at alpha = 1.2 by the float32 rounding of the one
+    multiply (tests/test_insert_reference.py shows on the CPU that a rule with '<', or with an unrounded product, gives other rows)"""
+    ix = I.lattice(iname, kind)
+    ref = Reference(ix)
+    lists, owns = I.lattice_lists(iname, kind)
+    want = _want_rows(ref, lists, owns, ix.R, alpha)
+    got, abort = _prune_gpu(ix, lists, owns, ix.R, alpha, max_wgs=2, max_waves=2)
+    assert abort == 0 and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("R", [1, 5])
+def test_prune_rows_of_one_and_of_five_ids(R):
+    """R = 1: the row is full at the first pick; R = 5: an odd row, 6 of 64 lanes store it"""
+    ref = _ref("i8")
+    lists, owns = _nineteen_lists(ref, R, 1.2)
+    want = _want_rows(ref, lists, owns, R, 1.2)
+    assert (want[:, 0] == R).any() and (want[:, 0] == 0).any()
+    got, abort = _prune_gpu(ref.ix, lists, owns, R, 1.2, max_wgs=4, max_waves=2)
+    assert abort == 0 and np.array_equal(got, want)
+
+
+def test_prune_count_words_beyond_the_stride_and_beyond_512():
+    """a count word of stride + 9 reads `stride` entries (behind them lie the next list's, which would change the row); 600 entries at a stride of
+    600 are cut at 512 (the entries behind would change the row)"""
+    ref = _ref("i8")
+    ix = ref.ix
+    rng = np.random.default_rng(21)
+    lists = [_make_list(ref, rng, 40, 70), _make_list(ref, rng, 41, 70)]
+    owns = [40, 41]
+    want = _want_rows(ref, lists, owns, ix.R, 1.2)
+    over = (np.concatenate([lists[0][0], lists[1][0][:9]]), np.concatenate([lists[0][1], lists[1][1][:9]]))
+    assert not np.array_equal(_want_rows(ref, [over], owns[:1], ix.R, 1.2)[0], want[0]), "the nine entries behind the stride would not show"
+    got, abort = _prune_gpu(ix, lists, owns, ix.R, 1.2, stride=70, cnt_words=[79, 70])
+    assert abort == 0 and np.array_equal(got, want)
+    # 600 entries in order: the nearest id 501 times (the copies die at e = 0), 11 more in front of entry 512 and 88 behind it
+    long = []
+    for node in (42, 43):
+        a, b = _make_list(ref, rng, node, 100)
+        rep = np.concatenate([np.zeros(501, np.int64), np.arange(1, 100)])
+        long.append((a[rep], b[rep]))
+        assert len(long[-1][0]) == 600
+    cut = [(a[:512], b[:512]) for a, b in long]
+    want = _want_rows(ref, cut, [42, 43], ix.R, 1.2)
+    assert not np.array_equal(_want_rows(ref, long, [42, 43], ix.R, 1.2), want), "the entries behind 512 would not show"
+    got, abort = _prune_gpu(ix, long, [42, 43], ix.R, 1.2, stride=600, cnt_words=[600, 600])
+    assert abort == 0 and np.array_equal(got, want)
+
+
+def test_prune_into_the_graph_table_changes_the_named_rows_only():
+    """the engine's call shape: out_by_own = 1, d_out = graph + vec_bytes, out_stride = entry_len -- between two rows lie other nodes' vectors; a
+    tenth list with own = n_nodes sets the abort word and leaves the (marked) entry behind the table alone"""
+    from bang_amd import binding as B
+    ref = _ref("u8")
+    ix = ref.ix
+    vb, R = ix.D, ix.R
+    rng = np.random.default_rng(8)
+    owns = [int(x) for x in rng.choice(ix.N, 9, replace=False)] + [ix.N]  # nine rows of the table; the tenth lies behind it
+    lists = [_make_list(ref, rng, t if t < ix.N else 0, n) for t, n in zip(owns, (0, 1, 40, 64, 65, 100, 130, 200, 512, 80))]
+    n = len(lists)
+    stride = 512
+    ids, d, cnt = np.zeros((n, stride), np.uint32), np.zeros((n, stride), np.float32), np.zeros(n, np.uint32)
+    for i, (a, b) in enumerate(lists):
+        ids[i, :len(a)], d[i, :len(a)], cnt[i] = a, b, len(a)
+    # the table with two marked spare entries behind node N - 1: a row written for own = N would land in the first of them
+    table = np.concatenate([ix.graph, np.full((2, ix.entry_len), 0xA5, np.uint8)])
+    g = B.DeviceBuffer.from_numpy(table, slack=256)
+    bufs = [B.DeviceBuffer.from_numpy(x) for x in (ids, d, cnt, np.asarray(owns, np.uint32))]
+    ab = B.DeviceBuffer(4)
+    p = B.PruneParams()
+    p.d_graph, p.entry_len, p.dtype, p.D, p.n_nodes, p.R = g.ptr, ix.entry_len, B.DTYPE_CODE[ix.dtype], ix.D, ix.N, R
+    p.alpha2, p.n_lists, p.list_stride = float(IR.alpha2_of(1.2)), n, stride
+    p.d_list_ids, p.d_list_dists, p.d_list_cnt, p.d_own = (b.ptr for b in bufs)
+    p.d_out, p.out_stride, p.out_by_own, p.max_wgs, p.max_waves, p.d_abort = g.ptr + vb, ix.entry_len, 1, 2, 2, ab.ptr
+    fn = B.lib().bang_k_prune
+    fn.argtypes = [C.c_void_p, C.c_void_p]
+    B._check(fn(C.byref(p), None), "bang_k_prune")
+    B.sync()
+    after, abort = g.download(np.uint8, table.shape), int(ab.download(np.uint32, (1,))[0])
+    for b in bufs + [g, ab]:
+        b.free()
+    want = table.copy()
+    want[owns[:9], vb:] = _want_rows(ref, lists[:9], owns[:9], R, 1.2).view(np.uint8)
+    assert abort == 2, "a row outside the table was not reported"
+    assert (after[ix.N:] == 0xA5).all(), "the list whose own node lies behind the table wrote a row"
+    assert np.array_equal(after, want), "the nine rows, and no other byte of the table"
+    assert not np.array_equal(after[:ix.N], ix.graph)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -263,6 +377,86 @@ def test_backedge_appends_overflows_and_never_follows_an_id_outside_the_index(na
         assert stats == [1, 1 if upto == 2 else 2, 0]
 
 
+@pytest.mark.parametrize("name", sorted(I.LAYOUTS))
+def test_backedge_every_layout(name):
+    """the target's vector as the wave's query at every layout: one target that appends, one whose candidates (old row ++ new ids) get their exact
+    distances"""
+    from bang_amd import formats
+    ix = I.layout(name)
+    R, N, vb = ix.R, ix.N, ix.D * (4 if ix.dtype == "float" else 1)
+    new = I.batch(ix, 16, 3)
+    graph = np.concatenate([ix.graph, formats.pack_graph(new, np.zeros(16, np.uint32), np.zeros((16, R), np.uint32))])
+    rows = graph[:, vb:].view(np.uint32)
+    t0, t1 = (int(x) for x in np.flatnonzero(rows[:N, 0] == R)[:2])
+    rows[t0, 0] = R - 2
+    rows[t0, 1 + R - 2:] = 0
+    before = graph.copy()
+    inc = [np.array([N + 3, N + 11]), np.array([N, N + 7, N + 15])]
+    ref = Reference(dataclasses.replace(ix, N=N + 16, graph=before, codes=np.zeros((N + 16, ix.m), np.uint8)))
+    after, ci, cd, offered, own, stats, abort = _backedge_gpu(ix, before, N + 16, [t0, t1], inc)
+    want = before.copy()
+    wrows = want[:, vb:].view(np.uint32)
+    wrows[t0, 1 + R - 2: 1 + R] = inc[0]
+    wrows[t0, 0] = R
+    assert abort == 0 and stats == [1, 1, 0] and np.array_equal(after, want)
+    cand = np.concatenate([before[t1, vb:].view(np.uint32)[1:1 + R], inc[1]]).astype(np.uint32)
+    assert list(offered) == [0, R + 3] and list(own) == [0xFFFFFFFF, t1]
+    assert np.array_equal(ci[1, :R + 3], cand) and np.array_equal(cd[1, :R + 3], _bits(ref.exact(cand, IR.vector_of(ref, t1))))
+    assert (ci[0] == 0xCDCDCDCD).all() and (ci[1, R + 3:] == 0xCDCDCDCD).all() and (cd[1, R + 3:] == 0xCDCDCDCD).all()
+
+
+@pytest.mark.parametrize("name", ["i8", "u8", "f32"])
+def test_backedge_edges(name):
+    """seven targets per launch (the last workgroup runs 3 of its 4 waves): no incoming id; an empty row that takes R ids; a row of one id that
+    overflows with R + 1 candidates; 130 incoming ids (three 64-lane pieces of the source part); a row word of R + 7 (read as R); 64 + 500 candidates
+    (cut at 512, 52 dropped); an id outside the index at source position 0, or -- second launch -- at candidate 64, the start of a piece"""
+    from bang_amd import formats
+    ix, _ = I.get(name)
+    R, N, vb = ix.R, ix.N, ix.D * (4 if ix.dtype == "float" else 1)
+    NEW, SKIP, MARK = 600, 0xFFFFFFFF, 0xCDCDCDCD
+    new = I.batch(ix, NEW, 9)
+    graph = np.concatenate([ix.graph, formats.pack_graph(new, np.zeros(NEW, np.uint32), np.zeros((NEW, R), np.uint32))])
+    rows = graph[:, vb:].view(np.uint32)
+    t = [int(x) for x in np.flatnonzero(rows[:N, 0] == R)[:8]]
+    assert len(t) == 8
+    rows[t[1], :] = 0                                                      # an empty row
+    rows[t[2], 0] = 1
+    rows[t[2], 2:] = 0
+    rows[t[4], 0] = R + 7                                                  # a corrupt degree word over a sound row
+    deg_b = min(R, 40)                                                     # the last target: the bad id becomes candidate 64
+    rows[t[7], 0] = deg_b
+    rows[t[7], 1 + deg_b:] = 0
+    before = graph.copy()
+    bad = N + NEW + 5
+    ids = lambda k, first=0: (N + first + np.arange(k)).astype(np.uint32)  # noqa: E731
+    inc = [ids(0), ids(R, 7), ids(R, 100), ids(130, 50), ids(3, 590), ids(64 + 500 - R), np.concatenate([[bad], ids(2, 20)]).astype(np.uint32),
+           np.concatenate([ids(64 - deg_b, 300), [bad], ids(5, 400)]).astype(np.uint32)]
+    deg = [R, 0, 1, R, R, R, R, deg_b]                                     # as the kernel reads them
+    assert all(deg[i] + len(inc[i]) > R for i in (2, 3, 4, 5, 6, 7)) and deg[1] + len(inc[1]) == R and deg[7] + len(inc[7]) > 64
+    ref = Reference(dataclasses.replace(ix, N=N + NEW, graph=before, codes=np.zeros((N + NEW, ix.m), np.uint8)))
+    for launch in ([0, 1, 2, 3, 4, 5, 6], [7, 0, 1, 2, 3, 4, 5]):
+        after, ci, cd, offered, own, stats, abort = _backedge_gpu(ix, before, N + NEW, [t[i] for i in launch], [inc[i] for i in launch])
+        assert abort == 2
+        want = before.copy()
+        wrows = want[:, vb:].view(np.uint32)
+        wrows[t[1], 0] = R
+        wrows[t[1], 1:] = inc[1]
+        assert np.array_equal(after, want), "the row that appended R ids, and no other byte of the table (a target without incoming ids keeps its row)"
+        for slot, i in enumerate(launch):
+            if i in (0, 1):                                                # appended
+                assert offered[slot] == 0 and own[slot] == SKIP and (ci[slot] == MARK).all() and (cd[slot] == MARK).all(), i
+                continue
+            cand = np.concatenate([before[t[i], vb:].view(np.uint32)[1:1 + deg[i]], inc[i]]).astype(np.uint32)[:512]
+            if (cand == bad).any():
+                cand = cand[:int(np.argmax(cand == bad))]                  # the list ends in front of the id
+            n = len(cand)
+            assert n == {2: R + 1, 3: R + 130, 4: R + 3, 5: 512, 6: R, 7: 64}[i]
+            assert offered[slot] == n and own[slot] == t[i], i
+            assert np.array_equal(ci[slot, :n], cand) and np.array_equal(cd[slot, :n], _bits(ref.exact(cand, IR.vector_of(ref, t[i])))), i
+            assert (ci[slot, n:] == MARK).all() and (cd[slot, n:] == MARK).all(), i
+        assert stats == [2, 5, 52]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # bang_k_pq_encode
 # ---------------------------------------------------------------------------------------------------------------------
@@ -305,6 +499,20 @@ def test_pq_encode_lowest_argmin(name):
     assert not (want == max(hi, lo)).any()
     for stride in (ix.m, 128):
         got = _encode_gpu(ix2, v, 5, stride)
+        assert np.array_equal(got[:, :ix.m], want), stride
+        assert not got[:, ix.m:].any(), "pad bytes of a row are 0"
+
+
+@pytest.mark.parametrize("name", sorted(I.PQ_LAYOUTS))
+def test_pq_encode_chunk_passes_and_ties(name):
+    """m = 1, 64, 65, 128, 129: one to three passes of 64 chunks with tails of 0 and 1; equal pivot rows k and k + 64 (one lane's strict '<'), 70 and
+    133 (the lower k in the higher lane: the second word of the wave's minimum), 0 and 255; 9 vectors in chunks of 4 tables"""
+    ix, v = I.pq_layout(name)
+    ref = Reference(ix)
+    want = np.stack([IR.encode(ref, x) for x in v])
+    assert all((want == lo).any() for lo, _ in I.PQ_TIES)
+    for stride in (ix.m, ix.m + 3):
+        got = _encode_gpu(ix, v, 4, stride)
         assert np.array_equal(got[:, :ix.m], want), stride
         assert not got[:, ix.m:].any(), "pad bytes of a row are 0"
 
@@ -361,6 +569,36 @@ def test_back_edges_beyond_the_candidate_cap():
         assert np.array_equal(e.entries(0, ix2.N), ix2.graph) and np.array_equal(e.codes(0, ix2.N), ix2.codes)
         s = e.insert_stats()
         assert (s["backedge_dropped"], s["backedge_appended"], s["backedge_pruned"]) == (st["dropped"], st["appended"], st["pruned"])
+
+
+@pytest.mark.parametrize("name", sorted(I.SEAMS))
+def test_chunk_seams_change_nothing(name, monkeypatch):
+    """the search + prune, back-edge and encode steps in small chunks (test hooks): the reference knows no chunks, so entries, codes and statistics
+    are its own.  tests/test_insert_reference.py shows that every seam is crossed with data that differ from the first chunk's"""
+    ix, v, L, alpha, ix2, st = I.seam_case(name)
+    for var, val in zip(("BANG_INSERT_SEARCH_CHUNK", "BANG_INSERT_TARGET_CHUNK", "BANG_INSERT_ENCODE_CHUNK"), I.SEAMS[name]):
+        monkeypatch.setenv(var, str(val))
+    with _engine(ix, ix.N + len(v) + 3) as e:
+        assert e.insert(v, L, alpha) == ix.N
+        entries, codes, s = e.entries(0, ix2.N), e.codes(0, ix2.N), e.insert_stats()
+    assert np.array_equal(entries, ix2.graph)
+    assert np.array_equal(codes, ix2.codes)
+    assert s == dict(capacity=ix.N + len(v) + 3, inserted=st["inserted"], backedge_appended=st["appended"], backedge_pruned=st["pruned"],
+                     backedge_dropped=st["dropped"])
+
+
+def test_chunk_hooks_are_clamped(monkeypatch):
+    """the lower clamp: 0 and a negative value are taken as 1 (a chunk of 0 would never end).  A value above the engine's own size is merely
+    accepted here: with 16 points the upper clamp cannot show in a result"""
+    ix, v, L, alpha = I.case("i8_a8")
+    ix2, st = I.reference("i8_a8")
+    for vals in (("0", "-5", "0"), ("100000", "100000", "100000")):
+        for var, val in zip(("BANG_INSERT_SEARCH_CHUNK", "BANG_INSERT_TARGET_CHUNK", "BANG_INSERT_ENCODE_CHUNK"), vals):
+            monkeypatch.setenv(var, val)
+        with _engine(ix, ix.N + len(v)) as e:
+            assert e.insert(v, L, alpha) == ix.N
+            assert np.array_equal(e.entries(0, ix2.N), ix2.graph) and np.array_equal(e.codes(0, ix2.N), ix2.codes), vals
+            assert e.insert_stats()["backedge_pruned"] == st["pruned"]
 
 
 def test_a_wide_layout_is_refused():
@@ -487,3 +725,167 @@ def test_refusals():
         assert np.array_equal(e.entries(0, ix.N), before), "a refused insert left a trace"
         assert e.insert(v, L, alpha) == ix.N                               # ... and the engine still inserts
         assert np.array_equal(e.entries(0, ix.N + len(v)), I.reference("deep_a12")[0].graph)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every search form the engine offers with the graph in HBM, on an engine that inserted
+# ---------------------------------------------------------------------------------------------------------------------
+FORM_L = 48
+# form -> (options for bang_load, options for bang_alloc, the cases it runs on)
+_WALK = ("i8_a12", "f32_a12")
+FORMS = {
+    "search0":        ({}, dict(distance=0, search=0), _WALK),
+    "search1":        ({}, dict(distance=0, search=1, fuse_rerank=1), _WALK),
+    "fuse_rerank0":   ({}, dict(distance=0, search=1, fuse_rerank=0), _WALK),
+    "semantics1":     ({}, dict(distance=0, search=1, semantics=1), _WALK),
+    "filter_layout1": ({}, dict(distance=0, search=1, filter_layout=1), _WALK),
+    "beam2":          ({}, dict(distance=1, search=1, beam=2), _WALK),
+    "beam4":          ({}, dict(distance=1, search=1, beam=4), _WALK),
+    "range":          ({}, dict(distance=1, search=1, range_hits=512), _WALK),
+    "labels":         ({}, dict(distance=1, search=1), _WALK),
+    "pq1":            (dict(pq=1), dict(distance=0, search=1), I.FORM_CASES),
+    "code_stride0":   (dict(code_stride=0), dict(distance=0, search=1), I.FORM_CASES),
+    "pq_ragged0":     (dict(pq_ragged=0), dict(distance=0, search=1), I.FORM_CASES),     # (no counter tells the padded pivot table from the exact-size
+}                                                                                        #  one, and the answers are the same by design)
+
+
+def _cached(key, fn):
+    if key not in _CACHE:
+        _CACHE[key] = fn()
+    return _CACHE[key]
+
+
+def _form_reference(form, name, ix2, q):
+    """what the CPU reference of the form answers on Index': a dict of the arrays _form_run returns (a subset: what the reference defines)"""
+    if form in ("search0", "search1", "fuse_rerank0", "pq1", "code_stride0", "pq_ragged0"):
+        from oracle import oracle as O
+        ids, d, st = _cached(("oracle", name), lambda: O.Oracle(ix2).search(q, K, FORM_L, with_stats=True))
+        out = dict(ids=ids, d=_bits(d))
+        if form != "search0":                                              # (the per-iteration kernels keep no per-query counters)
+            out["counters"] = st
+        return out
+    # semantics and beam have no counter in bang_get_stats: that the option took effect shows in the reference's answer, which must therefore
+    # differ from the plain walk's (asserted here) -- an engine that ignored the option would give the plain walk's counters
+    if form == "semantics1":
+        import inmemory_reference
+        from oracle import oracle as O
+        ids, d, st = inmemory_reference.Reference(ix2).search(q, K, FORM_L, "inmemory")
+        plain = _cached(("oracle", name), lambda: O.Oracle(ix2).search(q, K, FORM_L, with_stats=True))
+        assert not np.array_equal(st, plain[2]), "the Inmemory walk's counters equal BANG_Base's on these queries"
+        return dict(ids=ids, d=_bits(d), counters=st)
+    if form == "filter_layout1":
+        import wordfilter_reference
+        ids, d, st = wordfilter_reference.Reference(ix2).search(q, K, FORM_L, "word")
+        return dict(ids=ids, d=_bits(d), counters=st)
+    if form in ("beam2", "beam4"):
+        import beam_reference
+        ids, d, st, _ = beam_reference.Reference(ix2).search(q, K, FORM_L, int(form[4:]))
+        plain = _cached(("exact", name), lambda: Reference(ix2).search(q, K, FORM_L, "exact"))
+        assert not np.array_equal(st, plain[2]), "the beam walk's counters equal the one-parent walk's on these queries"
+        return dict(ids=ids, d=_bits(d), counters=st)
+    if form == "range":
+        import range_reference as RR
+        ref = _cached(("range ref", name), lambda: RR.Reference(ix2))
+        tr = ref.evaluated_all(q, FORM_L)
+        top_ids, top_d, top_st = _cached(("exact", name), lambda: Reference(ix2).search(q, K, FORM_L, "exact"))   # the same walk's k results
+        out = {}
+        for rname, r in _form_radii(name, ix2, q):
+            lims, ids, d, counts, offered = RR.collect_all(tr, r, 512)
+            out[rname] = dict(ids=top_ids, d=_bits(top_d), lims=lims, hit_ids=ids, hit_d=_bits(d), counts=counts, offered=offered,
+                              counters=np.array([t.stats for t in tr], np.int64))
+            assert np.array_equal(out[rname]["counters"], top_st)
+        return out
+    if form == "labels":
+        import labels_inputs as LI
+        import labels_reference as LR
+        any_, all_ = LI.batch("mixed", q.shape[0])
+        ids, d, matched, st, _ = LR.collect_all(LR.Reference(ix2).walks(q, FORM_L), LI.rand4(ix2.N), any_, all_, K, FORM_L, int(ix2.medoid))
+        return dict(ids=ids, d=_bits(d), matched=matched, counters=st)
+    raise ValueError(form)
+
+
+def _form_radii(name, ix2, q):
+    import range_inputs as RI
+    import range_reference as RR
+    ref = _cached(("range ref", name), lambda: RR.Reference(ix2))
+    return [(r, RI.radii(r, ref, ix2, q)) for r in ("rank100", "mixed")]
+
+
+def _form_run(e, form, alloc_opts, name, ix2, q):
+    """one batch (two for the range form: one per set of radii) on a loaded, unallocated engine -> dict of arrays"""
+    Q = q.shape[0]
+    for key, val in alloc_opts.items():
+        e.set_option(key, val)
+    e.set_searchparams(K, FORM_L)
+    if form == "labels":
+        import labels_inputs as LI
+        e.set_labels(LI.rand4(ix2.N))
+    e.alloc(Q)
+    if form == "range":
+        out = {}
+        for rname, r in _form_radii(name, ix2, q):
+            e.set_radii(r)
+            e.init(Q)
+            ids, d = e.query(q)
+            counts, offered = e.range_counts(Q)
+            lims, hit_ids, hit_d = e.range_results(Q)
+            out[rname] = dict(ids=ids, d=_bits(d), counters=e.query_counters(Q), counts=counts, offered=offered, lims=lims, hit_ids=hit_ids,
+                              hit_d=_bits(hit_d))
+            st = e.stats()
+            assert st["search_kernel"] == 1 and st["range_launches"] == 1 and st["range_queries"] == Q and st["range_hits"] == 512, (form, st)
+        e.free()
+        return out
+    if form == "labels":
+        e.set_filters(*LI.batch("mixed", Q))
+    e.init(Q)
+    ids, d = e.query(q)
+    out = dict(ids=ids, d=_bits(d), counters=e.query_counters(Q))
+    if form == "labels":
+        out["matched"] = e.matched_counts(Q)
+    # the engine ran the form that was asked for
+    st = e.stats()
+    assert st["search_kernel"] == (0 if form == "search0" else 1) and st["front_launches"] >= 1, (form, st)
+    if form in ("fuse_rerank0", "pq1"):                                    # (the LUT-path kernel never fuses the re-rank; the LDS-table kernel does,
+        assert st["rerank_fused"] == 0, st                                 #  which is how pq = 1 shows in the counters)
+    if form in ("search1", "code_stride0"):
+        assert st["rerank_fused"] == 1, st
+    if form == "filter_layout1":
+        assert st["filter_layout"] == 1, st
+    if form == "labels":
+        assert st["label_launches"] == 1 and st["labelled"] == ix2.N and st["filtered_queries"] == 16, st
+    if form == "code_stride0":
+        assert st["code_stride"] == ix2.m, st
+    e.free()
+    return out
+
+
+def _same_dicts(got, want, what, subset=False):
+    """every array of `want` equals that of `got`; unless subset, they hold the same arrays"""
+    assert subset or sorted(got) == sorted(want), what
+    for key, w in want.items():
+        if isinstance(w, dict):
+            _same_dicts(got[key], w, what + (key,), subset)
+        else:
+            assert np.array_equal(got[key], w), what + (key,)
+
+
+@pytest.mark.parametrize("form", sorted(FORMS))
+def test_every_form_after_an_insert(form):
+    """engine A loads with capacity and inserts; engine B is fresh on A's export.  24 queries (16 of the index's, 8 inserted vectors; k = 10,
+    L = 48) give the same results and counters on both -- and what the form's CPU reference answers on Index', for equality of two engines
+    that share a defect proves nothing.  Under the load-time variants the insert itself still equals the reference byte for byte."""
+    load_opts, alloc_opts, cases = FORMS[form]
+    for name in cases:
+        ix, v, L, alpha = I.case(name)
+        ix2, _ = I.reference(name)
+        q = I.form_queries(name)
+        with _engine(ix, ix.N + 128, **load_opts) as a:
+            assert a.insert(v, L, alpha) == ix.N
+            assert np.array_equal(a.entries(0, ix2.N), ix2.graph) and np.array_equal(a.codes(0, ix2.N), ix2.codes), (form, name)
+            exported = a.export_index(ix)
+            mine = _form_run(a, form, alloc_opts, name, ix2, q)
+        with _engine(exported, None, **load_opts) as b:
+            _same_dicts(_form_run(b, form, alloc_opts, name, ix2, q), mine, (form, name, "fresh engine"))
+        _same_dicts(mine, _form_reference(form, name, ix2, q), (form, name, "reference"), subset=True)
+        found = np.unique(np.concatenate([x["ids"] for x in (mine.values() if form == "range" else [mine])]))
+        assert ((found >= ix.N) & (found < ix2.N)).sum() >= 4, (form, name, "the answers hold fewer than 4 inserted ids")

@@ -121,3 +121,127 @@ def test_the_reference_applied_twice_sees_the_first_batch():
     new_rows = ix2.adjacency()[ix1.N:]
     base_n = I.get("i8")[0].N
     assert (new_rows >= base_n).any(), "no point of the second batch lists a point of the first: the second call must see the first"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the inputs of the seam, layout, tie and search-form tests reach the edges they are named for
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(I.SEAMS))
+def test_seam_cases_cross_their_seams_with_differing_data(name):
+    ix, v, L, alpha, ix2, st = I.seam_case(name)
+    sc, tc, ec = I.SEAMS[name]
+    n = len(v)
+    assert n > sc and n > ec, "no search / encode seam inside the batch"
+    targets, pruned = st["targets"], st["target_pruned"]
+    assert len(targets) > tc, "no target seam"
+    assert (np.diff(targets.astype(np.int64)) > 0).all() and pruned.sum() == st["pruned"] and (~pruned).sum() == st["appended"]
+    if tc == 1:                                                           # every target is a launch of its own: both paths, in launches behind the first
+        assert pruned[1:].any() and not pruned[1:].all()
+    else:
+        for side in (pruned[:tc], pruned[tc:]):                           # both paths on both sides of the first target seam
+            assert side.any() and not side.all(), name
+    # behind EVERY seam the data differ from the same slots of the first chunk: a launch that took the first chunk's vectors or rows again would
+    # show.  DUP_MIXED: chunks of copies of one vector cannot differ from each other; its chunks that hold distinct vectors are the ones asserted
+    rows = ix2.graph[ix.N:, ix.D * (4 if ix.dtype == "float" else 1):]
+    codes = ix2.codes[ix.N:]
+    n_dup = n - I.DUP_MIXED_TAIL if name == "DUP_MIXED" else 0
+    for what, table, chunk in (("rows", rows, sc), ("codes", codes, ec)):
+        checked = 0
+        for c0 in range(chunk, n, chunk):
+            c1 = min(c0 + chunk, n)
+            if c1 <= n_dup:
+                continue
+            assert any(not np.array_equal(table[x], table[x - c0]) for x in range(c0, c1)), (what, "chunk at", c0, "equals the first chunk")
+            checked += 1
+        assert checked >= 1 and (checked == (n - 1) // chunk or name == "DUP_MIXED"), (what, checked)
+    if name == "DUP_MIXED":
+        assert st["dropped"] > 0
+        last = codes[(n - 1) // ec * ec:]
+        assert len(np.unique(last, axis=0)) >= 2, "the last encode chunk holds one code row only"
+        q_last = (n - 1) // sc * sc
+        assert len(np.unique(rows[q_last:], axis=0)) >= 2 and len(np.unique(v[q_last:], axis=0)) >= 2
+
+
+@pytest.mark.parametrize("name", sorted(I.LAYOUTS))
+def test_layout_indexes_are_what_they_say(name):
+    from bang_amd.binding import NP_DTYPE
+    D, dtype, _ = I.LAYOUTS[name]
+    ix = I.layout(name)
+    assert (ix.N, ix.D, ix.R, ix.dtype) == (I.LAYOUT_N, D, I.LAYOUT_R, dtype)
+    v = ix.vectors()
+    assert v.dtype == NP_DTYPE[dtype] and len(np.unique(v, axis=0)) > ix.N // 2, "the vectors hardly differ: distances would not tell lanes apart"
+    assert (v[:, -1] != v[0, -1]).any() and (v[:, 0] != v[0, 0]).any(), "the first or the last dimension is constant"
+    assert (ix.degrees() == ix.R).sum() >= 2, "no two full rows: the back-edge test takes one to append to (cut short) and one that overflows"
+
+
+def _rows(ref, lists, owns, R, alpha, **kw):
+    return [tuple(IR.prune(ref, own, a, b, R, IR.alpha2_of(alpha), **kw)) for (a, b), own in zip(lists, owns)]
+
+
+@pytest.mark.parametrize("iname", ["i8", "u8"])
+def test_lattice_lists_pin_the_kill_rule_at_equality_and_at_float32_rounding(iname):
+    # alpha = 1 on {0, 1, 2}^6: '<=' and '<' part ways on at least a third of the lists, and a kill happens at alpha2 * e == d_t exactly
+    ix = I.lattice(iname, "tern6")
+    ref = Reference(ix)
+    assert len(np.unique(ix.vectors(), axis=0)) == I.LATTICE_N and ix.vectors()[:, 6:].max() == 0
+    lists, owns = I.lattice_lists(iname, "tern6")
+    assert sorted({len(a) for a, _ in lists}) == list(I.LATTICE_LENGTHS)
+    ties = []
+    le = [tuple(IR.prune(ref, own, a, b, ix.R, IR.alpha2_of(1.0), ties=ties)) for (a, b), own in zip(lists, owns)]
+    lt = _rows(ref, lists, owns, ix.R, 1.0, strict=True)
+    differ = sum(x != y for x, y in zip(le, lt))
+    assert 3 * differ >= len(lists), differ
+    assert sum(ties) >= 1
+    # alpha = 1.2: fl32(1.44f * e) decides at least one comparison that the unrounded product decides the other way.  1.44f * e meets an integer
+    # d_t that way at e = 25 (36), 50 (72), 100, 125 only -- {0, 1, 2}^6 ends at e = 24, so this is asserted on the lattice that reaches them
+    a2 = IR.alpha2_of(1.2)
+    assert np.float32(a2 * np.float32(25)) == 36 and float(a2) * 25 > 36 and np.float32(a2 * np.float32(50)) == 72 and float(a2) * 50 > 72
+    ix = I.lattice(iname, "plane7")
+    ref = Reference(ix)
+    assert len(np.unique(ix.vectors(), axis=0)) == I.LATTICE_N
+    lists, owns = I.lattice_lists(iname, "plane7")
+    f32 = _rows(ref, lists, owns, ix.R, 1.2)
+    f64 = _rows(ref, lists, owns, ix.R, 1.2, wide=True)
+    assert any(x != y for x, y in zip(f32, f64)), "no comparison is decided by the rounding of alpha2 * e"
+
+
+@pytest.mark.parametrize("name", sorted(I.PQ_LAYOUTS))
+def test_pq_layout_ties_are_row_minima(name):
+    ix, v = I.pq_layout(name)
+    assert (ix.m, ix.D) == I.PQ_LAYOUTS[name] and v.shape == (9, ix.D)
+    ref = Reference(ix)
+    luts = np.stack([ref.orc.lut_build(x) for x in v])                    # [9][m][256]
+    codes = np.stack([IR.encode(ref, x) for x in v])
+    for lo, hi in I.PQ_TIES:
+        assert lo < hi and np.array_equal(ix.pivots[lo], ix.pivots[hi])
+        both = (luts[:, :, lo] == luts.min(axis=2)) & (luts[:, :, hi] == luts.min(axis=2))
+        assert both.any(), (lo, hi, "the tie is nowhere the row minimum")
+        assert (codes[both] == lo).all() and not (codes == hi).any()
+    assert (I.PQ_TIES[0][1] - I.PQ_TIES[0][0]) == 64 and I.PQ_TIES[1][0] % 64 > I.PQ_TIES[1][1] % 64
+
+
+class _Recording(Reference):
+    """Reference that notes the nodes whose rows a walk reads."""
+    def __init__(self, ix):
+        super().__init__(ix)
+        self.expanded = set()
+
+    def adjacency(self, node):
+        self.expanded.add(int(node))
+        return super().adjacency(node)
+
+
+@pytest.mark.parametrize("name", sorted(I.FORM_CASES))
+def test_form_queries_find_inserted_points_through_changed_rows(name):
+    ix, v, _, _ = I.case(name)
+    ix2, st = I.reference(name)
+    q = I.form_queries(name)
+    assert q.shape[0] == 24
+    changed = {int(t) for t in st["targets"]}
+    for mode in ("exact", "pq"):
+        ref = _Recording(ix2)
+        ids, _, _ = ref.search(q, 10, 48, mode)
+        found = np.unique(ids[(ids >= ix.N) & (ids < ix2.N)])
+        assert len(found) >= 4, (mode, "the answers hold fewer than 4 inserted ids")
+        assert ref.expanded & changed, (mode, "the walk expands no old row that the insert changed")
+        assert any(x >= ix.N for x in ref.expanded) or mode == "pq"
