@@ -609,7 +609,7 @@ static inline int num_cus() {
 
 // Launch geometry of a wave-resident kernel (bang_wave_geometry) from the figures of instance k itself: its register count and its launch bound,
 // read once per device into the caller's cache (one WaveKernelAttr per instance; 128 registers / 16 waves where the runtime reports none)
-struct WaveKernelAttr { int regs[BANG_MAX_DEVICES], max_waves_wg[BANG_MAX_DEVICES]; };
+struct WaveKernelAttr { int regs[BANG_MAX_DEVICES], max_waves_wg[BANG_MAX_DEVICES]; bool lds_raised[BANG_MAX_DEVICES]; };
 static inline int wave_kernel_geometry(const void* k, WaveKernelAttr& c, uint32_t wave_bytes, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
                                        uint32_t* workgroups, uint32_t* waves) {
   const int dev = current_device();
@@ -620,6 +620,22 @@ static inline int wave_kernel_geometry(const void* k, WaveKernelAttr& c, uint32_
     c.regs[dev] = at.numRegs > 0 ? at.numRegs : 128;
   }
   return bang_wave_geometry((uint32_t)c.regs[dev], (uint32_t)c.max_waves_wg[dev], wave_bytes, (uint32_t)num_cus(), Q, max_wgs, max_waves, workgroups, waves);
+}
+
+// One launch of instance k in that geometry: workgroups of `waves` waves with wave_bytes of dynamic LDS each, the kernel's one argument a.  The
+// instance's dynamic-LDS limit is raised to a CU's LDS once per device (c: the instance's cache, as above).
+template <class Args>
+static inline int wave_kernel_launch(const void* k, WaveKernelAttr& c, uint32_t workgroups, uint32_t waves, uint32_t wave_bytes, void* stream,
+                                     const Args& a) {
+  const int dev = current_device();
+  if (!c.lds_raised[dev]) {
+    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BANG_WAVE_MAX_LDS));
+    c.lds_raised[dev] = true;
+  }
+  void* args[] = {(void*)&a};
+  (void)hipLaunchKernel(k, dim3(workgroups), dim3(waves * WAVE), args, (size_t)waves * wave_bytes, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());                                     // (a refused launch is reported here)
+  return BANG_OK;
 }
 
 // floats of the packed pivot table (multiple of 4: it is staged into LDS with 16-byte copies)

@@ -20,7 +20,9 @@
 // Narrow layouts only (those of bang_search_can_rerank: 8-bit D % 16 == 0 with D / 16 a power of two, float D % 4 == 0, D <= 256), float /
 // 8-bit rows (no fp16 table).  Built twice: bang_search_beam.o (search_exact_beam_kernel: graph entries in HBM) and, with
 // -DBANG_EXACT_PULL=1, bang_search_beam_pull.o (search_exact_beam_pull_kernel: row_layout 1, the packed vector table, every parent's row from
-// the slice table, the HBM row copy or pinned host memory, as bang_search_exact.hip selects it).
+// the slice table, the HBM row copy or pinned host memory: walk_fetch_pulled_row).  Around steps 1-5 the kernel calls the stages of
+// bang_wave_walk.h that bang_search_exact.hip calls (hand-out, LDS carve, query load, seed list, row fetches, counters, stamps); its
+// four-row filter -- branch-free probes, cross-row duplicates -- is its own.
 //
 // LDS per wave: the worklist (2L + L/4 words) + 144 words of sort scratch + two arrays of 64 W + 4 words (the kept survivors' ids and
 // distances, row after row).  No scratch memory, no flat_ instruction.
@@ -34,6 +36,7 @@
 #include "bang_device.h"
 #include "bang_worklist.h"
 #include "bang_exact_dist.h"
+#include "bang_wave_walk.h"
 
 #define BEAM_MAX 4                   // rows per iteration the kernel is compiled for
 #define BEAM_NO_MARK 0xFFFFFFFFu     // the merge marks nothing: parents are taken behind it
@@ -78,55 +81,33 @@ __global__ __launch_bounds__(1024) void BEAM_KERNEL(const BeamArgs a) {
   const uint64_t entry_len = p.entry_len;
   const uint32_t lim = n_nodes;                                   // 0: ids are not checked
 #endif
-  uint32_t* wbase = xlds + (size_t)wave * a.wave_words;
-  uint32_t* scratch = wbase + a.wl_words;
-  WaveLds s;
-  s.wd = (float*)wbase; s.wi = wbase + L; s.wv = (uint8_t*)(wbase + 2 * L);
-  s.sd = (float*)scratch; s.ti = scratch; s.td = (float*)(scratch + 72);
-  uint32_t* bid = scratch + WAVE_SCRATCH_WORDS;   // the kept survivors' ids, row after row, input order (16-byte aligned)
+  const WalkLds w = walk_lds(xlds + (size_t)wave * a.wave_words, L, a.wl_words);
+  const WaveLds& s = w.s;
+  uint32_t* bid = w.scratch + WAVE_SCRATCH_WORDS; // the kept survivors' ids, row after row, input order (16-byte aligned)
   float* bdist = (float*)(bid + a.row_words);     // ... and their distances
-  uint32_t* psel = scratch;                       // the parents picked by the selection (the sort scratch is dead there)
-  if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+  uint32_t* psel = w.scratch;                     // the parents picked by the selection (the sort scratch is dead there)
+  walk_stamp_start(p.d_ktime);
   const uint32_t total_waves = gridDim.x * nwaves;
   const uint32_t gw = blockIdx.x * nwaves + wave;
 
   for (bool first_q = true;; first_q = false) {
-    // ---------------- the next query: the first one by position, then from the hand-out counter
-    uint32_t q;
-    if (first_q) q = gw;
-    else {
-      uint32_t t = 0;
-      if (lane == 0) t = __hip_atomic_fetch_add(p.d_next_query, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      q = total_waves + uni(t);
-    }
+    const uint32_t q = walk_next_query(first_q, gw, total_waves, p.d_next_query, lane);
     if (q >= p.Q) break;
     const size_t qabs = (size_t)p.rr_q0 + q;
     uint32_t GAS* bloom = (uint32_t GAS*)p.d_bloom + (size_t)q * BANG_BF_WORDS;
 
     // the raw query, in registers
     const uint32_t D = p.rr_D;
-    u32x4a qw = {0u, 0u, 0u, 0u};
-    int qq = 0;
-    uint32_t G = 1;
-    float qr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (DT == BANG_F32) {
-      const float GAS* qsrc = (const float GAS*)p.rr_queries + qabs * D;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { const uint32_t j = (uint32_t)t * 64u + (uint32_t)lane; qr[t] = qsrc[j < D ? j : 0u]; }
-    } else {
-      G = D >> 4;
-      qw = *(const u32x4a GAS*)((const uint8_t GAS*)p.rr_queries + qabs * D + 16u * ((uint32_t)lane & (G - 1u)));
-      qq = xdot4<DT == BANG_I8>(qw.x, qw.x, xdot4<DT == BANG_I8>(qw.y, qw.y, xdot4<DT == BANG_I8>(qw.z, qw.z, xdot4<DT == BANG_I8>(qw.w, qw.w, 0))));
-    }
+    const NarrowQuery nq = walk_load_query_narrow<DT>(p.rr_queries, qabs, D, lane);
 
-    // ---------------- per-query state: candidate log = [MEDOID], one row: the seed list [MEDOID, adj(MEDOID)...]
+    // ---------------- per-query state: the walk's, with one row -- the seed list -- of up to BEAM_MAX
     uint32_t iter = 1, w_n = 0, cc = 1, evals = 0, fetched = 0, nrows = 1;
-    if (lane == 0) p.d_cand_ids[(size_t)q * cand_stride] = medoid;
+    const WalkSeed seed = walk_begin_query(p.d_cand_ids, p.d_seed, q, cand_stride, medoid, lane);
     uint32_t x[BEAM_MAX], cnt[BEAM_MAX];
 #pragma unroll
     for (int j = 0; j < BEAM_MAX; ++j) { x[j] = 0u; cnt[j] = 0u; }
-    cnt[0] = p.d_seed[0]; x[0] = p.d_seed[1 + lane];
-    uint32_t x1 = p.d_seed[65];
+    cnt[0] = seed.cnt; x[0] = seed.x0;
+    const uint32_t x1 = seed.x1;
 
     for (;;) {
       const bool first = (iter == 1);
@@ -217,8 +198,8 @@ __global__ __launch_bounds__(1024) void BEAM_KERNEL(const BeamArgs a) {
 
       // ---------------- step 3: exact distances (bang_exact_dist.h), one call over every kept survivor
       if (tot > 0u) {
-        if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, bid, tot, bdist, qr, lane);
-        else exact_dist8<DT == BANG_I8>(graph, entry_len, G, bid, tot, bdist, qw, qq, lane);
+        if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, bid, tot, bdist, nq.qr, lane);
+        else exact_dist8<DT == BANG_I8>(graph, entry_len, nq.G, bid, tot, bdist, nq.qw, nq.qq, lane);
       }
       wave_sync();
 
@@ -268,23 +249,11 @@ __global__ __launch_bounds__(1024) void BEAM_KERNEL(const BeamArgs a) {
         if ((uint32_t)j < got) {                                  // (uniform)
           const uint32_t parent = uni(psel[j]);
 #if BEAM_PULL
-          // all 64 lanes load one dword of the row.  Slice parent / slice_rows of the node's HBM-resident rows (this GPU's HBM or a peer's over
-          // xGMI; 0: that slice is not there), else the HBM copy of the first n_rows_hbm rows, else pinned host memory over PCIe
-          const uint32_t GAS* hb_rows = nullptr;
-          if (p.n_slices > 1u) {
-            const uint32_t sl = parent / p.slice_rows;            // (uniform: scalar)
-            if (sl < p.n_slices) hb_rows = (const uint32_t GAS*)slice_base(p.d_row_slices, sl);
-          } else if (parent < p.n_rows_hbm) hb_rows = (const uint32_t GAS*)p.d_rows_hbm;
-          if (hb_rows) x[j] = hb_rows[(uint64_t)parent * 64u + (uint32_t)lane];
-          else {
-            x[j] = __builtin_nontemporal_load((const uint32_t GAS*)p.d_graph + (uint64_t)parent * 64u + (uint32_t)lane);
-            asm volatile("; row from host memory");               // (keeps this load apart from the plain one: merged, the two lose the hint)
-          }
+          x[j] = walk_fetch_pulled_row(p.n_slices, p.slice_rows, p.d_row_slices, p.n_rows_hbm, p.d_rows_hbm, p.d_graph, parent, lane);
           cnt[j] = 64u;                                           // counted when the row is consumed
 #else
-          const uint32_t GAS* nrow = (const uint32_t GAS*)(graph + (uint64_t)parent * entry_len + p.vec_bytes);
-          cnt[j] = nrow[0];
-          x[j] = nrow[1 + ((uint32_t)lane < R ? (uint32_t)lane : 0u)];
+          const WalkEntryRow row = walk_fetch_entry_row(graph, entry_len, p.vec_bytes, R, parent, lane);
+          cnt[j] = row.cnt; x[j] = row.x;
 #endif
         }
       }
@@ -293,11 +262,9 @@ __global__ __launch_bounds__(1024) void BEAM_KERNEL(const BeamArgs a) {
     }
 
     // ---------------- the query is finished: counters, then the results straight from the worklist (CANON 11)
-    if (lane == 0) {
-      p.d_cand_cnt[q] = cc;
-      if (p.d_qstats) { p.d_qstats[(size_t)q * 2] = evals; p.d_qstats[(size_t)q * 2 + 1] = fetched; }
-      if (p.d_qiters) p.d_qiters[q] = iter;
-    }
+    walk_finish_query(p.d_cand_cnt, p.d_qstats, p.d_qiters, q, cc, evals, fetched, iter, lane);
+    // walk_write_results(s, w_n, ...), written out as in bang_search_exact.hip: inlined from the header the loop costs the u8 / i8 instances twice
+    // the SGPR spills (87 -> 178) and the small batches 2-3 % (profiles/wave_walk_device_code.md, profiles/wave_walk_bench.md)
     const uint32_t k = p.rr_k, Qt = p.rr_Q_total;
     uint64_t GAS* ids_out = (uint64_t GAS*)p.rr_ids_out;
     float GAS* dists_out = (float GAS*)p.rr_dists_out;
@@ -308,10 +275,7 @@ __global__ __launch_bounds__(1024) void BEAM_KERNEL(const BeamArgs a) {
     }
     wave_sync();                                                  // (the worklist is read before the next query overwrites it)
   }
-  if (p.d_ktime) {
-    __syncthreads();
-    if (threadIdx.x == 0) p.d_ktime[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-  }
+  walk_stamp_end(p.d_ktime);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -323,6 +287,7 @@ static const void* beam_instance(int dtype) {
   if (dtype == BANG_F32) return (const void*)BEAM_KERNEL<BANG_F32>;
   return nullptr;
 }
+static WaveKernelAttr beam_attr[3];                                // per instance: its figures, per device
 
 static uint32_t beam_wave_words(uint32_t L, uint32_t beam) { return wave_wl_words(L) + WAVE_SCRATCH_WORDS + 2u * beam_row_words(beam); }
 
@@ -332,8 +297,7 @@ extern "C" int BEAM_GEOMETRY(int dtype, uint32_t L, uint32_t beam, uint32_t Q, u
   if (beam == 0 || beam > BEAM_MAX) { bang_set_error("distance = 1: beam = %u is outside [1, %d]", beam, BEAM_MAX); return BANG_ERR_ARG; }
   const void* k = beam_instance(dtype);
   if (!k || L == 0 || L > BANG_MAX_L) { bang_set_error("distance = 1, beam = %u: bad dtype / L", beam); return BANG_ERR_ARG; }
-  static WaveKernelAttr attr[3];                                  // per instance
-  const int rc = wave_kernel_geometry(k, attr[dtype], beam_wave_words(L, beam) * 4u, Q, max_wgs, max_waves, workgroups, waves);
+  const int rc = wave_kernel_geometry(k, beam_attr[dtype], beam_wave_words(L, beam) * 4u, Q, max_wgs, max_waves, workgroups, waves);
   if (rc == BANG_ERR_UNSUPPORTED) bang_set_error("distance = 1, beam = %u: one wave's worklist does not fit LDS at L=%u", beam, L);
   return rc;
 }
@@ -349,21 +313,7 @@ static int beam_launch(const bang_search_params* p, uint32_t beam, void* stream)
   a.wl_words = wave_wl_words(p->L);
   a.row_words = beam_row_words(beam);
   a.wave_words = beam_wave_words(p->L, beam);
-  const size_t lds = (size_t)waves * a.wave_words * 4u;
-  const void* k = beam_instance((int)p->rr_dtype);
-  static bool attr_done[3][BANG_MAX_DEVICES] = {};
-  const int dev = current_device();
-  if (!attr_done[p->rr_dtype][dev]) {
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_MAX_LDS));
-    attr_done[p->rr_dtype][dev] = true;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(grid_n), block(waves * WAVE);
-  if (p->rr_dtype == BANG_F32) hipLaunchKernelGGL(BEAM_KERNEL<BANG_F32>, grid, block, lds, st, a);
-  else if (p->rr_dtype == BANG_I8) hipLaunchKernelGGL(BEAM_KERNEL<BANG_I8>, grid, block, lds, st, a);
-  else hipLaunchKernelGGL(BEAM_KERNEL<BANG_U8>, grid, block, lds, st, a);
-  HIP_TRY(hipGetLastError());
-  return BANG_OK;
+  return wave_kernel_launch(beam_instance((int)p->rr_dtype), beam_attr[p->rr_dtype], grid_n, waves, a.wave_words * 4u, stream, a);
 }
 
 #if BEAM_PULL

@@ -12,14 +12,11 @@
 //    fmaf chain gives (the arithmetic of wave_rerank8).  Float vectors: one lane per survivor runs the ascending fmaf chain over its
 //    vector, four 16-byte loads in flight (the arithmetic of wave_rerank_f32).  The query sits in registers in both cases.  Both routines
 //    live in bang_exact_dist.h, which the beam form (bang_search_beam.hip) includes too.
-//  * Filter (CANON 3): every id of the row is probed against the filter state at entry -- both words in one round trip, read past L1 --
-//    and only then are the survivors' bits set, with ATOMIC ORs into the query's private words.  The claim table of bang_search.hip
-//    (plain stores, same-word lanes merged in LDS) is an optimisation for a kernel whose iteration is bound by requests past L2; here an
-//    evaluation already costs 2-6 lines of vector, the atomics are one request per bit and need no LDS, and the next iteration's probes
-//    wait for them (s_waitcnt vmcnt(0) ahead of the probes, behind the adjacency row they need anyway).
+//  * The walk's stages that do not depend on the distance -- query hand-out, LDS carve, narrow query load, seed list, row length and the
+//    ids-in-range guard, the K5 filter (CANON 3), the K4 parent, the row fetches, counters, results, stamps -- are the functions of
+//    bang_wave_walk.h, shared with bang_search_lut.hip and bang_search_beam.hip; this file holds the distance stages and the blocks of its builds.
 //  * No pivot table: LDS holds 2L + L/4 + 144 words per wave and the launch is bound by VGPRs.  bang_search_exact_geometry reads the
 //    instance's register count and launch bound; the grid is bang_wave_geometry's (bang_wave_host.cpp).
-//  * An adjacency id >= n_nodes is never followed: the row counts as empty and *d_abort = 2 (the batch ends with an error).
 //  * ONE OBJECT PER FORM.  The Makefile builds this file once per form below, each under the flag named with it; the flags give the build its
 //    tag (EXACT_TAG), and kernel, geometry function and entry point are named after it (search_exact_wide_pull_kernel, ...), so that the
 //    instances of every other build stay the code they are.  The arguments are checked and routed to a build by bang_wave_host.cpp.
@@ -64,6 +61,7 @@
 #include "bang_device.h"
 #include "bang_worklist.h"
 #include "bang_exact_dist.h"
+#include "bang_wave_walk.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // this build: one tag from the flags; the kernel, the geometry function and the entry point are named after it
@@ -322,21 +320,17 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 #endif
   uint32_t* wbase = xlds + (size_t)wave * a.wave_words;
 #ifdef BANG_EXACT_LABELS
-  uint32_t* scratch = wbase + 2u * a.wl_words;                    // [worklist][result list][scratch]
+  const WalkLds w = walk_lds(wbase, L, 2u * a.wl_words);          // [worklist][result list][scratch]
 #else
-  uint32_t* scratch = wbase + a.wl_words;
+  const WalkLds w = walk_lds(wbase, L, a.wl_words);
 #endif
-  WaveLds s;
-  s.wd = (float*)wbase; s.wi = wbase + L; s.wv = (uint8_t*)(wbase + 2 * L);
-  s.sd = (float*)scratch; s.ti = scratch; s.td = (float*)(scratch + 72);
-  float* sdist = (float*)scratch;                 // the survivors' distances (dead before the sort writes sd)
-  uint32_t* sc = scratch + 72;                    // the survivors' ids, in input order (== td: dead before the sort)
+  const WaveLds& s = w.s;
+  float* sdist = w.sdist;
+  uint32_t* sc = w.sc;
 #ifdef BANG_EXACT_LABELS
   // the result list: a second sorted list of capacity L behind the worklist; it sorts and merges through the same scratch words, after the worklist's
   // merge is done (the survivors' ids and distances are in registers by then).  Its visited flags are written and never read.
-  WaveLds rl;
-  rl.wd = (float*)(wbase + a.wl_words); rl.wi = wbase + a.wl_words + L; rl.wv = (uint8_t*)(wbase + a.wl_words + 2 * L);
-  rl.sd = s.sd; rl.ti = s.ti; rl.td = s.td;
+  const WaveLds rl = walk_lds(wbase + a.wl_words, L, a.wl_words).s;
   const uint32_t GAS* labels = (const uint32_t GAS*)a.f.d_labels;
   const uint32_t GAS* excluded = (const uint32_t GAS*)a.f.d_excluded;    // or null
 #endif
@@ -344,28 +338,21 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
   const uint32_t GAS* excluded = (const uint32_t GAS*)a.r.d_excluded;    // or null
   const uint32_t hit_cap = a.r.cap;
 #endif
-  if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+  walk_stamp_start(p.d_ktime);
   const uint32_t total_waves = gridDim.x * nwaves;
   const uint32_t gw = blockIdx.x * nwaves + wave;
 
   for (bool first_q = true;; first_q = false) {
-    // ---------------- the next query: the first one by position, then from the hand-out counter
-    uint32_t q;
-    if (first_q) q = gw;
-    else {
-      uint32_t t = 0;
-      if (lane == 0) t = __hip_atomic_fetch_add(p.d_next_query, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      q = total_waves + uni(t);
-    }
+    const uint32_t q = walk_next_query(first_q, gw, total_waves, p.d_next_query, lane);
     if (q >= p.Q) break;
     const size_t qabs = (size_t)p.rr_q0 + q;
     uint32_t GAS* bloom = (uint32_t GAS*)p.d_bloom + (size_t)q * BANG_BF_WORDS;
 
     // the raw query, in registers
     const uint32_t D = p.rr_D;
+#ifdef BANG_EXACT_WIDE
     u32x4a qw = {0u, 0u, 0u, 0u};
     int qq = 0;
-#ifdef BANG_EXACT_WIDE
     float qr[EXACT_QREGS];
     if (DT == BANG_F32) {
       const float GAS* qsrc = (const float GAS*)p.rr_queries + qabs * D;
@@ -375,23 +362,12 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 #pragma unroll
       for (int t = 0; t < EXACT_QREGS; ++t) qr[t] = 0.0f;
       qw = *(const u32x4a GAS*)((const uint8_t GAS*)p.rr_queries + qabs * D + 16u * ((uint32_t)lane < (D >> 4) ? (uint32_t)lane : 0u));
-      qq = xdot4<DT == BANG_I8>(qw.x, qw.x, xdot4<DT == BANG_I8>(qw.y, qw.y, xdot4<DT == BANG_I8>(qw.z, qw.z, xdot4<DT == BANG_I8>(qw.w, qw.w, 0))));
+      qq = query_sumsq<DT == BANG_I8>(qw);
     }
 #else
-    uint32_t G = 1;
-    float qr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (DT == BANG_F32) {
-      const float GAS* qsrc = (const float GAS*)p.rr_queries + qabs * D;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { const uint32_t j = (uint32_t)t * 64u + (uint32_t)lane; qr[t] = qsrc[j < D ? j : 0u]; }
-    } else {
-      G = D >> 4;
-      qw = *(const u32x4a GAS*)((const uint8_t GAS*)p.rr_queries + qabs * D + 16u * ((uint32_t)lane & (G - 1u)));
-      qq = xdot4<DT == BANG_I8>(qw.x, qw.x, xdot4<DT == BANG_I8>(qw.y, qw.y, xdot4<DT == BANG_I8>(qw.z, qw.z, xdot4<DT == BANG_I8>(qw.w, qw.w, 0))));
-    }
+    const NarrowQuery nq = walk_load_query_narrow<DT>(p.rr_queries, qabs, D, lane);
 #endif
 
-    // ---------------- per-query state (bang_init :440-489): candidate log = [MEDOID], seed list [MEDOID, adj(MEDOID)...]
     uint32_t iter = 1, w_n = 0, cc = 1, mark = 0x01010101u, evals = 0, fetched = 0;
 #ifdef BANG_EXACT_LABELS
     const uint32_t f_any = uni(((const uint32_t GAS*)a.f.d_filters)[2u * qabs]), f_all = uni(((const uint32_t GAS*)a.f.d_filters)[2u * qabs + 1u]);
@@ -405,71 +381,23 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
     float GAS* hit_dists = (float GAS*)a.r.d_hit_dists + (uint64_t)qabs * hit_cap;
     uint32_t offered = 0;
 #endif
-    WlHead head;
-    head.found = false; head.idx = 0; head.id = 0; head.d = 0.0f; head.tail = 0.0f;
-    if (lane == 0) p.d_cand_ids[(size_t)q * cand_stride] = medoid;
-    uint32_t cnt_in = p.d_seed[0], x0 = p.d_seed[1 + lane], x1 = p.d_seed[65];
+    WlHead head = walk_empty_head();
+    const WalkSeed seed = walk_begin_query(p.d_cand_ids, p.d_seed, q, cand_stride, medoid, lane);
+    uint32_t cnt_in = seed.cnt, x0 = seed.x0;
+    const uint32_t x1 = seed.x1;
     bool have_row = true;
 
     for (;;) {
       const bool first = (iter == 1);
-      // ---------------- K5: filter (neighbor_filtering_new :1140-1165) ----------------
-      uint32_t ci = have_row ? uni(cnt_in) : 0u;
+      // ---------------- K5: filter
 #if EXACT_PULL
-      if (!first && have_row) ci = (uint32_t)__popcll(__ballot(x0 != BANG_ADJ_PAD));   // a 256-byte adjacency row: ids first, padding behind them
-#endif
-      {
-        const uint32_t cap = R + (first ? 1u : 0u);
-        if (ci > cap) ci = cap;
-      }
-#if EXACT_PULL
-      {
-        // (a pad value in front of an id -- a row overwritten since bang_load -- is an id out of range whether or not n_nodes was given)
-        const uint32_t lim = n_nodes != 0u ? n_nodes : BANG_ADJ_PAD;
-        if (__ballot((uint32_t)lane < ci && x0 >= lim) != 0ull || (ci > 64u && uni(x1) >= lim)) {
-          if (lane == 0 && p.d_abort) *p.d_abort = 2u;
-          ci = 0;
-        }
-      }
+      const uint32_t ci = walk_row_len_pulled(have_row, cnt_in, first, R, n_nodes, x0, x1, p.d_abort, lane);
 #else
-      if (n_nodes != 0u && (__ballot((uint32_t)lane < ci && x0 >= n_nodes) != 0ull || (ci > 64u && uni(x1) >= n_nodes))) {
-        if (lane == 0 && p.d_abort) *p.d_abort = 2u;
-        ci = 0;
-      }
+      const uint32_t ci = walk_row_len_entry(have_row, cnt_in, first, R, n_nodes, x0, x1, p.d_abort, lane);
 #endif
       fetched += ci;
-      const bool v0 = (uint32_t)lane < ci;
-      const bool v1 = ci > 64;                                    // the 65th id exists in the seed list only (uniform)
-      const uint32_t h0a = hash1(x0), h0b = hash2(x0);
-      uint32_t h1a = 0, h1b = 0, w0a = 0, w0b = 0, w1a = 0, w1b = 0;
-      // CANON 3: every id is tested against the filter state at entry; the previous iteration's atomic ORs have completed
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (v0) { w0a = ld_bypass_l1(&bloom[h0a >> 5]); w0b = ld_bypass_l1(&bloom[h0b >> 5]); }
-      if (v1) {
-        h1a = hash1(x1); h1b = hash2(x1);
-        if (lane == 0) { w1a = ld_bypass_l1(&bloom[h1a >> 5]); w1b = ld_bypass_l1(&bloom[h1b >> 5]); }
-      }
-      const bool pass0 = v0 && !(((w0a >> (h0a & 31)) & 1u) && ((w0b >> (h0b & 31)) & 1u));
-      const bool pass1 = v1 && (lane == 0) && !(((w1a >> (h1a & 31)) & 1u) && ((w1b >> (h1b & 31)) & 1u));
-      const uint64_t m0 = __ballot(pass0);
-      const uint64_t m1 = __ballot(pass1);
-      const uint32_t n0 = (uint32_t)__popcll(m0);
-      const uint32_t n = n0 + (uint32_t)__popcll(m1);
-      // ... then every survivor's two bits are set (:1159-1160)
-      if (pass0) {
-        (void)__hip_atomic_fetch_or(&bloom[h0a >> 5], 1u << (h0a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        (void)__hip_atomic_fetch_or(&bloom[h0b >> 5], 1u << (h0b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (pass1) {
-        (void)__hip_atomic_fetch_or(&bloom[h1a >> 5], 1u << (h1a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        (void)__hip_atomic_fetch_or(&bloom[h1b >> 5], 1u << (h1b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      // ordered compaction through LDS: survivors keep input order (CANON; the reference emits in atomicAdd order :1161)
-      if (pass0) sc[lanes_below(m0)] = x0;
-      if (pass1) sc[n0] = x1;
-      wave_sync();
-      const uint32_t sid0 = ((uint32_t)lane < n) ? sc[lane] : 0u;
-      const uint32_t sid1 = (lane == 0 && n > 64) ? sc[64] : 0u;
+      const WalkSurvivors sv = walk_filter(bloom, ci, x0, x1, sc, lane);
+      const uint32_t n = sv.n, sid0 = sv.sid0, sid1 = sv.sid1;
       evals += n;
 #ifdef BANG_EXACT_LABELS
       // the survivors' label words, and their words of the exclusion bitmap: requested here, so that they travel with the vectors (every survivor id
@@ -491,14 +419,14 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       // ---------------- exact distances (CANON 10: replaces K2) ----------------
       if (n > 0) {
 #ifdef BANG_EXACT_WIDE
-        exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, scratch + WAVE_SCRATCH_WORDS, qr, qw, qq, lane);
+        exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, w.scratch + WAVE_SCRATCH_WORDS, qr, qw, qq, lane);
 #else
 #ifdef BANG_EXACT_F16
-        if (DT == BANG_F32) exact_dist_f16(graph, entry_len, D, sc, n, sdist, qr, lane);
+        if (DT == BANG_F32) exact_dist_f16(graph, entry_len, D, sc, n, sdist, nq.qr, lane);
 #else
-        if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, sc, n, sdist, qr, lane);
+        if (DT == BANG_F32) exact_dist_f32(graph, entry_len, D, sc, n, sdist, nq.qr, lane);
 #endif
-        else exact_dist8<DT == BANG_I8>(graph, entry_len, G, sc, n, sdist, qw, qq, lane);
+        else exact_dist8<DT == BANG_I8>(graph, entry_len, nq.G, sc, n, sdist, nq.qw, nq.qq, lane);
 #endif
       }
       wave_sync();
@@ -520,68 +448,21 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       }
 #endif
 
-      // ---------------- K4: parent (compute_parent1 :1464-1521 / compute_parent2 :1384-1459), as bang_search.hip ----------------
+      // ---------------- K4: parent
       uint32_t parent = 0;
       bool found = false;
-      {
-        const bool elig = (uint32_t)lane < n && sid0 != medoid && d0 < BIG_DIST;
-        // (squared distances are non-negative: their bit patterns order like the floats; {bits, lane}: first minimum wins)
-        uint32_t khi = elig ? __float_as_uint(d0) : 0xFFFFFFFFu, klo = (uint32_t)lane;
-        wave_min_key(khi, klo);
-        uint32_t bi = (khi != 0xFFFFFFFFu) ? klo : 0xFFFFu;
-        float bd = (khi != 0xFFFFFFFFu) ? __uint_as_float(khi) : BIG_DIST;
-        uint32_t bid = (uint32_t)__builtin_amdgcn_readlane((int)sid0, (int)(klo & 63u));
-        if (n > 64) {                                             // element 64 can only win with a strictly smaller distance
-          const float e_d = __shfl(d1, 0);
-          const uint32_t e_id = (uint32_t)__shfl((int)sid1, 0);
-          if (e_id != medoid && e_d < BIG_DIST && (bi == 0xFFFFu || e_d < bd)) { bd = e_d; bi = 64; bid = e_id; }
-        }
-        const bool have_best = (bi != 0xFFFFu);
-        if (!have_best) bd = BIG_DIST;
-        bool from_best = false;
-        if (first) {
-          if (have_best) { found = true; parent = bid; from_best = true; }
-        } else {
-          if (head.found) {                                       // first unvisited entry :1425-1439
-            found = true;
-            if (bd < head.d) { parent = bid; from_best = true; }
-            else { parent = head.id; if (lane == 0) s.wv[head.idx] = 1; }
-          } else if (w_n > 0) {                                   // corner case :1442-1446
-            if (bd < head.tail) { found = true; parent = bid; from_best = true; }
-          }
-        }
-        parent = uni(parent);
-        if (found) {
-          if (from_best) mark = parent;
-          ++cc;
-        }
-      }
+      walk_parent(s, head, n, sid0, sid1, d0, d1, first, w_n, medoid, mark, cc, parent, found, lane);
 
       // ---------------- hand the parent over: its adjacency row is requested now and travels during the sort/merge
-      const bool want_row = found && iter < cap_iter;
+      if (found && iter < cap_iter) {
 #if EXACT_PULL
-      if (want_row) {
-        // all 64 lanes load one dword of the row.  Slice parent / slice_rows of the node's HBM-resident rows (this GPU's HBM or a peer's over
-        // xGMI; 0: that slice is not there), else the HBM copy of the first n_rows_hbm rows, else pinned host memory over PCIe
-        const uint32_t GAS* hb = nullptr;
-        if (p.n_slices > 1u) {
-          const uint32_t sl = parent / p.slice_rows;              // (uniform: scalar)
-          if (sl < p.n_slices) hb = (const uint32_t GAS*)slice_base(p.d_row_slices, sl);
-        } else if (parent < p.n_rows_hbm) hb = (const uint32_t GAS*)p.d_rows_hbm;
-        if (hb) x0 = hb[(uint64_t)parent * 64u + (uint32_t)lane];
-        else {
-          x0 = __builtin_nontemporal_load((const uint32_t GAS*)p.d_graph + (uint64_t)parent * 64u + (uint32_t)lane);
-          asm volatile("; row from host memory");                 // (keeps this load apart from the plain one: merged, the two lose the hint)
-        }
+        x0 = walk_fetch_pulled_row(p.n_slices, p.slice_rows, p.d_row_slices, p.n_rows_hbm, p.d_rows_hbm, p.d_graph, parent, lane);
         cnt_in = 64u;                                             // counted when the row is consumed
-      }
 #else
-      if (want_row) {
-        const uint32_t GAS* nrow = (const uint32_t GAS*)(graph + (uint64_t)parent * entry_len + p.vec_bytes);
-        cnt_in = nrow[0];
-        x0 = nrow[1 + ((uint32_t)lane < R ? (uint32_t)lane : 0u)];
-      }
+        const WalkEntryRow row = walk_fetch_entry_row(graph, entry_len, p.vec_bytes, R, parent, lane);
+        cnt_in = row.cnt; x0 = row.x;
 #endif
+      }
       if (found && lane == 0) p.d_cand_ids[(size_t)q * cand_stride + cc - 1u] = parent;      // :1451-1458
 
       // ---------------- K3a + K3b: sort the survivors, merge them into the worklist (not at the cap: CANON 6) ----------------
@@ -619,37 +500,29 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
     }
 
     // ---------------- the query is finished: counters, then the results straight from the worklist (CANON 11: replaces K6 + K7)
-    if (lane == 0) {
-      p.d_cand_cnt[q] = cc;
-      if (p.d_qstats) { p.d_qstats[(size_t)q * 2] = evals; p.d_qstats[(size_t)q * 2 + 1] = fetched; }
-      if (p.d_qiters) p.d_qiters[q] = iter;
-    }
-    const uint32_t k = p.rr_k, Qt = p.rr_Q_total;
-    uint64_t GAS* ids_out = (uint64_t GAS*)p.rr_ids_out;
-    float GAS* dists_out = (float GAS*)p.rr_dists_out;
+    walk_finish_query(p.d_cand_cnt, p.d_qstats, p.d_qiters, q, cc, evals, fetched, iter, lane);
 #ifdef BANG_EXACT_RANGE
     if (lane == 0) ((uint32_t GAS*)a.r.d_offered)[qabs] = offered;
 #endif
 #ifdef BANG_EXACT_LABELS
     if (lane == 0 && a.f.d_matched) ((uint32_t GAS*)a.f.d_matched)[qabs] = matched;
-    for (uint32_t r = (uint32_t)lane; r < k; r += WAVE) {         // CANON 18: the result list where the loop below reads the worklist
-      const bool have = r < r_n;
-      ids_out[qabs * k + r] = have ? (uint64_t)rl.wi[r] : ~0ull;
-      dists_out[(size_t)r * Qt + qabs] = have ? rl.wd[r] : BIG_DIST;
-    }
+    walk_write_results(rl, r_n, p.rr_ids_out, p.rr_dists_out, p.rr_k, p.rr_Q_total, qabs, lane);   // CANON 18: the result list, not the worklist
 #else
+    // walk_write_results(s, w_n, ...), written out: inlined from the header the loop's two conditional stores become one store of a phi, and that
+    // moves the narrow graph-entry and range instances from 97-98 VGPRs to 95-96 -- another allocation, another number of waves per CU
+    // (profiles/wave_walk_device_code.md)
+    const uint32_t k = p.rr_k, Qt = p.rr_Q_total;
+    uint64_t GAS* ids_out = (uint64_t GAS*)p.rr_ids_out;
+    float GAS* dists_out = (float GAS*)p.rr_dists_out;
     for (uint32_t r = (uint32_t)lane; r < k; r += WAVE) {
       const bool have = r < w_n;                                  // a short worklist is padded (CANON 8)
       ids_out[qabs * k + r] = have ? (uint64_t)s.wi[r] : ~0ull;                     // [Q][k] u64
       dists_out[(size_t)r * Qt + qabs] = have ? s.wd[r] : BIG_DIST;                 // [rank][Q]
     }
 #endif
-    wave_sync();                                                  // (the worklist is read before the next query overwrites it)
+    wave_sync();                                                  // (the list is read before the next query overwrites it)
   }
-  if (p.d_ktime) {
-    __syncthreads();
-    if (threadIdx.x == 0) p.d_ktime[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-  }
+  walk_stamp_end(p.d_ktime);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -663,6 +536,7 @@ static const void* exact_instance(int dtype) {
   if (dtype == BANG_F32) return (const void*)EXACT_KERNEL<BANG_F32>;
   return nullptr;
 }
+static WaveKernelAttr exact_attr[3];                               // per instance: its figures, per device
 
 // LDS words per wave: worklist + scratch (+ the row tile of the wide builds); the label-filter builds hold a second list, the result list --
 // 2 (2L + L/4) + 144 words, 16 waves per CU up to L = 512
@@ -684,8 +558,7 @@ extern "C" int EXACT_GEOMETRY(int dtype, uint32_t L, uint32_t Q, uint32_t max_wg
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   const void* k = exact_instance(dtype);
   if (!k || L == 0 || L > BANG_MAX_L) { bang_set_error("distance = 1: bad dtype / L"); return BANG_ERR_ARG; }
-  static WaveKernelAttr attr[3];                                  // per instance
-  const int rc = wave_kernel_geometry(k, attr[dtype], exact_wave_words(L) * 4u, Q, max_wgs, max_waves, workgroups, waves);
+  const int rc = wave_kernel_geometry(k, exact_attr[dtype], exact_wave_words(L) * 4u, Q, max_wgs, max_waves, workgroups, waves);
   if (rc == BANG_ERR_UNSUPPORTED) bang_set_error("distance = 1: one wave's worklist does not fit LDS at L=%u", L);
   return rc;
 }
@@ -711,23 +584,7 @@ static int exact_launch(const bang_search_params* p, void* stream) {
 #ifdef BANG_EXACT_RANGE
   a.r = *r;
 #endif
-  const size_t lds = (size_t)waves * a.wave_words * 4u;
-  const void* k = exact_instance((int)p->rr_dtype);
-  static bool attr_done[3][BANG_MAX_DEVICES] = {};
-  const int dev = current_device();
-  if (!attr_done[p->rr_dtype][dev]) {
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_MAX_LDS));
-    attr_done[p->rr_dtype][dev] = true;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(grid_n), block(waves * WAVE);
-  if (p->rr_dtype == BANG_F32) hipLaunchKernelGGL(EXACT_KERNEL<BANG_F32>, grid, block, lds, st, a);
-#ifndef BANG_EXACT_F16
-  else if (p->rr_dtype == BANG_I8) hipLaunchKernelGGL(EXACT_KERNEL<BANG_I8>, grid, block, lds, st, a);
-  else hipLaunchKernelGGL(EXACT_KERNEL<BANG_U8>, grid, block, lds, st, a);
-#endif
-  HIP_TRY(hipGetLastError());
-  return BANG_OK;
+  return wave_kernel_launch(exact_instance((int)p->rr_dtype), exact_attr[p->rr_dtype], grid_n, waves, a.wave_words * 4u, stream, a);
 }
 
 // This build's entry point (EXACT_ENTRY: bang_internal.h), called by bang_k_search_exact / bang_k_search_exact_labels (bang_wave_host.cpp) with

@@ -3,10 +3,9 @@
 // estimate gathered from the query's look-up table (K2, compute_neighborDist_par bang_search.cu:1201-1241) and the candidate log as its result
 // (the re-rank launch bang_k_rerank follows, as behind bang_k_search without the fused re-rank).
 //
-//  * Query-resident, self-paced: a wave owns one query from its first iteration to its last (worklist + survivors in LDS), then pulls the
-//    next unstarted query from *d_next_query.  Graph entries resident in HBM (d_graph, row_layout 0).  Filter, eager parent, merge, per-query
-//    activity, the L + 49 cap and the guard against adjacency ids >= n_nodes are those of search_exact_kernel, on the same device code
-//    (bang_worklist.h, bang_device.h).
+//  * Query-resident, self-paced, graph entries resident in HBM (d_graph, row_layout 0).  Everything but the distance stage is the walk of
+//    search_exact_kernel, called from the same functions: bang_wave_walk.h (hand-out, filter, eager parent, row fetch, the guard against
+//    adjacency ids >= n_nodes, counters) and bang_worklist.h (sort, merge, worklist head); per-query activity and the L + 49 cap as there.
 //  * Distances: one lane per survivor.  The lane walks its code row 16 chunks at a time -- a 16-byte window read from the row's 4-byte-aligned
 //    base with the non-temporal hint (a row is read once), the next window in flight meanwhile; rows that are not dword-aligned (m = 65, m = 5)
 //    are shifted into place with v_alignbyte -- and gathers the 16 table entries lut[c][code_c] together with ordinary cached loads (the query
@@ -28,6 +27,7 @@
 #include "bang_device.h"
 #include "bang_worklist.h"
 #include "bang_exact_dist.h"
+#include "bang_wave_walk.h"
 
 struct LutArgs {
   bang_search_params p;
@@ -104,83 +104,34 @@ __global__ __launch_bounds__(1024) void search_lut_kernel(const LutArgs a) {
   const uint8_t GAS* graph = (const uint8_t GAS*)p.d_graph;
   const uint8_t GAS* codes = (const uint8_t GAS*)p.d_codes;
   const uint64_t entry_len = p.entry_len;
-  uint32_t* wbase = llds + (size_t)wave * a.wave_words;
-  uint32_t* scratch = wbase + a.wl_words;
-  WaveLds s;
-  s.wd = (float*)wbase; s.wi = wbase + L; s.wv = (uint8_t*)(wbase + 2 * L);
-  s.sd = (float*)scratch; s.ti = scratch; s.td = (float*)(scratch + 72);
-  float* sdist = (float*)scratch;                 // the survivors' distances (dead before the sort writes sd)
-  uint32_t* sc = scratch + 72;                    // the survivors' ids, in input order (== td: dead before the sort)
-  if (p.d_ktime && threadIdx.x == 0) p.d_ktime[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+  const WalkLds w = walk_lds(llds + (size_t)wave * a.wave_words, L, a.wl_words);
+  const WaveLds& s = w.s;
+  float* sdist = w.sdist;
+  uint32_t* sc = w.sc;
+  walk_stamp_start(p.d_ktime);
   const uint32_t total_waves = gridDim.x * nwaves;
   const uint32_t gw = blockIdx.x * nwaves + wave;
 
   for (bool first_q = true;; first_q = false) {
-    // ---------------- the next query: the first one by position, then from the hand-out counter
-    uint32_t q;
-    if (first_q) q = gw;
-    else {
-      uint32_t t = 0;
-      if (lane == 0) t = __hip_atomic_fetch_add(p.d_next_query, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      q = total_waves + uni(t);
-    }
+    const uint32_t q = walk_next_query(first_q, gw, total_waves, p.d_next_query, lane);
     if (q >= p.Q) break;
     uint32_t GAS* bloom = (uint32_t GAS*)p.d_bloom + (size_t)q * BANG_BF_WORDS;
     const float GAS* lut = (const float GAS*)p.d_lut + (size_t)q * m * 256u;      // K1's table of this query :1236
 
-    // ---------------- per-query state (bang_init :440-489): candidate log = [MEDOID], seed list [MEDOID, adj(MEDOID)...]
     uint32_t iter = 1, w_n = 0, cc = 1, mark = 0x01010101u, evals = 0, fetched = 0;
-    WlHead head;
-    head.found = false; head.idx = 0; head.id = 0; head.d = 0.0f; head.tail = 0.0f;
-    if (lane == 0) p.d_cand_ids[(size_t)q * cand_stride] = medoid;
-    uint32_t cnt_in = p.d_seed[0], x0 = p.d_seed[1 + lane], x1 = p.d_seed[65];
+    WlHead head = walk_empty_head();
+    const WalkSeed seed = walk_begin_query(p.d_cand_ids, p.d_seed, q, cand_stride, medoid, lane);
+    uint32_t cnt_in = seed.cnt, x0 = seed.x0;
+    const uint32_t x1 = seed.x1;
     bool have_row = true;
 
     for (;;) {
       const bool first = (iter == 1);
-      // ---------------- K5: filter (neighbor_filtering_new :1140-1165) ----------------
-      uint32_t ci = have_row ? uni(cnt_in) : 0u;
-      {
-        const uint32_t cap = R + (first ? 1u : 0u);
-        if (ci > cap) ci = cap;
-      }
-      if (n_nodes != 0u && (__ballot((uint32_t)lane < ci && x0 >= n_nodes) != 0ull || (ci > 64u && uni(x1) >= n_nodes))) {
-        if (lane == 0 && p.d_abort) *p.d_abort = 2u;
-        ci = 0;
-      }
+      // ---------------- K5: filter
+      const uint32_t ci = walk_row_len_entry(have_row, cnt_in, first, R, n_nodes, x0, x1, p.d_abort, lane);
       fetched += ci;
-      const bool v0 = (uint32_t)lane < ci;
-      const bool v1 = ci > 64;                                    // the 65th id exists in the seed list only (uniform)
-      const uint32_t h0a = hash1(x0), h0b = hash2(x0);
-      uint32_t h1a = 0, h1b = 0, w0a = 0, w0b = 0, w1a = 0, w1b = 0;
-      // CANON 3: every id is tested against the filter state at entry; the previous iteration's atomic ORs have completed
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (v0) { w0a = ld_bypass_l1(&bloom[h0a >> 5]); w0b = ld_bypass_l1(&bloom[h0b >> 5]); }
-      if (v1) {
-        h1a = hash1(x1); h1b = hash2(x1);
-        if (lane == 0) { w1a = ld_bypass_l1(&bloom[h1a >> 5]); w1b = ld_bypass_l1(&bloom[h1b >> 5]); }
-      }
-      const bool pass0 = v0 && !(((w0a >> (h0a & 31)) & 1u) && ((w0b >> (h0b & 31)) & 1u));
-      const bool pass1 = v1 && (lane == 0) && !(((w1a >> (h1a & 31)) & 1u) && ((w1b >> (h1b & 31)) & 1u));
-      const uint64_t m0 = __ballot(pass0);
-      const uint64_t m1 = __ballot(pass1);
-      const uint32_t n0 = (uint32_t)__popcll(m0);
-      const uint32_t n = n0 + (uint32_t)__popcll(m1);
-      // ... then every survivor's two bits are set (:1159-1160)
-      if (pass0) {
-        (void)__hip_atomic_fetch_or(&bloom[h0a >> 5], 1u << (h0a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        (void)__hip_atomic_fetch_or(&bloom[h0b >> 5], 1u << (h0b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (pass1) {
-        (void)__hip_atomic_fetch_or(&bloom[h1a >> 5], 1u << (h1a & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        (void)__hip_atomic_fetch_or(&bloom[h1b >> 5], 1u << (h1b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      // ordered compaction through LDS: survivors keep input order (CANON; the reference emits in atomicAdd order :1161)
-      if (pass0) sc[lanes_below(m0)] = x0;
-      if (pass1) sc[n0] = x1;
-      wave_sync();
-      const uint32_t sid0 = ((uint32_t)lane < n) ? sc[lane] : 0u;
-      const uint32_t sid1 = (lane == 0 && n > 64) ? sc[64] : 0u;
+      const WalkSurvivors sv = walk_filter(bloom, ci, x0, x1, sc, lane);
+      const uint32_t n = sv.n, sid0 = sv.sid0, sid1 = sv.sid1;
       evals += n;
 
       // ---------------- K2: PQ distances from the query's table (compute_neighborDist_par :1201-1241) ----------------
@@ -190,49 +141,15 @@ __global__ __launch_bounds__(1024) void search_lut_kernel(const LutArgs a) {
       const float d1 = (lane == 0 && n > 64) ? sdist[64] : BIG_DIST;
       wave_sync();
 
-      // ---------------- K4: parent (compute_parent1 :1464-1521 / compute_parent2 :1384-1459), as bang_search.hip ----------------
+      // ---------------- K4: parent
       uint32_t parent = 0;
       bool found = false;
-      {
-        const bool elig = (uint32_t)lane < n && sid0 != medoid && d0 < BIG_DIST;
-        // (squared distances are non-negative: their bit patterns order like the floats; {bits, lane}: first minimum wins)
-        uint32_t khi = elig ? __float_as_uint(d0) : 0xFFFFFFFFu, klo = (uint32_t)lane;
-        wave_min_key(khi, klo);
-        uint32_t bi = (khi != 0xFFFFFFFFu) ? klo : 0xFFFFu;
-        float bd = (khi != 0xFFFFFFFFu) ? __uint_as_float(khi) : BIG_DIST;
-        uint32_t bid = (uint32_t)__builtin_amdgcn_readlane((int)sid0, (int)(klo & 63u));
-        if (n > 64) {                                             // element 64 can only win with a strictly smaller distance
-          const float e_d = __shfl(d1, 0);
-          const uint32_t e_id = (uint32_t)__shfl((int)sid1, 0);
-          if (e_id != medoid && e_d < BIG_DIST && (bi == 0xFFFFu || e_d < bd)) { bd = e_d; bi = 64; bid = e_id; }
-        }
-        const bool have_best = (bi != 0xFFFFu);
-        if (!have_best) bd = BIG_DIST;
-        bool from_best = false;
-        if (first) {
-          if (have_best) { found = true; parent = bid; from_best = true; }
-        } else {
-          if (head.found) {                                       // first unvisited entry :1425-1439
-            found = true;
-            if (bd < head.d) { parent = bid; from_best = true; }
-            else { parent = head.id; if (lane == 0) s.wv[head.idx] = 1; }
-          } else if (w_n > 0) {                                   // corner case :1442-1446
-            if (bd < head.tail) { found = true; parent = bid; from_best = true; }
-          }
-        }
-        parent = uni(parent);
-        if (found) {
-          if (from_best) mark = parent;
-          ++cc;
-        }
-      }
+      walk_parent(s, head, n, sid0, sid1, d0, d1, first, w_n, medoid, mark, cc, parent, found, lane);
 
       // ---------------- hand the parent over: its adjacency row is requested now and travels during the sort/merge
-      const bool want_row = found && iter < cap_iter;
-      if (want_row) {
-        const uint32_t GAS* nrow = (const uint32_t GAS*)(graph + (uint64_t)parent * entry_len + p.vec_bytes);
-        cnt_in = nrow[0];
-        x0 = nrow[1 + ((uint32_t)lane < R ? (uint32_t)lane : 0u)];
+      if (found && iter < cap_iter) {
+        const WalkEntryRow row = walk_fetch_entry_row(graph, entry_len, p.vec_bytes, R, parent, lane);
+        cnt_in = row.cnt; x0 = row.x;
       }
       if (found && lane == 0) p.d_cand_ids[(size_t)q * cand_stride + cc - 1u] = parent;      // :1451-1458
 
@@ -247,17 +164,10 @@ __global__ __launch_bounds__(1024) void search_lut_kernel(const LutArgs a) {
     }
 
     // ---------------- the query is finished: its candidate log feeds the re-rank launch (K6 + K7)
-    if (lane == 0) {
-      p.d_cand_cnt[q] = cc;
-      if (p.d_qstats) { p.d_qstats[(size_t)q * 2] = evals; p.d_qstats[(size_t)q * 2 + 1] = fetched; }
-      if (p.d_qiters) p.d_qiters[q] = iter;
-    }
+    walk_finish_query(p.d_cand_cnt, p.d_qstats, p.d_qiters, q, cc, evals, fetched, iter, lane);
     wave_sync();
   }
-  if (p.d_ktime) {
-    __syncthreads();
-    if (threadIdx.x == 0) p.d_ktime[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-  }
+  walk_stamp_end(p.d_ktime);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -269,12 +179,13 @@ extern "C" int bang_search_lut_supported(uint32_t m, uint32_t L) {
   return lut_wave_bytes(L) <= WAVE_MAX_LDS ? 1 : 0;
 }
 
+static WaveKernelAttr lut_attr;                                    // the instance's figures, per device
+
 // The grid of a launch (bang_wave_geometry on the instance's own figures), as bang_search_exact_geometry
 extern "C" int bang_search_lut_geometry(uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves) {
   if (!workgroups || !waves || Q == 0) return BANG_ERR_ARG;
   if (L == 0 || L > BANG_MAX_L) { bang_set_error("LUT search kernel: bad L"); return BANG_ERR_ARG; }
-  static WaveKernelAttr attr;
-  const int rc = wave_kernel_geometry((const void*)search_lut_kernel, attr, lut_wave_bytes(L), Q, max_wgs, max_waves, workgroups, waves);
+  const int rc = wave_kernel_geometry((const void*)search_lut_kernel, lut_attr, lut_wave_bytes(L), Q, max_wgs, max_waves, workgroups, waves);
   if (rc == BANG_ERR_UNSUPPORTED) bang_set_error("LUT search kernel: one wave's worklist does not fit LDS at L=%u", L);
   return rc;
 }
@@ -303,14 +214,5 @@ extern "C" int bang_k_search_lut(const bang_search_params* p, void* stream) {
   a.p = *p;
   a.wl_words = wave_wl_words(p->L);
   a.wave_words = a.wl_words + WAVE_SCRATCH_WORDS;
-  const size_t lds = (size_t)waves * a.wave_words * 4u;
-  static bool attr_done[BANG_MAX_DEVICES] = {};
-  const int dev = current_device();
-  if (!attr_done[dev]) {
-    HIP_TRY(hipFuncSetAttribute((const void*)search_lut_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WAVE_MAX_LDS));
-    attr_done[dev] = true;
-  }
-  hipLaunchKernelGGL(search_lut_kernel, dim3(grid_n), dim3(waves * WAVE), lds, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return BANG_OK;
+  return wave_kernel_launch((const void*)search_lut_kernel, lut_attr, grid_n, waves, a.wave_words * 4u, stream, a);
 }

@@ -3,6 +3,7 @@ public *_geometry functions read a kernel's register count and launch bound off 
 alone: known answers worked out by hand from the rule, then a sweep against a restatement of the rule."""
 import ctypes as C
 import itertools
+import os
 
 import pytest
 
@@ -95,6 +96,20 @@ def test_bad_arguments(libbang):
     assert f(98, 16, 1952, CUS, 100, 0, 0, C.byref(wg), None) == ERR_ARG
     for regs, bound, nbytes, cus in ((0, 16, 1952, CUS), (98, 0, 1952, CUS), (98, 16, 0, CUS), (98, 16, 1952, 0)):    # nothing to divide by
         assert f(regs, bound, nbytes, cus, 100, 0, 0, C.byref(wg), C.byref(w)) == ERR_ARG
+
+
+def test_the_walk_stages_are_written_once():
+    """The stages the exact, beam and LUT kernels share live in csrc/bang_wave_walk.h (the hand-out counter, the filter with its atomic ORs, the
+    parent rule) and the launch in wave_kernel_launch (bang_device.h): none of the three sources carries a copy of its own.  The beam's
+    four-row filter is a different algorithm and keeps its ORs."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bang-billion-scale-ann_amd", "csrc")
+    sources = ("bang_search_exact.hip", "bang_search_beam.hip", "bang_search_lut.hip")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sources + ("bang_wave_walk.h",)}
+    for f in sources:
+        for copy in ("__hip_atomic_fetch_add(p.d_next_query", "wave_min_key(", "hipFuncAttributeMaxDynamicSharedMemorySize"):
+            assert copy not in text[f], (f, copy)
+        assert '#include "bang_wave_walk.h"' in text[f], f
+    assert sorted(f for f in text if "__hip_atomic_fetch_or" in text[f]) == ["bang_search_beam.hip", "bang_wave_walk.h"]
 
 
 @pytest.mark.parametrize("regs", [64, 97, 104, 105, 128, 134, 256])
