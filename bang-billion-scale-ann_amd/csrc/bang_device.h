@@ -638,10 +638,4 @@ static inline int wave_kernel_launch(const void* k, WaveKernelAttr& c, uint32_t 
   return BANG_OK;
 }
 
-// floats of the packed pivot table (multiple of 4: it is staged into LDS with 16-byte copies)
-static inline uint32_t pivot_table_floats(uint32_t psz, uint32_t mp, uint32_t nhi) {
-  if (psz == 2 && nhi != 0) return ((nhi * 512u + (mp - nhi) * 256u + 3u) & ~3u) + 4u;
-  return mp * 256u * psz;
-}
-
 #endif

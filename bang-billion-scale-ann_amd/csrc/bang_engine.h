@@ -342,7 +342,7 @@ struct bang_engine {
   double insert_ms[6] = {0, 0, 0, 0, 0, 0};   // the last bang_insert_e: {search, prune, rows down + host grouping, back-edges, encode} on the stream / host, the whole call
 };
 
-// bang_search.hip, part 2 (semantics = 1): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride
+// bang_search_host.cpp (semantics = 1: parts 2 and 3 of bang_search.hip): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride
 extern "C" int bang_search_inmem_has_instance(uint32_t psz, uint32_t mp, uint32_t code_stride);
 
 namespace bang {

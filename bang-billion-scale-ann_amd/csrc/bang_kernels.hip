@@ -25,6 +25,7 @@
 #include "bang_internal.h"
 #include "bang_device.h"
 #include "bang_f16.h"
+#include "bang_search_args.h"
 
 // LUT path (PSZ == 0): LUT[m][256] gathered from global memory as the reference does (:1236); any m.
 __device__ __forceinline__ float pq_distance_lut(const uint8_t* __restrict__ codes, uint32_t m, uint32_t stride, uint32_t id,
@@ -1029,79 +1030,6 @@ __global__ __launch_bounds__(256) void rerank_f16_kernel(const RerankArgs a) {
 // ------------------------------------------------------------------------------------------
 // launchers (C-ABI)
 // ------------------------------------------------------------------------------------------
-// Supported (PSZ, NDW) instances of the LDS-resident distance kernel.  LDS need = NDW*4*256*PSZ*4 B.
-static const int kNdwList[4][4] = {{8, 16, 24, 32}, {8, 16, 18, 19}, {4, 8, 0, 0}, {2, 4, 0, 0}};
-static int psz_slot(int psz) { return psz == 1 ? 0 : psz == 2 ? 1 : psz == 4 ? 2 : psz == 8 ? 3 : -1; }
-
-extern "C" int bang_pq_layout(const uint32_t* chunk_off, uint32_t D, uint32_t m, uint32_t* psz_out, uint32_t* mp_out) {
-  if (!chunk_off || m == 0 || !psz_out || !mp_out) return BANG_ERR_ARG;
-  *psz_out = 0;
-  *mp_out = m;
-  uint32_t mx = 0;
-  for (uint32_t c = 0; c < m; ++c) {
-    if (chunk_off[c + 1] < chunk_off[c] || chunk_off[c + 1] > D) { bang_set_error("bad chunk offsets"); return BANG_ERR_ARG; }
-    const uint32_t sz = chunk_off[c + 1] - chunk_off[c];
-    if (sz > mx) mx = sz;
-  }
-  const int psz = mx <= 1 ? 1 : mx <= 2 ? 2 : mx <= 4 ? 4 : mx <= 8 ? 8 : 0;
-  if (psz == 0) return BANG_OK;                       // LUT path
-  const int need = (int)((m + 3) / 4);
-  const int slot = psz_slot(psz);
-  for (int i = 0; i < 4; ++i) {
-    const int ndw = kNdwList[slot][i];
-    if (ndw >= need && ndw > 0) {
-      *psz_out = (uint32_t)psz;
-      *mp_out = (uint32_t)ndw * 4;
-      return BANG_OK;
-    }
-  }
-  return BANG_OK;                                     // too many chunks for LDS: LUT path
-}
-
-extern "C" int bang_pack_pivots_ragged(const float* pivots, const uint32_t* chunk_off, uint32_t D, uint32_t m, uint32_t mp,
-                                       uint32_t* nhi_out, float* out, uint64_t* floats_out) {
-  if (!chunk_off || !nhi_out || m == 0 || mp < m) return BANG_ERR_ARG;
-  *nhi_out = 0;
-  if (floats_out) *floats_out = 0;
-  uint32_t nhi = 0;
-  while (nhi < m && chunk_off[nhi + 1] - chunk_off[nhi] == 2) ++nhi;
-  if (nhi == 0 || nhi == m) return BANG_OK;                          // no 2-dim prefix, or nothing to save
-  for (uint32_t c = nhi; c < m; ++c)
-    if (chunk_off[c + 1] - chunk_off[c] > 1) return BANG_OK;       // not of the form 2,..,2,1,..,1
-  const uint32_t total = pivot_table_floats(2, mp, nhi);
-  *nhi_out = nhi;
-  if (floats_out) *floats_out = total;
-  if (!out) return BANG_OK;
-  if (!pivots) return BANG_ERR_ARG;
-  for (uint32_t i = 0; i < total; ++i) out[i] = 0.0f;
-  for (uint32_t c = 0; c < m; ++c) {
-    const uint32_t sz = chunk_off[c + 1] - chunk_off[c];
-    const size_t base = c < nhi ? (size_t)c * 512 : (size_t)nhi * 256 + (size_t)c * 256;
-    for (uint32_t code = 0; code < 256; ++code)
-      for (uint32_t i = 0; i < sz; ++i) {
-        const uint32_t j = chunk_off[c] + i;
-        if (j < D) out[base + (size_t)code * (c < nhi ? 2 : 1) + i] = pivots[(size_t)code * D + j];
-      }
-  }
-  return BANG_OK;
-}
-
-extern "C" int bang_pack_pivots(const float* pivots, const uint32_t* chunk_off, uint32_t D, uint32_t m, uint32_t psz,
-                                uint32_t mp, float* out) {
-  if (!pivots || !chunk_off || !out || psz == 0 || mp < m) return BANG_ERR_ARG;
-  for (uint32_t c = 0; c < mp; ++c)
-    for (uint32_t code = 0; code < 256; ++code)
-      for (uint32_t i = 0; i < psz; ++i) {
-        float v = 0.0f;
-        if (c < m) {
-          const uint32_t j = chunk_off[c] + i;
-          if (j < chunk_off[c + 1]) v = pivots[(size_t)code * D + j];
-        }
-        out[((size_t)c * 256 + code) * psz + i] = v;
-      }
-  return BANG_OK;
-}
-
 template <typename F>
 static int dispatch_dtype(int dtype, F&& f) {
   switch (dtype) {
@@ -1159,9 +1087,8 @@ static int launch_front_inst(const FrontArgs& a, dim3 grid, dim3 block, size_t l
 template <int PSZ, int NDW>
 static int launch_front_al(const FrontArgs& a, bool aligned, int nqw, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
   if (a.p.pq_nhi) {
-    // exact-size pivot table: compiled for the two layouts of the BASELINE configs (128 dims in 70 chunks: 58 x 2 + 12 x 1;
-    // 96 dims in 74 chunks: 22 x 2 + 52 x 1), production (ALL) form only, rows of 70 / 74 bytes are never dword aligned
-    constexpr int NHI = (PSZ == 2 && NDW == 18) ? 58 : (PSZ == 2 && NDW == 19) ? 22 : 0;
+    // exact-size pivot table (bang_layout_nhi), production (ALL) form only, rows of 70 / 74 bytes are never dword aligned
+    constexpr int NHI = bang_layout_nhi(PSZ, NDW);
     if constexpr (NHI != 0) {
       if ((int)a.p.pq_nhi == NHI && !aligned && a.stages == 7u)
         return launch_front_inst<PSZ, NDW, false, true, 4, 512, NHI>(a, grid, block, lds, st);
@@ -1254,33 +1181,17 @@ static int launch_front(const bang_iter_params* p, uint32_t stages, void* stream
   const dim3 grid(grid_n), block(waves * WAVE);
   const bool al = ((p->code_stride ? p->code_stride : p->m) % 4u) == 0;
   hipStream_t st = (hipStream_t)stream;
-  const uint32_t key = p->psz * 100u + (p->psz ? p->mp / 4u : 0u);
-  switch (key) {
+  switch (bang_layout_key(p->psz, p->psz ? p->mp / 4u : 0u)) {
     case 0: return launch_front_al<0, 1>(a, true, nqw, grid, block, lds, st);
-    case 108: return launch_front_al<1, 8>(a, al, nqw, grid, block, lds, st);
-    case 116: return launch_front_al<1, 16>(a, al, nqw, grid, block, lds, st);
-    case 124: return launch_front_al<1, 24>(a, al, nqw, grid, block, lds, st);
-    case 132: return launch_front_al<1, 32>(a, al, nqw, grid, block, lds, st);
-    case 208: return launch_front_al<2, 8>(a, al, nqw, grid, block, lds, st);
-    case 216: return launch_front_al<2, 16>(a, al, nqw, grid, block, lds, st);
-    case 218: return launch_front_al<2, 18>(a, al, nqw, grid, block, lds, st);
-    case 219: return launch_front_al<2, 19>(a, al, nqw, grid, block, lds, st);
-    case 404: return launch_front_al<4, 4>(a, al, nqw, grid, block, lds, st);
-    case 408: return launch_front_al<4, 8>(a, al, nqw, grid, block, lds, st);
-    case 802: return launch_front_al<8, 2>(a, al, nqw, grid, block, lds, st);
-    case 804: return launch_front_al<8, 4>(a, al, nqw, grid, block, lds, st);
+#define FRONT_CASE(PSZ, NDW) case bang_layout_key(PSZ, NDW): return launch_front_al<PSZ, NDW>(a, al, nqw, grid, block, lds, st);
+    BANG_PQ_LAYOUTS(FRONT_CASE)
+#undef FRONT_CASE
     default: bang_set_error("no kernel instance for psz=%u mp=%u", p->psz, p->mp); return BANG_ERR_UNSUPPORTED;
   }
 }
 
 extern "C" int bang_k_front(const bang_iter_params* p, void* stream) { return launch_front(p, 7u, stream); }
 extern "C" int bang_num_cus(void) { return num_cus(); }
-
-// Is there a kernel instance for the exact-size pivot table of this layout (see launch_front_al)?
-extern "C" int bang_ragged_supported(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t m) {
-  return (psz == 2 && (m & 3u) != 0 && ((mp == 72 && nhi == 58) || (mp == 76 && nhi == 22))) ? 1 : 0;
-}
-
 extern "C" int bang_k_filter(const bang_iter_params* p, void* stream) { return launch_front(p, 1u, stream); }
 extern "C" int bang_k_pqdist(const bang_iter_params* p, void* stream) { return launch_front(p, 2u, stream); }
 extern "C" int bang_k_parent(const bang_iter_params* p, void* stream) { return launch_front(p, 4u, stream); }

@@ -12,6 +12,7 @@
 #include "bang_c.h"
 #include "bang_internal.h"
 #include "bang_device.h"
+#include "bang_search_args.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // K2 alone, streaming form (compute_neighborDist_par :1201-1241): dist[q][j] for the cnt[q] <= 64 neighbours of every query
@@ -139,7 +140,7 @@ template <int PSZ, int NDW>
 static int launch_pqdist_al(const bang_iter_params& p, uint32_t piv_floats, hipStream_t st) {
   const bool al = ((p.code_stride ? p.code_stride : p.m) % 4u) == 0;            // rows start dword-aligned
   if (p.pq_nhi) {
-    constexpr int NHI = (PSZ == 2 && NDW == 18) ? 58 : (PSZ == 2 && NDW == 19) ? 22 : 0;
+    constexpr int NHI = bang_layout_nhi(PSZ, NDW);
     if constexpr (NHI != 0) {
       if ((int)p.pq_nhi == NHI) return al ? launch_pqdist_inst<PSZ, NDW, true, NHI>(p, piv_floats, st) : launch_pqdist_inst<PSZ, NDW, false, NHI>(p, piv_floats, st);
     }
@@ -157,25 +158,10 @@ extern "C" int bang_k_pqdist_stream(const bang_iter_params* p, void* stream) {
   if (p->pq_nhi && (p->psz != 2 || p->pq_nhi > p->mp)) { bang_set_error("bad pq_nhi"); return BANG_ERR_ARG; }
   const uint32_t pf = pivot_table_floats(p->psz, p->mp, p->pq_nhi);
   hipStream_t st = (hipStream_t)stream;
-  switch (p->psz * 100u + p->mp / 4u) {
-#ifdef BANG_DEV_ONLY_218
-    case 218: return launch_pqdist_al<2, 18>(*p, pf, st);
-    default: bang_set_error("development build: psz=2 mp=72 only"); return BANG_ERR_UNSUPPORTED;
-  }
-  switch (0u) {
-#endif
-    case 108: return launch_pqdist_al<1, 8>(*p, pf, st);
-    case 116: return launch_pqdist_al<1, 16>(*p, pf, st);
-    case 124: return launch_pqdist_al<1, 24>(*p, pf, st);
-    case 132: return launch_pqdist_al<1, 32>(*p, pf, st);
-    case 208: return launch_pqdist_al<2, 8>(*p, pf, st);
-    case 216: return launch_pqdist_al<2, 16>(*p, pf, st);
-    case 218: return launch_pqdist_al<2, 18>(*p, pf, st);
-    case 219: return launch_pqdist_al<2, 19>(*p, pf, st);
-    case 404: return launch_pqdist_al<4, 4>(*p, pf, st);
-    case 408: return launch_pqdist_al<4, 8>(*p, pf, st);
-    case 802: return launch_pqdist_al<8, 2>(*p, pf, st);
-    case 804: return launch_pqdist_al<8, 4>(*p, pf, st);
+  switch (bang_layout_key(p->psz, p->mp / 4u)) {
+#define PQDIST_CASE(PSZ, NDW) case bang_layout_key(PSZ, NDW): return launch_pqdist_al<PSZ, NDW>(*p, pf, st);
+    BANG_SEARCH_LAYOUTS(PQDIST_CASE)         // (a BANG_DEV_ONLY_218 build: the SIFT1B layout only)
+#undef PQDIST_CASE
     default: bang_set_error("no K2 instance for psz=%u mp=%u", p->psz, p->mp); return BANG_ERR_UNSUPPORTED;
   }
 }

@@ -44,13 +44,13 @@
 #include <type_traits>
 #include <utility>
 #include <stdint.h>
-#include <stdlib.h>
 #include <algorithm>
 
 #include "bang_c.h"
 #include "bang_internal.h"
 #include "bang_device.h"
 #include "bang_worklist.h"
+#include "bang_search_args.h"
 
 // BANG_SEARCH_INMEM (Makefile: bang_search_inmem.o / bang_search_inmem_b.o, BANG_SEARCH_PART 2 / 3): the same kernel under another name
 // (search_inmem_kernel), self-paced instances only, with the parent rule and the iteration cap of the reference's BANG_Inmemory variant
@@ -73,7 +73,6 @@
 // the bits of id x in filter word hash1(x) >> 5 (one bit where the two positions coincide, about 1 id in 32)
 __device__ __forceinline__ uint32_t wf_mask(uint32_t ha, uint32_t hb) { return (1u << (ha & 31u)) | (1u << ((hb >> 5) & 31u)); }
 
-struct SearchArgs;
 // A kernel-argument field read WHERE IT IS USED (a scalar load from the kernarg segment through a pointer the optimiser cannot see through),
 // for arguments that are needed once per query (the seed list at its start, the counters and the re-rank at its end): read the ordinary way they are loop-invariant, get
 // hoisted out of the search loop and occupy scalar registers the loop has none to spare of (106 of 106: they spill into VGPR lanes).
@@ -97,56 +96,6 @@ __device__ __forceinline__ uint64_t scalar_load_u64(uint64_t tab, uint32_t idx) 
 #define KARG(field) karg_at<decltype(bang_search_params::field)>(offsetof(SearchArgs, p) + offsetof(bang_search_params, field))
 // ... a pointer field, as a pointer to global memory (bang_device.h GAS: a pointer read this way is generic to the compiler otherwise, its accesses flat_)
 #define KARGP(type, field) ((type GAS*)(uintptr_t)KARG(field))
-
-// What an ITERATION needs of the launch's arguments (as opposed to a query: KARG) -- where the code table, the filters, the candidate log and the next
-// adjacency row are -- travels in the LANES OF ONE VECTOR REGISTER of the wave (lane k = dword k of this block, loaded once at the wave's start) and is
-// read with v_readlane where it is used: no memory round trip.  History of these ~24 dwords: as ordinary kernel arguments they are loop-invariant, get
-// hoisted and take scalar registers the search loop has none to spare of (106 of 106: spills, or re-loads from the kernarg segment the compiler places
-// where it pleases: d_bloom, summ_iters and cap_iter were re-read on the chain of every iteration); read from the kernarg segment one by one where the
-// branches need them (round 5: KARG) the hand-over alone was five dependent scalar-cache round trips between "the parent is known" and "its row is
-// requested" (as one block: 1 250-query SIFT1B-shape shard 1.63 -> 1.53 ms, 10 K batch 8.32 -> 8.15).  The register passes through an empty asm in front
-// of each use site so that the reads stay THERE (a v_readlane of a loop-invariant register is loop-invariant too and would be hoisted back into scalar
-// registers).  Pointers rebuilt from these dwords are typed GAS (bang_device.h): generic, every access through them is a flat_ instruction.
-struct IterArgs {
-  const uint8_t* d_codes; uint32_t n_nodes, prio;                                               // dwords 0-1, 2, 3
-  uint32_t* d_cand_ids; const uint8_t* d_graph; uint64_t entry_len;                             // 4-5, 6-7, 8-9
-  uint32_t vec_bytes, row_layout, n_rows_hbm, n_slices;                                         // 10, 11, 12, 13
-  const uint32_t* d_rows_hbm; const uint64_t* d_row_slices;                                     // 14-15, 16-17
-  uint32_t slice_rows, summ_iters;                                                              // 18, 19
-  uint32_t* d_bloom; uint32_t cap_iter, pad1;                                                   // 20-21, 22, 23
-};
-enum { IA_CODES = 0, IA_N_NODES = 2, IA_PRIO = 3, IA_CAND_IDS = 4, IA_GRAPH = 6, IA_ENTRY_LEN = 8, IA_VEC_BYTES = 10, IA_ROW_LAYOUT = 11, IA_N_ROWS_HBM = 12,
-       IA_N_SLICES = 13, IA_ROWS_HBM = 14, IA_ROW_SLICES = 16, IA_SLICE_ROWS = 18, IA_SUMM_ITERS = 19, IA_BLOOM = 20, IA_CAP_ITER = 22, IA_DWORDS = 24 };
-static_assert(sizeof(IterArgs) == 4 * IA_DWORDS && offsetof(IterArgs, d_cand_ids) == 4 * IA_CAND_IDS && offsetof(IterArgs, vec_bytes) == 4 * IA_VEC_BYTES &&
-              offsetof(IterArgs, d_rows_hbm) == 4 * IA_ROWS_HBM && offsetof(IterArgs, slice_rows) == 4 * IA_SLICE_ROWS && offsetof(IterArgs, d_bloom) == 4 * IA_BLOOM && offsetof(IterArgs, cap_iter) == 4 * IA_CAP_ITER,
-              "IterArgs dword map");
-struct SearchArgs {
-  bang_search_params p;
-  IterArgs iter __attribute__((aligned(16)));
-  uint32_t lds_piv_floats;
-  uint32_t wave_words;       // LDS words per wave: nctx worklists + 144 scratch (+ 32 parked context state when nctx == 2)
-  uint32_t wl_words;         // LDS words of one worklist (2L + ceil(L/4), rounded to 4)
-  uint32_t nctx;             // query contexts per wave: 1, or 2 in the host-paced form
-  uint32_t gs;               // host-paced form: waves per pacing group (a workgroup's waves advance in lock-step per GROUP)
-};
-
-// Code rows are fetched cooperatively (CoopFetch, bang_device.h) from three 16-byte pieces per row on (rows of 12+ code dwords,
-// m > 44): two-piece rows (m = 32) gain nothing in the kernel (2.69 vs 2.70 ms on SIFT1M-like) and would only lose LDS to the staging
-// area.  The host-paced instances do so for the long-row layouts only (12 waves x 168 VGPRs, with the filter summary).
-__host__ __device__ constexpr bool search_coop(int ndw, bool host_paced) { return ndw >= 12 && (!host_paced || ndw >= 16); }
-// self-paced instances with the speculative row request (SPEC) exist for the long-row layouts of the BASELINE configs (70 / 74 chunks: 168-VGPR
-// instances); the 128-VGPR instance of the 32-chunk layout measured 2-5 % slower with it
-__host__ __device__ constexpr bool search_has_spec(int ndw) { return ndw == 18 || ndw == 19; }
-// per-wave scratch: sd/ti [72] + td/compaction [72]; the filter claim table (128 slots; 256 where the scratch has them) and the
-// summary's transposition area alias both, and so does the staging area of the cooperative code-row fetch (256 words: one wave
-// instruction's worth of 16-byte pieces)
-__host__ __device__ constexpr int search_maxt(int ndw, bool host_paced);
-__host__ __device__ constexpr uint32_t search_scratch_words(int ndw, bool host_paced);
-
-__host__ __device__ inline uint32_t search_wl_words(uint32_t L) { return (2u * L + (L + 3u) / 4u + 3u) & ~3u; }
-__host__ __device__ inline uint32_t search_wave_words(uint32_t L, uint32_t nctx, int ndw, bool host_paced) {
-  return nctx * search_wl_words(L) + search_scratch_words(ndw, host_paced) + (nctx == 2 ? 32u : 0u);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // K5, second half (:1159-1160): set the two filter bits of every survivor -- plain stores, same-word lanes merged in LDS
@@ -308,22 +257,6 @@ __device__ __forceinline__ void group_barrier(uint32_t* bar, uint32_t n, int lan
 #define SRCH_GO_STOP 0xFFFFFFFFu
 #define SRCH_FIN 0xFFFFFFFFu        // h_done value: this context group of the workgroup has no queries left
 #define SRCH_CTX_WORDS 16u          // parked per-context state of a wave, in LDS
-
-// MAXT: threads per workgroup the instance is compiled for -- 1024 (16 waves, 128 VGPRs each) or, for the instances of the long code
-// rows (>= 64 chunks), 768 (12 waves, 168 VGPRs each).  Build switch BANG_LONG_MAXT=1024: the self-paced long-row instances as 16-wave
-// instances -- 120-127 VGPRs without scratch (LANE_FRESH below), 144 words of scratch per wave (the cooperative fetch hands its pieces over in
-// rounds, 128-slot claim table), 16 x (2L + L/4 + 144) words beside the 128 KB pivot table up to L = 161.  Measured (round 6, docs/HISTORY.md):
-// 16 waves run the 10 K SIFT1B-shape batch no faster than the 12 of the 168-VGPR build (8.31 vs 8.30 ms: the launch sits on the rate of requests
-// past L2, not on waves in flight) and the 128-VGPR code loses 3-9 % where fewer waves are resident: 768 stays the default.
-#ifndef BANG_LONG_MAXT
-#define BANG_LONG_MAXT 768
-#endif
-
-__host__ __device__ constexpr int search_maxt(int ndw, bool host_paced) { return (search_coop(ndw, host_paced) && ndw >= 16) ? (host_paced ? 768 : BANG_LONG_MAXT) : 1024; }
-// 256 words where 12 waves share the LDS beside the pivot table; the 16-wave instances hand the pieces of the cooperative fetch over in rounds (144)
-__host__ __device__ constexpr uint32_t search_scratch_words(int ndw, bool host_paced) {
-  return search_coop(ndw, host_paced) ? ((ndw >= 16 && search_maxt(ndw, host_paced) >= 1024) ? 144u : 256u) : 144u;
-}
 
 #if BANG_SEARCH_INMEM
 #define search_kernel search_inmem_kernel          // (its own symbols: the instances of parts 0 and 1 keep their names)
@@ -585,7 +518,7 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
       // a row that names a node the index does not have (rows overwritten behind the engine's back: the self-paced form has no host
       // thread that could notice) is not followed: the batch ends with BANG_ERR_HIP instead of a wild read of the code table
       IA_FRESH();
-      // Wave priority (launch policy `prio`, bang_k_search): the two stretches of an iteration that END in memory requests -- hashes -> probes -> code-row
+      // Wave priority (launch policy `prio`, search_setup in bang_search_host.cpp): the two stretches of an iteration that END in memory requests -- hashes -> probes -> code-row
       // requests here, parent selection -> row request below -- run at raised priority, the reduce and the merge at the default: a wave that is about to
       // put requests in flight is not held up by its neighbours' arithmetic.  Pays where wave slots are free (2 500-query shard 2.24 -> 2.20 ms, 1 250:
       // 1.46 -> 1.44), costs a full chip 2 % (10 K batch 7.92 -> 8.12): on for launches of at most 10 queries per CU.
@@ -608,7 +541,7 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
       // CANON: every id is tested against the filter state at entry (all loads before any store); both words in one round trip.
       // A word the summary knows to be untouched is zero: no request (FilterSummary).
       bool la = v0, lb = v0;                                 // load word a / b?
-      const bool summ_on = SUMM && (HOST || iter <= IA32(IA_SUMM_ITERS));     // (uniform; one-way per query: once off, the registers go stale.  bang_k_search resolves 0 = auto)
+      const bool summ_on = SUMM && (HOST || iter <= IA32(IA_SUMM_ITERS));     // (uniform; one-way per query: once off, the registers go stale.  search_setup resolves 0 = auto)
 #if BANG_SEARCH_WORDFILTER
       // word-local layout: ONE word per id (that of hash1), its one or two bits in bm0 / bm1; the b side of everything below is gone
       const uint32_t bm0 = wf_mask(h0a, h0b);
@@ -1045,33 +978,28 @@ static int launch_inst(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, h
   return BANG_OK;
 }
 
-// The instances live in TWO translation units of this one file (Makefile): part 0 (BANG_SEARCH_PART = 0: bang_search.o, built with
-// -mllvm -amdgpu-sched-strategy=iterative-ilp -- round 6: every BASELINE layout 1-5 % faster under it, a 1 250-query SIFT1B-shape shard 1.52 -> 1.45 ms) and part 1
-// (bang_search_b.o, the default scheduler): the instances the ILP strategy costs scratch -- rows of 96+ chunks, 74-chunk rows that are not dword-aligned
-// (0 -> 72-116 B per lane), and the host-paced instances of the long-row layouts (20-68 -> 116-168 B).  Both units compile the same dispatch; each instantiates only its own instances.
+// This translation unit's share of the instances (bang_search_args.h: search_in_part1 and the parts of a variant).  BANG_SEARCH_PART is even in the
+// first part of a variant, which the host calls (bang_search_host.cpp) and which hands what it does not hold to the part after it.
 #ifndef BANG_SEARCH_PART
 #define BANG_SEARCH_PART 0
 #endif
-constexpr bool search_in_part1(int ndw, bool aligned, bool host_paced) { return ndw >= 24 || (ndw == 19 && !aligned) || (host_paced && ndw >= 16); }
-#if BANG_SEARCH_INMEM
-// semantics = 1: parts 2 (bang_search_inmem.o, iterative-ILP) and 3 (bang_search_inmem_b.o, the default scheduler) split the instances the way
-// parts 0 and 1 do
-#define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 3)
-#define bang_search_launch_part1 bang_search_inmem_launch_part3
-#elif BANG_SEARCH_WORDFILTER
-// filter_layout = 1: parts 4 (bang_search_wf.o, iterative-ILP) and 5 (bang_search_wf_b.o, the default scheduler), split the same way
-#define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 5)
-#define bang_search_launch_part1 bang_search_wf_launch_part5
-#else
-#define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART == 1)
+#if BANG_SEARCH_PART / 2 != BANG_SEARCH_INMEM + 2 * BANG_SEARCH_WORDFILTER
+#error "parts 0 / 1 are the BANG_Base walk, 2 / 3 BANG_SEARCH_INMEM, 4 / 5 BANG_SEARCH_WORDFILTER (Makefile)"
 #endif
-extern "C" int bang_search_launch_part1(const SearchArgs* a, uint32_t grid, uint32_t block, size_t lds, void* stream);
+#define BANG_SEARCH_SECOND_PART (BANG_SEARCH_PART % 2)
+#define SRCH_CAT_(a, b) a##b
+#define SRCH_CAT(a, b) SRCH_CAT_(a, b)
+#define SRCH_NEXT_0 1
+#define SRCH_NEXT_2 3
+#define SRCH_NEXT_4 5
+#define SRCH_THIS_PART SRCH_CAT(bang_search_launch_part, BANG_SEARCH_PART)
+#define SRCH_NEXT_PART SRCH_CAT(bang_search_launch_part, SRCH_CAT(SRCH_NEXT_, BANG_SEARCH_PART))
 
 template <int PSZ, int NDW, bool ALIGNED, int NHI, bool HOST, bool SPEC>
 static int launch_part(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
   if constexpr (search_in_part1(NDW, ALIGNED, HOST) == BANG_SEARCH_SECOND_PART) return launch_inst<PSZ, NDW, ALIGNED, NHI, HOST, SPEC>(a, grid, block, lds, st);
 #if !BANG_SEARCH_SECOND_PART
-  return bang_search_launch_part1(&a, grid.x, block.x, lds, (void*)st);
+  return SRCH_NEXT_PART(&a, grid.x, block.x, lds, (void*)st);
 #else
   bang_set_error("search-kernel instance psz=%u mp=%u is not part of this translation unit", a.p.psz, a.p.mp);
   return BANG_ERR_UNSUPPORTED;
@@ -1100,9 +1028,8 @@ template <int PSZ, int NDW>
 static int launch_al(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
   const bool al = ((a.p.code_stride ? a.p.code_stride : a.p.m) % 4u) == 0;          // rows start dword-aligned
   if (a.p.pq_nhi) {
-    // exact-size pivot table: compiled for the two layouts of the BASELINE configs (128 dims in 70 chunks: 58 x 2 + 12 x 1;
-    // 96 dims in 74 chunks: 22 x 2 + 52 x 1), rows packed (m = 70 / 74 bytes apart) or padded to a dword-aligned stride
-    constexpr int NHI = (PSZ == 2 && NDW == 18) ? 58 : (PSZ == 2 && NDW == 19) ? 22 : 0;
+    // exact-size pivot table (bang_layout_nhi), rows packed (m = 70 / 74 bytes apart) or padded to a dword-aligned stride
+    constexpr int NHI = bang_layout_nhi(PSZ, NDW);
     if constexpr (NHI != 0) {
       if ((int)a.p.pq_nhi == NHI) return al ? launch_hd<PSZ, NDW, true, NHI>(a, grid, block, lds, st) : launch_hd<PSZ, NDW, false, NHI>(a, grid, block, lds, st);
     }
@@ -1120,229 +1047,14 @@ static int launch_al(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hip
 
 static int search_dispatch(const SearchArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
   const bang_search_params* p = &a.p;
-  const uint32_t key = p->psz * 100u + p->mp / 4u;
-  switch (key) {
-#ifndef BANG_DEV_ONLY_218          // development builds (ISA dumps, quick A/B libraries): the SIFT1B layout only
-    case 108: return launch_al<1, 8>(a, grid, block, lds, st);
-    case 116: return launch_al<1, 16>(a, grid, block, lds, st);
-    case 124: return launch_al<1, 24>(a, grid, block, lds, st);
-    case 132: return launch_al<1, 32>(a, grid, block, lds, st);
-    case 208: return launch_al<2, 8>(a, grid, block, lds, st);
-    case 216: return launch_al<2, 16>(a, grid, block, lds, st);
-    case 219: return launch_al<2, 19>(a, grid, block, lds, st);
-#endif
-    case 218: return launch_al<2, 18>(a, grid, block, lds, st);
-#ifndef BANG_DEV_ONLY_218
-    case 404: return launch_al<4, 4>(a, grid, block, lds, st);
-    case 408: return launch_al<4, 8>(a, grid, block, lds, st);
-    case 802: return launch_al<8, 2>(a, grid, block, lds, st);
-    case 804: return launch_al<8, 4>(a, grid, block, lds, st);
-#endif
+  switch (bang_layout_key(p->psz, p->mp / 4u)) {
+#define SRCH_CASE(PSZ, NDW) case bang_layout_key(PSZ, NDW): return launch_al<PSZ, NDW>(a, grid, block, lds, st);
+    BANG_SEARCH_LAYOUTS(SRCH_CASE)
+#undef SRCH_CASE
     default: bang_set_error("no search-kernel instance for psz=%u mp=%u", p->psz, p->mp); return BANG_ERR_UNSUPPORTED;
   }
 }
 
-#if BANG_SEARCH_SECOND_PART
-extern "C" int bang_search_launch_part1(const SearchArgs* a, uint32_t grid, uint32_t block, size_t lds, void* stream) {
+extern "C" int SRCH_THIS_PART(const SearchArgs* a, uint32_t grid, uint32_t block, size_t lds, void* stream) {
   return search_dispatch(*a, dim3(grid), dim3(block), lds, (hipStream_t)stream);
 }
-#else
-
-#define SRCH_WG_SHARED_BYTES 2048u     // group-shared LDS behind the waves' regions (host-paced form): 128 words per pacing group, up to 4 groups
-#define SRCH_DEFAULT_GROUP_WAVES 8u
-
-// Argument checks, IterArgs, grid and launch policies of a search-kernel launch -- ONE copy for bang_k_search (parts 0 / 1) and
-// bang_k_search_inmem (parts 2 / 3, inmem: semantics = 1 -- self-paced only, cap up to L + 119, no speculative row request)
-static int search_setup(const bang_search_params* p, bool inmem, SearchArgs* out, dim3* grid, dim3* block, size_t* lds) {
-  if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L || p->m == 0) { bang_set_error("bad R/L/m"); return BANG_ERR_ARG; }
-  if (p->psz == 0 || p->mp < p->m || (p->mp & 3u)) { bang_set_error("the search kernel needs the LDS-resident pivot layout"); return BANG_ERR_UNSUPPORTED; }
-  if (!p->d_codes || !p->d_pivots_packed || !p->d_qc || !p->d_seed || !p->d_bloom || !p->d_cand_ids || !p->d_cand_cnt ||
-      !p->d_next_query) { bang_set_error("null buffer"); return BANG_ERR_ARG; }
-  if (!p->d_graph && (!p->d_rows || !p->d_ctl || !p->h_done || !p->h_parents || (p->ship_vectors && (!p->h_pub_q || !p->h_pub_c)))) {
-    bang_set_error("host-paced search kernel: null pacing buffer"); return BANG_ERR_ARG;
-  }
-  if (inmem && (!p->d_graph || p->row_layout != 0u)) { bang_set_error("semantics = 1: the graph entries must be in HBM (d_graph, row_layout 0)"); return BANG_ERR_UNSUPPORTED; }
-  if (p->pq_nhi && (p->psz != 2 || p->pq_nhi > p->mp)) { bang_set_error("bad pq_nhi"); return BANG_ERR_ARG; }
-  if (p->cap_iter == 0 || p->cap_iter > p->L + (inmem ? BANG_INMEM_EXTRA_ITERS : BANG_EXTRA_ITERS) - 1) { bang_set_error("bad iteration cap"); return BANG_ERR_ARG; }
-  if (p->rr_queries) {
-    if (!p->d_graph) { bang_set_error("the fused re-rank belongs to the self-paced form"); return BANG_ERR_ARG; }
-    if (!p->rr_vec_base || !p->rr_ids_out || !p->rr_dists_out || p->rr_k == 0 || p->rr_Q_total < p->rr_q0 + p->Q ||
-        !bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0) || (((uintptr_t)p->rr_vec_base) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
-      bang_set_error("fused re-rank: bad arguments / unsupported vector layout"); return BANG_ERR_ARG;
-    }
-  }
-  SearchArgs& a = *out;
-  a.p = *p;
-  a.lds_piv_floats = pivot_table_floats(p->psz, p->mp, p->pq_nhi);
-  __builtin_memset(&a.iter, 0, sizeof(a.iter));
-  a.iter.d_codes = p->d_codes; a.iter.n_nodes = p->n_nodes; a.iter.d_cand_ids = p->d_cand_ids; a.iter.d_graph = p->d_graph; a.iter.entry_len = p->entry_len;
-  a.iter.vec_bytes = p->vec_bytes; a.iter.row_layout = p->row_layout; a.iter.n_rows_hbm = p->n_rows_hbm; a.iter.n_slices = p->n_slices;
-  a.iter.d_rows_hbm = p->d_rows_hbm; a.iter.d_row_slices = p->d_row_slices; a.iter.slice_rows = p->slice_rows;
-  a.iter.d_bloom = p->d_bloom; a.iter.cap_iter = p->cap_iter;      // (summ_iters: below, once the policy is resolved)
-  uint32_t grid_n = 0, waves = 0, nctx = p->nctx, gs = p->group_waves;
-  const int rc = bang_search_geometry(p->psz, p->mp, p->pq_nhi, p->L, p->Q, p->max_wgs, p->max_waves, p->d_graph ? 0 : 1, &grid_n, &waves, &nctx, &gs);
-  if (rc != BANG_OK) return rc;
-  a.nctx = nctx;
-  a.gs = gs;
-  // The filter summary trades LDS-crossbar work on the chain of every iteration (12 ds_bpermute + two transposition passes) for
-  // memory requests.  A full chip is short of requests-in-flight: with it the 10 K SIFT1B-shape batch takes 8.36 instead of 9.09 ms, 5 000 /
-  // 2 500 queries 4.68 / 2.37 instead of 4.99 / 2.71.  A lightly loaded one is short of nothing but the chain: 1 250 queries (5 waves per CU)
-  // 1.70 ms without it against 1.77, 625 queries 1.43 against 1.53 (profiles/r04_summary_cutoff.md).  auto then: off up to 6 queries per CU.
-  // (with spec_rows on, re-measured: 1 250 queries 1.69 with / 1.63 without, 1 400: 1.73 / 1.72, 1 536 = 6 per CU: 1.74-1.78 / 1.73-1.74, 1 900: 1.94 / 1.99)
-  // (round 6, final kernel: 1 536 queries = 6 per CU 1.555 with / 1.585 without, 1 250 = 5 per CU 1.493 / 1.453: the cut-off is 5)
-  const bool light = (p->Q + grid_n - 1) / grid_n <= 5u;
-  if (a.p.summ_iters == 0u) a.p.summ_iters = light ? 1u : 0xFFFFFFFFu;
-  a.iter.summ_iters = a.p.summ_iters;
-  // wave priority around the request-issuing stretches of an iteration: on where wave slots are free (<= 10 queries per CU); BANG_SEARCH_PRIO = 0 / 1 forces it
-  { const char* e = getenv("BANG_SEARCH_PRIO"); a.iter.prio = (e && e[0] >= '0' && e[0] <= '3') ? (e[0] == '1' ? 3u : e[0] == '3' ? 1u : (uint32_t)(e[0] - '0')) : (((p->Q + grid_n - 1) / grid_n <= 10u) ? 3u : 0u); }   // (1 = both stretches, 2 = the hand-over's only, 3 = the top's only)
-  // spec_rows: one memory latency less on the chain of every iteration, the rows of the ids the filter drops fetched in vain.  Without / with,
-  // ms per batch (profiles/r05_spec_rows.md) -- rows pulled, N = 1e9 random graph: 10 000 queries 8.75 / 8.38, 5 000 4.72 / 4.61, 2 500 2.33 / 2.29, 1 250 1.74 / 1.63; N = 1e8 Vamana-style graph, pulled:
-  // 6.48 / 6.38, 1.77 / 1.77, 1.29 / 1.23; the same graph in HBM: 4.68 / 4.79, 1.44 / 1.41, 1.13 / 1.07.
-  // auto: on where the rows are pulled, and up to 8 queries per CU where the graph is in HBM
-  // (round 6, final kernel, structured 1e8-point graph in HBM, without / with: 10 000 queries 4.40 / 4.62 ms, 2 500: 1.32 / 1.345, 2 000: 1.18 / 1.13, 1 250: 1.05 / 1.02, 625: 0.94 / 0.91;
-  //  the shape-only DEEP100M index -- its filter drops next to nothing -- 7.16 / 7.05 at 10 000: the policy follows the structured graph, up to 8 queries per CU)
-  const bool spec_auto = p->row_layout != 0u || (p->Q + grid_n - 1) / grid_n <= 8u;
-  a.p.spec_rows = (!inmem && search_has_spec((int)(p->mp / 4u)) && p->d_graph && (p->spec_rows == 1u || (p->spec_rows == 0u && spec_auto))) ? 1u : 2u;
-  // (semantics = 1: no instances with the speculative row request -- off)
-  a.wl_words = search_wl_words(p->L);
-  a.wave_words = search_wave_words(p->L, nctx, (int)(p->mp / 4u), p->d_graph == nullptr);
-  *lds = (size_t)a.lds_piv_floats * 4 + (size_t)waves * a.wave_words * 4 + (p->d_graph ? 0u : SRCH_WG_SHARED_BYTES);
-  *grid = dim3(grid_n);
-  *block = dim3(waves * WAVE);
-  return BANG_OK;
-}
-
-#if BANG_SEARCH_INMEM
-
-// semantics = 1: the grid is that of the self-paced form of bang_k_search (the same LDS per wave: the candidate log is in HBM)
-extern "C" int bang_search_inmem_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
-                                          uint32_t* workgroups, uint32_t* waves) {
-  uint32_t nctx = 1, gs = 0;
-  return bang_search_geometry(psz, mp, nhi, L, Q, max_wgs, max_waves, 0, workgroups, waves, &nctx, &gs);
-}
-
-// engine-internal (bang_engine.h): does a semantics = 1 instance exist for this pivot layout and code-row stride?  (launch_al: not for 128-chunk
-// rows that are not dword-aligned)
-extern "C" int bang_search_inmem_has_instance(uint32_t psz, uint32_t mp, uint32_t code_stride) {
-  return (psz != 0 && mp / 4u >= 32u && (code_stride % 4u) != 0u) ? 0 : 1;
-}
-
-extern "C" int bang_k_search_inmem(const bang_search_params* p, void* stream) {
-  if (!p) return BANG_ERR_ARG;
-  if (p->Q == 0) return BANG_OK;
-  SearchArgs a;
-  dim3 grid, block;
-  size_t lds = 0;
-  const int rc = search_setup(p, true, &a, &grid, &block, &lds);
-  if (rc != BANG_OK) return rc;
-  // the fused re-rank works in the wave's LDS region: its n <= L + 120 candidate words fit (2L + L/4 + 144 words)
-  static_assert(BANG_INMEM_EXTRA_ITERS <= 144, "the fused re-rank's candidates fit the wave's LDS region");
-  return search_dispatch(a, grid, block, lds, (hipStream_t)stream);
-}
-
-#elif BANG_SEARCH_WORDFILTER
-
-// filter_layout = 1: the grid is that of the self-paced form of bang_k_search (the filter memory and the LDS per wave are what they were)
-extern "C" int bang_search_wf_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves,
-                                       uint32_t* workgroups, uint32_t* waves) {
-  uint32_t nctx = 1, gs = 0;
-  return bang_search_geometry(psz, mp, nhi, L, Q, max_wgs, max_waves, 0, workgroups, waves, &nctx, &gs);
-}
-
-// does a search_wf_kernel instance exist for this pivot layout and code-row stride?  (every layout of search_dispatch, in both row alignments)
-extern "C" int bang_search_wf_has_instance(uint32_t psz, uint32_t mp, uint32_t code_stride) {
-  (void)code_stride;
-  if (psz == 0 || (mp & 3u)) return 0;
-  switch (psz * 100u + mp / 4u) {
-    case 108: case 116: case 124: case 132: case 208: case 216: case 218: case 219: case 404: case 408: case 802: case 804: return 1;
-    default: return 0;
-  }
-}
-
-extern "C" int bang_k_search_wf(const bang_search_params* p, void* stream) {
-  if (!p) return BANG_ERR_ARG;
-  if (p->Q == 0) return BANG_OK;
-  if (!p->d_graph) { bang_set_error("filter_layout = 1: the word-local filter belongs to the self-paced form (d_graph: graph entries or pulled rows)"); return BANG_ERR_UNSUPPORTED; }
-  SearchArgs a;
-  dim3 grid, block;
-  size_t lds = 0;
-  const int rc = search_setup(p, false, &a, &grid, &block, &lds);
-  if (rc != BANG_OK) return rc;
-  return search_dispatch(a, grid, block, lds, (hipStream_t)stream);
-}
-
-#else
-
-// waves per workgroup that fit beside the pivot table with nctx query contexts each (0: not even one); the host-paced form also
-// keeps its pacing groups' shared words there
-static uint32_t waves_that_fit(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t nctx, bool host_paced) {
-  const size_t piv_bytes = (size_t)pivot_table_floats(psz, mp, nhi) * 4u;
-  const size_t per_wave = (size_t)search_wave_words(L, nctx, (int)(mp / 4u), host_paced) * 4u;
-  const size_t cap = (size_t)160 * 1024 - (host_paced ? SRCH_WG_SHARED_BYTES : 0u);
-  if (piv_bytes + per_wave > cap) return 0;
-  const size_t w = (cap - piv_bytes) / per_wave;
-  const size_t most = (size_t)search_maxt((int)(mp / 4u), host_paced) / WAVE;      // what the instance is compiled for
-  return (uint32_t)(w > most ? most : w);
-}
-
-extern "C" int bang_search_can_rerank(int dtype, uint32_t D, uint64_t vec_stride, uint32_t dim_adjust) {
-  const uint32_t G = D >> 4;
-  if (dim_adjust != 0 || (vec_stride & 3u) != 0 || D > 256) return 0;
-  if (dtype == BANG_F32) return D >= 4 && (D & 3u) == 0;                       // (one lane per candidate: wave_rerank_f32)
-  return (dtype == BANG_U8 || dtype == BANG_I8) && D >= 16 && (D & 15u) == 0 && (G & (G - 1u)) == 0;
-}
-
-extern "C" int bang_search_supported(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L) {
-  if (psz == 0 || L == 0 || L > BANG_MAX_L) return 0;
-  return (int)waves_that_fit(psz, mp, nhi, L, 1, false);            // (the self-paced form; the host-paced one may hold one wave less)
-}
-
-// One workgroup per CU at most (the pivot table takes most of the LDS).  A batch smaller than CUs x waves is spread over all
-// CUs with fewer waves each: a wave's iteration is latency bound, and fewer waves per CU contend less for LDS and L1.
-// Host-paced form: *nctx_io = query contexts per wave (0 = auto = 1), *group_waves_io = waves per pacing group (0 = auto = 8).
-extern "C" int bang_search_geometry(uint32_t psz, uint32_t mp, uint32_t nhi, uint32_t L, uint32_t Q, uint32_t max_wgs,
-                                    uint32_t max_waves, int host_paced, uint32_t* workgroups, uint32_t* waves_out, uint32_t* nctx_io,
-                                    uint32_t* group_waves_io) {
-  if (!workgroups || !waves_out || !nctx_io || !group_waves_io || Q == 0) return BANG_ERR_ARG;
-  if (psz == 0 || L == 0 || L > BANG_MAX_L) { bang_set_error("bad pq layout / L"); return BANG_ERR_ARG; }
-  uint32_t nctx = *nctx_io;
-  if (!host_paced) nctx = 1;
-  else if (nctx == 0) nctx = 1;     // two contexts per wave measured slower (more, emptier half-rounds): kept as an experiment knob
-  else if (nctx > 2) nctx = 2;
-  if (host_paced && search_maxt((int)(mp / 4u), true) < 1024) nctx = 1;       // (the filter summary lives in registers: one query per wave)
-  uint32_t waves = waves_that_fit(psz, mp, nhi, L, nctx, host_paced != 0);
-  if (waves == 0) { bang_set_error("pivot table + one wave's worklist do not fit LDS at L=%u", L); return BANG_ERR_UNSUPPORTED; }
-  if (max_waves && max_waves < waves) waves = max_waves;
-  const uint32_t cus = (uint32_t)num_cus();
-  uint32_t grid_n = Q < cus ? Q : cus;
-  if (max_wgs && max_wgs < grid_n) grid_n = max_wgs;
-  const uint32_t per_wg = ((Q + grid_n - 1) / grid_n + nctx - 1) / nctx;       // waves a workgroup needs to hold its share at once
-  if (per_wg < waves) waves = per_wg;
-  // A batch of one to two wave-fulls per CU runs as two EQUAL rounds (a full one followed by a nearly empty one keeps the chip a query
-  // lifetime longer for a few queries: 4 000 queries 3.75 -> 3.50 ms with 8 waves, 5 000: 4.39 -> 4.28 with 10; three rounds and more: nothing)
-  else if (!host_paced && per_wg > waves && per_wg <= 2 * waves) waves = (per_wg + 1) / 2;
-  // pacing groups: 8 waves by default, at least 4 (the group-shared LDS area holds 4 groups), the whole workgroup if it is small
-  uint32_t gs = *group_waves_io ? *group_waves_io : SRCH_DEFAULT_GROUP_WAVES;
-  if (gs > 16) gs = 16;
-  if (gs < 4) gs = 4;
-  if (gs > waves) gs = waves;
-  *workgroups = grid_n;
-  *waves_out = waves;
-  *nctx_io = nctx;
-  *group_waves_io = host_paced ? gs : waves;
-  return BANG_OK;
-}
-
-extern "C" int bang_k_search(const bang_search_params* p, void* stream) {
-  if (!p) return BANG_ERR_ARG;
-  if (p->Q == 0) return BANG_OK;
-  SearchArgs a;
-  dim3 grid, block;
-  size_t lds = 0;
-  const int rc = search_setup(p, false, &a, &grid, &block, &lds);
-  if (rc != BANG_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  return search_dispatch(a, grid, block, lds, st);
-}
-#endif   // BANG_SEARCH_INMEM
-#endif   // parts 0 / 2

@@ -46,7 +46,7 @@ def tsize(dtype: str) -> int:
 
 
 def fusable(dtype: str, D: int, vec_stride: int) -> bool:
-    """bang_search_can_rerank (csrc/bang_search.hip) restated, so that a parameter list can be made without the library;
+    """bang_search_can_rerank (csrc/bang_search_host.cpp) restated, so that a parameter list can be made without the library;
     tests/test_instance_inputs.py pins it to the library's answer."""
     if vec_stride % 4 or D > 256:
         return False

@@ -13,10 +13,10 @@ from bang_amd import binding as B
 from oracle import oracle as O
 
 # The twelve keys (psz * 100 + mp / 4) were read from
-#   csrc/bang_search.hip   search_dispatch, the `case` lines 1055-1068: 108 116 124 132 208 216 219 218 404 408 802 804
-#                          launch_al, lines 1029-1048: ALIGNED from (code_stride ? code_stride : m) % 4, NHI = 58 / 22 for 218 / 219
-#   csrc/bang_kernels.hip  kNdwList, line 906: {8, 16, 24, 32}, {8, 16, 18, 19}, {4, 8}, {2, 4} code dwords for psz 1, 2, 4, 8;
-#                          bang_pq_layout, lines 909-932; bang_ragged_supported, line 1153
+#   csrc/bang_search_args.h    BANG_PQ_LAYOUTS, the one list every switch over the layouts is generated from: (1, 8) (1, 16) (1, 24) (1, 32)
+#                              (2, 8) (2, 16) (2, 18) (2, 19) (4, 4) (4, 8) (8, 2) (8, 4) as (psz, code dwords); bang_layout_nhi: 58 / 22 for 218 / 219
+#   csrc/bang_search.hip       launch_al: ALIGNED from (code_stride ? code_stride : m) % 4
+#   csrc/bang_search_host.cpp  bang_pq_layout, bang_ragged_supported
 # Whoever adds an instance there extends KEYS here and instance_inputs.ENTRIES.
 KEYS = {108, 116, 124, 132, 208, 216, 218, 219, 404, 408, 802, 804}
 NHI = {218: 58, 219: 22}

@@ -112,6 +112,24 @@ def test_the_walk_stages_are_written_once():
     assert sorted(f for f in text if "__hip_atomic_fetch_or" in text[f]) == ["bang_search_beam.hip", "bang_wave_walk.h"]
 
 
+def test_the_search_kernels_host_side_and_layout_list_are_written_once():
+    """csrc/bang_search.hip holds the kernel and its instance dispatch; the argument checks, the geometry and the entry points live in
+    csrc/bang_search_host.cpp.  The compiled PQ layouts are listed once, in csrc/bang_search_args.h: no source switches over hand-written keys."""
+    import glob
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bang-billion-scale-ann_amd", "csrc")
+    text = {os.path.basename(f): open(f).read() for f in glob.glob(os.path.join(csrc, "*"))}
+    kernel = text["bang_search.hip"]
+    assert "getenv(" not in kernel and "bang_k_search" not in kernel and not re.search(r"\bint bang_search_geometry\(", kernel)
+    assert '#include "bang_search_args.h"' in kernel and "BANG_SEARCH_LAYOUTS(" in kernel
+    keys = "|".join(str(100 * psz + ndw) for psz, ndw in ((1, 8), (1, 16), (1, 24), (1, 32), (2, 8), (2, 16), (2, 18), (2, 19), (4, 4), (4, 8), (8, 2), (8, 4)))
+    for name, body in text.items():
+        if name.endswith(".hip"):
+            assert not re.search(rf"\bcase\s+({keys})\s*:", body), name
+        assert "kNdwList" not in body, name
+    assert sorted(name for name, body in text.items() if re.search(r"#define BANG_PQ_LAYOUTS\(", body)) == ["bang_search_args.h"]
+
+
 @pytest.mark.parametrize("regs", [64, 97, 104, 105, 128, 134, 256])
 def test_sweep_against_the_restated_rule(libbang, regs):
     sizes = [f(L) for L in (1, 37, 152, 512) for f in (plain_bytes, labels_bytes, *(lambda L, b=b: beam_bytes(L, b) for b in (2, 3, 4)))]

@@ -9,7 +9,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -5
 EXPORTS = ("bang_k_search_wf", "bang_search_wf_geometry", "bang_search_wf_has_instance", "bang_get_stats_ext")
-KEYS = (108, 116, 124, 132, 208, 216, 218, 219, 404, 408, 802, 804)          # search_dispatch, csrc/bang_search.hip
+KEYS = (108, 116, 124, 132, 208, 216, 218, 219, 404, 408, 802, 804)          # BANG_PQ_LAYOUTS, csrc/bang_search_args.h
 
 
 def _options(lib):

@@ -4,7 +4,8 @@
 For every *.o that carries a .hip_fatbin section the code object is unbundled and compared: the bytes of .text and of .rodata (the kernel
 descriptors), and per kernel the metadata note -- register counts, spills, LDS and private segment sizes, the kernarg layout.  Prints what
 differs; the exit status is 1 on any difference (an object missing on one side included), else 0.  What a refactor of host code or of shared
-headers must leave alone is exactly this."""
+headers must leave alone is exactly this.  Where the sections differ but every kernel's own bytes do not -- its code, and its descriptor apart from
+the distance between the two -- the kernels only stand in another order (the order their instances are first named in the source), and the report says so."""
 import glob
 import os
 import re
@@ -39,7 +40,21 @@ def device_code(obj, tmp):
     kernels = {}
     for entry in re.split(r"^  - ", body, flags=re.M)[1:]:
         kernels[re.search(r"\.name:\s*(\S+)", entry).group(1)] = entry
-    return sections, kernels
+    return sections, kernels, _own_bytes(co, sections)
+
+
+def _own_bytes(co, sections):
+    """{symbol: bytes} of every kernel (.text) and kernel descriptor (.rodata; without bytes 16-23, the offset from the descriptor to the code)"""
+    base = {m.group(1): int(m.group(2), 16) for m in re.finditer(r"\] (\.text|\.rodata)\s+PROGBITS\s+([0-9a-f]+)", _run("llvm-readelf", "-S", "-W", co))}
+    own = {}
+    for m in re.finditer(r"^\s*\d+: ([0-9a-f]+)\s+(\d+) (FUNC|OBJECT)\s+\S+\s+\S+\s+\d+ (\S+)$", _run("llvm-readelf", "--dyn-syms", "-W", co), flags=re.M):
+        if m.group(3) == "OBJECT" and not m.group(4).endswith(".kd"):
+            continue
+        sec = ".text" if m.group(3) == "FUNC" else ".rodata"
+        at = int(m.group(1), 16) - base[sec]
+        b = sections[sec][at:at + int(m.group(2))]
+        own[m.group(4)] = b if sec == ".text" else b[:16] + b[24:]
+    return own
 
 
 def _fields(entry):
@@ -74,6 +89,8 @@ def main(a, b):
                     fa, fb = _fields(ca[1][k]), _fields(cb[1][k])
                     what = ", ".join(f"{f} {fa.get(f)} -> {fb.get(f)}" for f in sorted(set(fa) | set(fb)) if fa.get(f) != fb.get(f))
                     diffs.append(f"kernel {k}: {what or 'metadata text differs'}")
+            if diffs and all(d.startswith(".") for d in diffs) and ca[2] == cb[2]:
+                diffs.append(f"each of the {len(ca[1])} kernels and its descriptor is byte-identical: the kernels stand in another order")
             if diffs:
                 bad += 1
                 print(f"{name}: DIFFERENT\n  " + "\n  ".join(diffs))
