@@ -117,6 +117,31 @@ class StatsExt5(C.Structure):
                                      ("backedge_pruned", C.c_uint64), ("backedge_dropped", C.c_uint64)]
 
 
+class StatsExt6(C.Structure):
+    """bang_stats_ext6: bang_stats_ext5 with the consolidation fields behind it (bang_get_stats_ext6)."""
+    _fields_ = StatsExt5._fields_ + [("consolidated_rows", C.c_uint64), ("removed", C.c_uint64), ("consolidate_dropped", C.c_uint64)]
+
+
+class ConsolidateScanParams(C.Structure):
+    """bang_consolidate_scan_params (include/bang_c.h): device addresses."""
+    _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("R", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("medoid", C.c_uint32), ("d_excluded", C.c_void_p), ("d_affected", C.c_void_p), ("d_abort", C.c_void_p)]
+
+
+class ConsolidateGatherParams(C.Structure):
+    """bang_consolidate_gather_params (include/bang_c.h): device addresses."""
+    _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("R", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("medoid", C.c_uint32), ("n_lists", C.c_uint32), ("d_excluded", C.c_void_p), ("d_nodes", C.c_void_p),
+                ("d_cand_ids", C.c_void_p), ("d_cand_dists", C.c_void_p), ("d_offered", C.c_void_p), ("d_own_out", C.c_void_p),
+                ("d_stats", C.c_void_p), ("d_abort", C.c_void_p)]
+
+
+class ConsolidateClearParams(C.Structure):
+    """bang_consolidate_clear_params (include/bang_c.h): device addresses."""
+    _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("R", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("medoid", C.c_uint32), ("d_excluded", C.c_void_p)]
+
+
 class PruneParams(C.Structure):
     """bang_prune_params (include/bang_c.h): device addresses."""
     _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("n_nodes", C.c_uint32),
@@ -569,6 +594,31 @@ class Engine:
         ms = (C.c_double * 6)()
         _check(lib().bang_get_insert_times(self._h, ms), "bang_get_insert_times")
         return dict(zip(("search", "prune", "group", "backedge", "encode", "total"), (float(x) for x in ms)))
+
+    # ---- consolidation (bang_consolidate_e)
+    def consolidate(self, alpha: float = 1.2) -> dict:
+        """bang_consolidate_e: fold the exclusion set into the graph in HBM -- the rows that list an excluded node are re-pruned from their own
+        live ids and the live ids of the excluded neighbours' rows, the excluded nodes' rows are emptied, the set shrinks to the medoid (if it was
+        in it).  -> dict(rows, removed, dropped, still_excluded) of this call.  Needs Engine(..., graph=GRAPH_DEVICE, capacity=...) and no live
+        allocation."""
+        st = (C.c_uint64 * 4)()
+        fn = lib().bang_consolidate_e
+        fn.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+        _check(fn(self._h, C.c_float(alpha), st), "bang_consolidate")
+        return dict(zip(("rows", "removed", "dropped", "still_excluded"), (int(x) for x in st)))
+
+    def consolidate_stats(self) -> dict:
+        """bang_stats_ext6's own fields: consolidated_rows, removed, consolidate_dropped (totals since the load)."""
+        s = StatsExt6()
+        _check(lib().bang_get_stats_ext6(self._h, C.byref(s)), "bang_get_stats_ext6")
+        return {f: getattr(s, f) for f, _ in StatsExt6._fields_[len(StatsExt5._fields_):]}
+
+    def consolidate_times(self) -> dict:
+        """bang_get_consolidate_times: milliseconds of the last consolidation per part (scan + list, the gather / sort / prune chunks, clear +
+        seed list) and in all."""
+        ms = (C.c_double * 4)()
+        _check(lib().bang_get_consolidate_times(self._h, ms), "bang_get_consolidate_times")
+        return dict(zip(("scan", "rows", "clear", "total"), (float(x) for x in ms)))
 
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the

@@ -8,6 +8,8 @@
 //   bang_cabi.cpp     the engine-level C-ABI of include/bang_c.h
 //   bang_insert_host.cpp  bang_insert_e: the launches of an insert (option capacity), the entry / code downloads; bang_insert_group.cpp: its
 //                     host-side grouping of the new rows by target (no HIP call, no engine)
+//   bang_consolidate_host.cpp  bang_consolidate_e: the launches that fold the exclusion set into the graph; bang_consolidate_group.cpp: the
+//                     affected bitmap as a list of ids (no HIP call, no engine)
 #ifndef BANG_ENGINE_H_
 #define BANG_ENGINE_H_
 
@@ -340,6 +342,9 @@ struct bang_engine {
   uint64_t stat_inserted = 0, stat_be_appended = 0, stat_be_pruned = 0, stat_be_dropped = 0;   // bang_stats_ext5: totals since the load
   bool insert_broken = false;          // a bang_insert_e failed after it had begun to write the tables: bang_insert_e and bang_alloc_e refuse until bang_unload
   double insert_ms[6] = {0, 0, 0, 0, 0, 0};   // the last bang_insert_e: {search, prune, rows down + host grouping, back-edges, encode} on the stream / host, the whole call
+  // consolidation (bang_consolidate_e)
+  uint64_t stat_cons_rows = 0, stat_cons_removed = 0, stat_cons_dropped = 0;   // bang_stats_ext6: totals since the load
+  double consolidate_ms[4] = {0, 0, 0, 0};    // the last bang_consolidate_e: {scan + list, gather / sort / prune, clear + seed, the whole call}, host wall time
 };
 
 // bang_search_host.cpp (semantics = 1: parts 2 and 3 of bang_search.hip): 0 where no search_inmem_kernel instance exists for the pivot layout and code-row stride
@@ -410,6 +415,8 @@ int wait_flag(bang_engine* e, Lane& ln, uint32_t value);
 void lane_job(bang_engine* e, Lane& ln);
 void start_threads(bang_engine* e);
 void stop_threads(bang_engine* e);
+// ---- bang_insert_host.cpp
+int rebuild_seed(bang_engine* e);         // the seed list {count, medoid, row(medoid)} from the medoid's row as it stands in HBM (insert, consolidation)
 // ---- bang_lane.cpp
 int lane_run(bang_engine* e, Lane& ln, const void* h_queries, uint64_t* h_ids, float* h_dists, int Q);
 

@@ -49,18 +49,6 @@ int check_abort(uint32_t* d_abort, const char* where) {
   return BANG_OK;
 }
 
-int rebuild_seed(bang_engine* e) {
-  const size_t vb = vec_bytes(e);
-  std::vector<uint32_t> row(1 + e->R), seed(2 + BANG_MAX_R + 1, 0);
-  HIP_TRY(hipMemcpy(row.data(), e->d_graph + e->medoid * e->entry_len + vb, row.size() * 4, hipMemcpyDeviceToHost));
-  const uint32_t deg = std::min(row[0], e->R);
-  seed[0] = deg + 1;
-  seed[1] = (uint32_t)e->medoid;
-  memcpy(&seed[2], row.data() + 1, (size_t)deg * 4);
-  HIP_TRY(hipMemcpy(e->d_seed, seed.data(), seed.size() * 4, hipMemcpyHostToDevice));
-  return BANG_OK;
-}
-
 int insert_batch(bang_engine* e, const uint8_t* h_vectors, uint32_t n, uint32_t L, float alpha2) {
   const uint32_t N = e->N, R = e->R, D = e->D;
   const size_t vb = vec_bytes(e);
@@ -205,6 +193,18 @@ int insert_batch(bang_engine* e, const uint8_t* h_vectors, uint32_t n, uint32_t 
 }
 
 }  // namespace
+
+int bang::rebuild_seed(bang_engine* e) {
+  const size_t vb = vec_bytes(e);
+  std::vector<uint32_t> row(1 + e->R), seed(2 + BANG_MAX_R + 1, 0);
+  HIP_TRY(hipMemcpy(row.data(), e->d_graph + e->medoid * e->entry_len + vb, row.size() * 4, hipMemcpyDeviceToHost));
+  const uint32_t deg = std::min(row[0], e->R);
+  seed[0] = deg + 1;
+  seed[1] = (uint32_t)e->medoid;
+  memcpy(&seed[2], row.data() + 1, (size_t)deg * 4);
+  HIP_TRY(hipMemcpy(e->d_seed, seed.data(), seed.size() * 4, hipMemcpyHostToDevice));
+  return BANG_OK;
+}
 
 extern "C" int bang_insert_e(bang_engine_t* e, const void* h_vectors, uint32_t n, uint32_t L_build, float alpha, uint64_t* first_id) {
   if (!e) { bang_set_error("bang_insert: the engine is null"); return BANG_ERR_ARG; }

@@ -262,6 +262,24 @@ int bang_insert_e(bang_engine_t* e, const void* h_vectors, uint32_t n, uint32_t 
  * (n * m bytes, whatever the stride in HBM).  first + n <= N. */
 int bang_get_entries_e(bang_engine_t* e, uint64_t first, uint64_t n, void* out);
 int bang_get_codes_e(bang_engine_t* e, uint64_t first, uint64_t n, void* out);
+/* CONSOLIDATION (DESIGN.md section 2 CANON 22, section 4.16; FreshDiskANN Algorithm 4): folds the exclusion set X into the graph, in HBM.  med = the
+ * medoid, D = X \ {med} the nodes removed (an excluded medoid stays a routing node: live below, its row repaired like any other, still excluded from
+ * answers).  Every p not in D whose row lists a node of D is AFFECTED; its candidates are the ids of its row outside D, then for each v of its row in
+ * D the ids of row(v) that are neither in D nor p (row order, duplicates kept, cut at BANG_PRUNE_MAX_LIST = 512, the rest counted as dropped); each
+ * gets its exact distance to vector(p); the list is sorted and de-duplicated by (distance bits << 32) | id (bang_k_range_sort) and RobustPruned at
+ * alpha2 = fl32(fl32(alpha) * fl32(alpha)) into p's row (bang_k_prune; an empty list gives degree 0).  Every affected row goes through the prune --
+ * DiskANN's copy of a candidate set of at most R ids without pruning is not built.  Rows are computed from the graph as it stood at the call, so
+ * the result does not depend on the order or chunking.  Then the row of every node of D becomes degree 0 with all R slots 0 (vector and PQ code
+ * stay, ids are not renumbered, N does not move), the seed list is rebuilt from the medoid's row and the exclusion set becomes X & {med}.  Rows of
+ * nodes that are not affected, and every byte outside rows, are unchanged.
+ * out_stats4 (may be NULL): {rows rewritten, nodes removed, candidates dropped by the cut, ids still excluded (0 or 1)} of this call.
+ * Refused with "bang_consolidate" in the message and no side effect: a null engine or no index loaded; a live allocation (bang_free_e first); an
+ * engine whose insert failed half-way; no option capacity (the mutable, HBM-resident engine of bang_insert_e: capacity = N is enough); alpha not
+ * finite or outside [1, 8] (BANG_ERR_ARG); MIPS search parameters; a layout outside bang_search_can_rerank (BANG_ERR_UNSUPPORTED).  A label table
+ * may stay set.  An empty exclusion set is BANG_OK with zero statistics and writes nothing.  A row that lists an id >= N: the id is never
+ * dereferenced, the call returns BANG_ERR_IO and names the step.  A call that fails before the rows of D are cleared leaves a graph that every
+ * walk may run on -- rewritten rows list live nodes only, the others nodes that still exist -- and the exclusion set untouched. */
+int bang_consolidate_e(bang_engine_t* e, float alpha, uint64_t* out_stats4);
 int bang_unload_e(bang_engine_t* e);                                                        /* bang.h:82 */
 
 /* statistics of the last bang_query_e */
@@ -361,6 +379,17 @@ int bang_get_stats_ext5(bang_engine_t* e, bang_stats_ext5* out);
  * back-edge launches (CSR upload included), [4] the PQ encode -- stream time between event stamps --, [2] the new rows' download + the host-side
  * grouping and [5] the whole call, host wall time (allocations and copies included). */
 int bang_get_insert_times(bang_engine_t* e, double* ms6);
+/* ... and once more for consolidation (bang_consolidate_e): the earlier structs keep size and offsets.  The three counters are totals since the load */
+typedef struct {
+  bang_stats_ext5 ext5;
+  uint64_t consolidated_rows;   /* rows rewritten by bang_consolidate_e */
+  uint64_t removed;             /* nodes whose rows it emptied */
+  uint64_t consolidate_dropped; /* candidates dropped because a row's list exceeded BANG_PRUNE_MAX_LIST */
+} bang_stats_ext6;
+int bang_get_stats_ext6(bang_engine_t* e, bang_stats_ext6* out);
+/* Where the last bang_consolidate_e spent its time, milliseconds of host wall time: ms4[0] the scan, the download of the affected bitmap and the
+ * list, [1] the gather / sort / prune chunks, [2] the clear, the seed list and the exclusion set, [3] the whole call (allocations included). */
+int bang_get_consolidate_times(bang_engine_t* e, double* ms4);
 /* Per-query counters of the last bang_query_e (arrays of num_queries words; any pointer may be NULL): PQ distance evaluations,
  * adjacency ids offered to the filter, expanded nodes (candidate-log length) and -- search kernel only, else zeros -- the number
  * of iterations the query ran.  Test hook: the oracle reports the same four numbers per query. */
@@ -863,6 +892,59 @@ int bang_k_pq_encode(const float* d_pivots_T, const void* d_vectors, int dtype, 
  * BANG_ERR_ARG (no message) on a null argument, row_stride < 2, a degree > R or an id >= n_old. */
 int bang_insert_group(const uint32_t* rows, uint32_t n, uint32_t row_stride, uint32_t first_id, uint32_t n_old, uint32_t* targets, uint32_t* offs,
                       uint32_t* srcs, uint32_t* n_targets);
+
+/* CONSOLIDATION, device side (csrc/bang_consolidate.hip; engine: bang_consolidate_e; DESIGN.md section 2 CANON 22, section 4.16).  d_excluded is the
+ * exclusion bitmap X as bang_k_worklist_pick reads it (ceil(n_nodes / 32) words plus one of slack); a node is REMOVED when its id is < n_nodes, is
+ * not `medoid` and has its bit set (D = X \ {medoid}).  row(p) is the first min(degree word, R) ids of p's row, read as ending in front of its
+ * first id >= n_nodes: such an id is never dereferenced and *d_abort = 2.  Layouts are those of bang_k_backedge (the entry stride holds vector
+ * and row); the wide layouts are BANG_ERR_UNSUPPORTED.  Every entry checks its arguments before any HIP call and names the offending one:
+ * a null or misaligned d_graph, d_excluded null, R outside [1, 64], n_nodes = 0, medoid >= n_nodes, a null output (BANG_ERR_ARG).
+ *
+ * bang_k_consolidate_scan: one wave per node over [0, n_nodes).  Bit p of d_affected (ceil(n_nodes / 32) words, ZEROED BY THE CALLER) is set
+ * when p is not removed and row(p) lists a removed node.  Nothing else is written. */
+typedef struct {
+  const uint8_t* d_graph;      /* [n_nodes][entry_len] */
+  uint64_t entry_len;
+  uint32_t dtype, D, R, n_nodes, medoid;
+  const uint32_t* d_excluded;
+  uint32_t* d_affected;        /* [ceil(n_nodes / 32)] */
+  uint32_t* d_abort;           /* [1] or NULL */
+} bang_consolidate_scan_params;
+int bang_k_consolidate_scan(const bang_consolidate_scan_params* p, void* stream);
+/* bang_k_consolidate_gather: one wave per list.  List i belongs to node p = d_nodes[i] (p >= n_nodes: d_offered[i] = 0, d_own_out[i] =
+ * BANG_PRUNE_SKIP, *d_abort = 2).  Its candidates, in this order: the ids of row(p) that are not removed, in row order; then, for each removed v of
+ * row(p) in row order, the ids of row(v) that are neither removed nor p, in row order.  Duplicates stay.  The first BANG_PRUNE_MAX_LIST of them go
+ * to row i of d_cand_ids ([n_lists][BANG_PRUNE_MAX_LIST]), each one's exact distance to the query vector(p) -- exact_dist8 / exact_dist_f32 -- to
+ * the same place of d_cand_dists; d_offered[i] = their number (0: nothing of the row is written), d_own_out[i] = p; d_stats[0] is incremented by
+ * the candidates the cut dropped.  bang_k_range_sort (cap = BANG_PRUNE_MAX_LIST) and bang_k_prune (out_by_own) then write p's row.  The graph is
+ * only read. */
+typedef struct {
+  const uint8_t* d_graph;
+  uint64_t entry_len;
+  uint32_t dtype, D, R, n_nodes, medoid, n_lists;
+  const uint32_t* d_excluded;
+  const uint32_t* d_nodes;     /* [n_lists] */
+  uint32_t* d_cand_ids;
+  float* d_cand_dists;
+  uint32_t* d_offered;         /* [n_lists] */
+  uint32_t* d_own_out;         /* [n_lists] */
+  uint32_t* d_stats;           /* [1] */
+  uint32_t* d_abort;           /* [1] or NULL */
+} bang_consolidate_gather_params;
+int bang_k_consolidate_gather(const bang_consolidate_gather_params* p, void* stream);
+/* bang_k_consolidate_clear: one wave per node over [0, n_nodes); the row of every removed node becomes R + 1 zero words (degree 0, every slot 0).
+ * Its vector, and every other node's entry, are not written. */
+typedef struct {
+  uint8_t* d_graph;
+  uint64_t entry_len;
+  uint32_t dtype, D, R, n_nodes, medoid;
+  const uint32_t* d_excluded;
+} bang_consolidate_clear_params;
+int bang_k_consolidate_clear(const bang_consolidate_clear_params* p, void* stream);
+/* Host side of a consolidation, no HIP call in it (csrc/bang_consolidate_group.cpp): the affected bitmap as the ascending list of its node ids.
+ * bitmap holds ceil(n_nodes / 32) words; bits of the last word at or behind n_nodes are ignored.  ids holds up to n_nodes words.  BANG_ERR_ARG
+ * (no message) on a null argument. */
+int bang_consolidate_group(const uint32_t* bitmap, uint32_t n_nodes, uint32_t* ids, uint32_t* n_ids);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
