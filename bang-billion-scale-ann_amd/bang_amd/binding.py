@@ -63,6 +63,7 @@ class SearchParams(C.Structure):
         ("group_waves", C.c_uint32), ("d_prof", C.c_void_p), ("code_stride", C.c_uint32), ("n_rows_hbm", C.c_uint32), ("d_rows_hbm", C.c_void_p),
         ("d_row_slices", C.c_void_p), ("n_slices", C.c_uint32), ("slice_rows", C.c_uint32), ("go_timeout_ticks", C.c_uint64), ("d_qskip", C.c_void_p),
         ("n_nodes", C.c_uint32), ("summ_iters", C.c_uint32), ("spec_rows", C.c_uint32),
+        ("n_rows_pad", C.c_uint32),          # padded rows: the rows of the nodes [0, n_rows_pad) sit in d_codes' padding (in the former padding: no member moved)
         ("rr_queries", C.c_void_p), ("rr_vec_base", C.c_void_p), ("rr_vec_stride", C.c_uint64), ("rr_ids_out", C.c_void_p), ("rr_dists_out", C.c_void_p),
         ("rr_dtype", C.c_uint32), ("rr_D", C.c_uint32), ("rr_k", C.c_uint32), ("rr_q0", C.c_uint32), ("rr_Q_total", C.c_uint32),
         ("rr_vec_f16", C.c_uint32),          # bang_k_search_exact, row_layout = 1: rr_vec_base holds fp16 rows (in the former padding: no member moved)
@@ -372,6 +373,14 @@ class Engine:
         h = C.c_uint64()
         _check(lib().bang_get_rows_hash(self._h, C.byref(h)), "bang_get_rows_hash")
         return int(h.value)
+
+    def rows_pad(self) -> int:
+        """bang_rows_pad_e: adjacency rows of the nodes [0, n) that sit in the padding of the PQ code table (option rows_pad), 0 = none."""
+        n = C.c_uint64()
+        fn = lib().bang_rows_pad_e
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        _check(fn(self._h, C.byref(n)), "bang_rows_pad")
+        return int(n.value)
 
     # ---- peer rows (include/bang_c.h): the node's adjacency rows in the node's spare HBM
     def rows_capacity(self) -> int:

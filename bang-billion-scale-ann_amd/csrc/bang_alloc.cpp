@@ -228,6 +228,16 @@ static int resolve_form(bang_engine* e) {
                    "this form re-ranks from a vector log (%s), whose rows are indexed by log position", e->form == LoopForm::HostPaced ? "by query" : "by iteration");
     return BANG_ERR_UNSUPPORTED;
   }
+  // padded rows (option rows_pad; bang_load filled the code table's padding): only the self-paced PQ search kernel reads them -- bang_k_search and
+  // bang_k_search_wf, not the Inmemory walk (graph in HBM anyway) -- and never through a slice table.  Forced, anything else is refused; on auto they
+  // are given up for the rest of this load and the HBM copy starts over at row 0
+  if (e->n_rows_pad != 0) {
+    const char* no = e->form == LoopForm::Exact ? "distance = 1 (the exact-distance kernels)" : e->form == LoopForm::HostPaced ? "walker = 1 (the host-paced search kernel)"
+                   : e->form == LoopForm::Lut ? "the LUT path" : e->form == LoopForm::PerIteration ? "the per-iteration kernels (search = 0 / persistent = 0 / no room in LDS)"
+                   : e->search_inmem ? "semantics = 1" : e->n_slices > 1 ? "peer rows" : nullptr;
+    if (no && e->rows_pad_opt == 1) { bang_set_error("option rows_pad = 1: padded rows cannot be read with %s", no); return BANG_ERR_UNSUPPORTED; }
+    if (no) drop_pad_rows(e);
+  }
   return BANG_OK;
 }
 

@@ -462,7 +462,7 @@ extern "C" int bang_alloc_e(bang_engine_t* e, int Q) {
     // the copy of the first adjacency rows took the HBM a batch of this size needs: the rows are in host memory anyway
     free_batch(e);
     dfree(e->d_rows_hbm);
-    e->n_rows_hbm = 0; e->rows_first = 0;
+    e->n_rows_hbm = 0; e->rows_first = e->n_rows_pad;      // (the padded rows cost no memory: they stay)
     (void)hipGetLastError();
     rc = alloc_buffers(e, Q);
   }
@@ -617,8 +617,8 @@ static int query_impl(bang_engine_t* e, const void* h_queries, int Q, uint64_t* 
   e->stat_filter_layout = e->search_wordfilter ? 1 : 0;          // (reported behind bang_stats: bang_get_stats_ext)
   s.code_stride = e->code_stride;
   // what the kernel was GIVEN (bang_lane.cpp): without a slice table a slice moved off row 0 (bang_rows_slice_e(first > 0)) is not reachable
-  const uint32_t rows_direct = (e->rows_first == 0 ? e->n_rows_hbm : 0);
-  s.rows_in_hbm = (s.graph_pull ? (e->n_slices > 1 ? e->n_rows_hbm : rows_direct) : 0);
+  // (padded rows, option rows_pad: the nodes [0, n_rows_pad) in front of the copy count too)
+  s.rows_in_hbm = (s.graph_pull ? (e->n_slices > 1 ? e->n_rows_hbm : (uint64_t)e->n_rows_pad + rows_direct(e)) : 0);
   return rc;
 }
 
@@ -684,7 +684,7 @@ extern "C" int bang_get_stats(bang_engine_t* e, bang_stats* out) {
     s.hops_max = cc.back();
     if (s.graph_pull || e->walker_self) {                // one row per expansion (the seed list is on the device) ...
       uint64_t pulled = s.candidates - (uint64_t)e->Qcur;
-      if (e->n_rows_hbm || e->n_slices > 1) {            // ... unless the expanded node's row sits in HBM (this GPU's or a peer's): count the candidate log
+      if (e->n_rows_hbm || e->n_rows_pad || e->n_slices > 1) {            // ... unless the expanded node's row sits in HBM (this GPU's or a peer's): count the candidate log
         std::vector<uint32_t> ids((size_t)e->Qcur * e->cand_stride);
         HIP_TRY(hipMemcpy(ids.data(), e->d_cand_ids, ids.size() * 4, hipMemcpyDeviceToHost));
         pulled = 0;
@@ -697,7 +697,7 @@ extern "C" int bang_get_stats(bang_engine_t* e, bang_stats* out) {
               const uint32_t sl = id / e->slice_rows;
               if (sl < e->n_slices && e->slice_base[sl]) { if (sl == e->own_slot) ++s.rows_from_own_hbm; else ++s.rows_from_peer; }
               else ++pulled;
-            } else if (id < (e->rows_first == 0 ? e->n_rows_hbm : 0)) ++s.rows_from_own_hbm;
+            } else if (id < e->n_rows_pad || id - e->n_rows_pad < rows_direct(e)) ++s.rows_from_own_hbm;      // (padded rows, then the copy behind them)
             else ++pulled;
           }
       }

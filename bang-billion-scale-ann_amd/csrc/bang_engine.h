@@ -285,7 +285,10 @@ struct bang_engine {
                                        // 12 GB -- where the rows do not all fit --, 0 = none): read from HBM instead of pulled over PCIe
   uint32_t* d_rows_hbm = nullptr;      // [n_rows_hbm][64]: the rows [rows_first, rows_first + n_rows_hbm)
   uint32_t n_rows_hbm = 0;
-  uint64_t rows_first = 0;             // first node of the HBM copy (0 unless bang_rows_slice_e moved it: peer rows)
+  uint64_t rows_first = 0;             // first node of the HBM copy: n_rows_pad, unless bang_rows_slice_e moved it (peer rows)
+  int rows_pad_opt = -1;               // option "rows_pad": adjacency rows in the code table's padding (-1 = auto, 0 = off, 1 = forced: what cannot have them is refused)
+  uint32_t n_rows_pad = 0;             // padded rows (bang_pad_rows.h): the rows of the nodes [0, n_rows_pad) sit in d_codes' padding, read by the self-paced PQ search kernel
+  bool rows_pad_dropped = false;       // this load's padded rows were given up (a form that cannot read them, peer rows): not filled again before bang_unload
   bool rows_exported = false;          // an IPC handle of d_rows_hbm is out: never freed before bang_unload
   // peer rows (bang_rows_import_e): slice s of the node's HBM-resident rows starts at node s * slice_rows
   uint32_t n_slices = 0, slice_rows = 0, own_slot = 0xFFFFFFFFu;
@@ -354,6 +357,9 @@ namespace bang {
 
 // the whole batch is ONE launch of a search kernel (every form but the launch-per-iteration loop)
 inline bool one_launch(const bang_engine* e) { return e->form != LoopForm::PerIteration; }
+// rows of the HBM copy a kernel reaches without a slice table: the copy starts where the padded rows end (row 0 without them) -- a slice moved
+// elsewhere (bang_rows_slice_e) is only reachable through the table
+inline uint32_t rows_direct(const bang_engine* e) { return e->rows_first == e->n_rows_pad ? e->n_rows_hbm : 0u; }
 inline size_t vec_bytes(const bang_engine* e) { return (size_t)e->D * e->tsize; }
 // bytes between the rows of the HBM vector table d_vecs: the vector as the index holds it, or its fp16 image padded to whole dwords
 inline size_t vec_table_stride(const bang_engine* e) { return e->vecs_f16 ? (((size_t)2 * e->D + 3) & ~(size_t)3) : vec_bytes(e); }
@@ -402,6 +408,7 @@ int load_files(bang_engine* e, const char* prefix);
 int load_shared(bang_engine* e, uint64_t expect_rows_hash);    // vectors already in the caller's device buffer, rows in the node's rows file
 int map_graph_file(bang_engine* e);
 int validate_pull_rows(bang_engine* e);   // pull mode, at bang_alloc: the rows mapping is still what bang_load registered
+void drop_pad_rows(bang_engine* e);        // padded rows off for the rest of this load; the HBM copy starts over at row 0 (unless it is exported / a peer slice)
 // ---- bang_alloc.cpp
 int alloc_buffers(bang_engine* e, int Q);
 void free_batch(bang_engine* e);

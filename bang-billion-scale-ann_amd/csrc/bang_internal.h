@@ -35,6 +35,12 @@ int bang_k_init_state(uint32_t Q, uint32_t medoid, uint32_t cand_stride, uint32_
                       uint32_t* d_cand_cnt, uint32_t* d_wl_cnt, uint32_t* d_mark, uint32_t* d_parents, uint32_t* d_cnt,
                       void* stream);
 
+// padded rows (option rows_pad; bang_pad_rows.hip, layout in bang_pad_rows.h): the staged 256-byte rows d_rows[n_rows][64] go into the padding of
+// the code lines of the padded rows [row0, row0 + n_rows) of a table of n_lines lines; m = the chunks the lines are interpreted as (the layout's mp).
+// Refused (BANG_ERR_ARG, nothing launched) where the layout is unusable or the last line lies behind the table
+int bang_k_pad_rows_scatter(uint8_t* d_codes, uint64_t n_lines, uint32_t code_stride, uint32_t m, const uint32_t* d_rows, uint32_t row0,
+                            uint32_t n_rows, void* stream);
+
 #define BANG_ADJ_PAD 0xFFFFFFFFu      /* unused slot of a 256-byte adjacency row (bang_search_params.row_layout = 1) */
 
 // bang_init in one launch: clears the visited filters, resets the per-query state (as bang_k_init_state) and the diagnostic counters

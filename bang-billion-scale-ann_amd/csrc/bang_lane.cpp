@@ -150,7 +150,8 @@ static int walk_params(bang_engine* e, Lane& ln, const RunFacts& r, const bang_i
 // HBM copy of the first rows and the node's slice table
 static void pulled_rows(const bang_engine* e, bang_search_params& sp) {
   sp.d_graph = (const uint8_t*)e->d_adj; sp.entry_len = 256; sp.row_layout = 1;
-  sp.d_rows_hbm = e->d_rows_hbm; sp.n_rows_hbm = e->rows_first == 0 ? e->n_rows_hbm : 0;      // (a moved slice is only reachable through the table)
+  sp.d_rows_hbm = e->d_rows_hbm; sp.n_rows_hbm = rows_direct(e);      // (a moved slice is only reachable through the table)
+  sp.n_rows_pad = e->n_rows_pad;                                      // (padded rows: the self-paced PQ form alone -- bang_alloc gave them up or refused for every other)
   if (e->n_slices > 1 && e->d_slice_tab) { sp.d_row_slices = e->d_slice_tab; sp.n_slices = e->n_slices; sp.slice_rows = e->slice_rows; }
 }
 
@@ -325,7 +326,7 @@ static int run_host_paced(bang_engine* e, Lane& ln, const RunFacts& r, const ban
   sp.d_codes = e->d_codes; sp.code_stride = e->code_stride; sp.d_pivots_packed = p.d_pivots_packed; sp.d_qc = p.d_qc;
   sp.d_graph = nullptr; sp.entry_len = e->entry_len; sp.vec_bytes = (uint32_t)r.vb;
   // walker-from-rows: parents whose row sits in this GPU's HBM copy of the first rows are served by the kernel itself
-  e->walker_self = e->walker_rows && e->d_rows_hbm && e->rows_first == 0 && env_long("BANG_WALKER_SELF_ROWS", 1) != 0;
+  e->walker_self = e->walker_rows && e->d_rows_hbm && e->rows_first == 0 && e->n_rows_pad == 0 && env_long("BANG_WALKER_SELF_ROWS", 1) != 0;
   if (e->walker_self) { sp.d_rows_hbm = e->d_rows_hbm; sp.n_rows_hbm = e->n_rows_hbm; }
   sp.d_rows = e->d_srows; sp.d_ctl = e->d_sctl; sp.h_done = e->h_done_dev; sp.h_parents = e->d_parents_map;
   sp.h_pub_q = e->d_pub_q; sp.h_pub_c = e->d_pub_c; sp.ship_vectors = e->vec_on_device ? 0u : 1u;

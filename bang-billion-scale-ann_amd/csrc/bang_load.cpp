@@ -1,6 +1,7 @@
 // bang_load.cpp -- bang_load (bang_search.cu:138-362): index files and entry sources, graph placement, pull rows, streamed load.
 // Reference line numbers: /root/reference/BANG_Base/bang_search.cu.
 #include "bang_engine.h"
+#include "bang_pad_rows.h"
 
 namespace bang {
 
@@ -267,39 +268,110 @@ static int build_pull_rows(bang_engine* e) {
   return pull_rows_finish(e, pr, sig);
 }
 
-// Pull mode, after everything else of the index is in place: HBM the index leaves over takes a copy of the first adjacency rows.
+// Padded rows (option rows_pad, bang_pad_rows.h): the rows of the nodes [0, n_pad) go into the bytes of the code lines that no kernel interprets --
+// HBM that is allocated anyway (SIFT1B-shape: 56 of every 128 bytes, room for N / 5 rows).  Staged through an HBM buffer in chunks of at most
+// 1 GiB and scattered by bang_k_pad_rows_scatter.  Returns the reason it cannot be done (nullptr: e->n_rows_pad is set); a half-filled padding is
+// harmless -- nothing reads it while n_rows_pad is 0.  A caller's code table (bang_index_desc.d_codes) is written to like the engine's own: those
+// bytes of its lines are no code either, and the caller that keeps something of its own there sets rows_pad = 0 (include/bang_c.h)
+static const char* fill_pad_rows(bang_engine* e) {
+  e->n_rows_pad = 0;
+  const uint32_t stride = e->code_stride ? e->code_stride : e->m;
+  const BangPadRowsLayout l = bang_pad_rows_layout(stride, e->mp);
+  if (e->capacity > 0) return "option capacity";
+  // what the search kernel's hand-over is compiled for (search_has_pad_rows): the 70-chunk layout, its 72 code bytes in front of 128-byte lines
+  if (e->psz == 0 || !l.usable || l.pad_off != e->mp || stride != 128u || !search_has_pad_rows((int)(e->mp / 4u), false))
+    return "the code layout (70-chunk rows -- mp = 72 -- at code_stride = 128 only)";
+  const uint32_t n_pad = bang_pad_rows_count(l, e->N);
+  if (n_pad == 0) return "an index of fewer nodes than a row takes lines";
+  const size_t chunk_rows = std::min<size_t>(n_pad, ((size_t)1 << 30) / 256);
+  uint32_t* d_stage = nullptr;
+  if (hipMalloc((void**)&d_stage, chunk_rows * 256) != hipSuccess) { (void)hipGetLastError(); return "no HBM for the staging buffer"; }
+  const char* no = nullptr;
+  for (size_t r0 = 0; r0 < n_pad && !no; r0 += chunk_rows) {
+    const size_t nr = std::min(chunk_rows, (size_t)n_pad - r0);
+    if (hipMemcpy(d_stage, (const uint8_t*)e->h_adj + r0 * 256, nr * 256, hipMemcpyHostToDevice) != hipSuccess) no = "the copy of the rows to HBM failed";
+    else if (bang_k_pad_rows_scatter(e->d_codes, e->N, stride, e->mp, d_stage, (uint32_t)r0, (uint32_t)nr, nullptr) != BANG_OK) no = "the scatter launch failed";
+    else if (hipDeviceSynchronize() != hipSuccess) no = "the scatter launch failed";
+  }
+  if (no) (void)hipGetLastError();
+  (void)hipFree(d_stage);
+  if (no) return no;
+  e->n_rows_pad = n_pad;
+  if (env_flag("BANG_DEBUG")) fprintf(stderr, "[bang] %u of %u adjacency rows (%.1f GB) in the padding of the code table (%u ids per line, %u lines per row)\n", n_pad, e->N,
+                                      n_pad * 256.0 / 1e9, l.slots, l.lines_per_row);
+  return nullptr;
+}
+
+// Pull mode, after everything else of the index is in place: the code table's padding takes the first adjacency rows (option rows_pad) and HBM the
+// index leaves over takes a copy of the rows behind them.
 // The link is the next limiter of the pull mode (SIFT1B-shape: 47-49 of 57 GB/s): every row that sits in HBM is a PCIe read less.
 static int cache_rows_in_hbm(bang_engine* e) {
-  e->n_rows_hbm = 0;
-  if (!e->pull || !e->h_adj || e->rows_hbm_opt == 0) return BANG_OK;
+  e->n_rows_hbm = 0; e->rows_first = 0; e->n_rows_pad = 0;
+  if (!e->pull || !e->h_adj) {
+    if (e->rows_pad_opt == 1) { bang_set_error("option rows_pad = 1: padded rows belong to the pull mode (graph = host, pull != 0), which this load does not run in"); return BANG_ERR_UNSUPPORTED; }
+    return BANG_OK;
+  }
   size_t free_b = 0, total_b = 0;
   (void)hipMemGetInfo(&free_b, &total_b);
   const size_t keep = (size_t)6 << 30;                                    // per-batch state (filters: 50 KB per query; 0.6 GB at 10 K queries) + slack; a batch
                                                                           // that needs more gets it: bang_alloc drops this copy and retries (bang_cabi.cpp)
-  size_t budget = free_b > keep ? free_b - keep : 0;
+  size_t left = free_b > keep ? free_b - keep : 0;
+  left = std::min(left, (size_t)std::max(0L, env_long("BANG_ROWS_HBM_SPARE_ROWS", 1L << 40)) * 256);      // (test hook: "the rows do not all fit" on a small index)
+  // padded rows -- auto: only where the rows do NOT all fit the HBM the index leaves over (as the copy's auto below).  They are an optimisation: on
+  // auto a failure leaves the engine as it is without them, and only rows_pad = 1 reports it
+  if (e->rows_pad_opt != 0 && !e->rows_pad_dropped && (e->rows_pad_opt == 1 || left / 256 < e->N)) {
+    const char* no = fill_pad_rows(e);
+    if (no && e->rows_pad_opt == 1) { bang_set_error("option rows_pad = 1: the padding of the code table cannot hold adjacency rows here: %s", no); return BANG_ERR_UNSUPPORTED; }
+    if (no && env_flag("BANG_DEBUG")) fprintf(stderr, "[bang] no adjacency rows in the padding of the code table: %s\n", no);
+  }
+  e->rows_first = e->n_rows_pad;                                          // the copy holds the rows behind the padded ones
+  if (e->rows_hbm_opt == 0) return BANG_OK;
+  const size_t rest = (size_t)e->N - e->n_rows_pad;
+  size_t budget = left;
   if (e->rows_hbm_opt > 0) budget = std::min(budget, (size_t)e->rows_hbm_opt << 20);
-  size_t n = std::min<size_t>(e->N, budget / 256);
+  size_t n = std::min<size_t>(rest, budget / 256);
   // auto: only where the rows do NOT all fit -- an index small enough to sit in HBM whole is on the host because the caller put
   // it there (graph = host), and graph = auto would have placed it in HBM anyway
-  if (e->rows_hbm_opt < 0 && n >= e->N) return BANG_OK;
+  // (asked of the whole index: where padded rows were filled the rows did NOT all fit, and the copy takes whatever is left of them)
+  if (e->rows_hbm_opt < 0 && left / 256 >= e->N) return BANG_OK;
   n = std::min<size_t>(n, (size_t)std::max(0L, env_long("BANG_ROWS_HBM_MAX_ROWS", 1L << 40)));      // (test hook: a partial copy of a small index)
   if (n < 64) return BANG_OK;
   if (hipMalloc((void**)&e->d_rows_hbm, n * 256) != hipSuccess) { (void)hipGetLastError(); e->d_rows_hbm = nullptr; return BANG_OK; }
   const size_t step = (size_t)1 << 30;
+  const uint8_t* src = (const uint8_t*)e->h_adj + (size_t)e->rows_first * 256;
   for (size_t off = 0; off < n * 256; off += step)
-    if (hipMemcpy((uint8_t*)e->d_rows_hbm + off, (const uint8_t*)e->h_adj + off, std::min(step, n * 256 - off), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy((uint8_t*)e->d_rows_hbm + off, src + off, std::min(step, n * 256 - off), hipMemcpyHostToDevice) != hipSuccess) {
       (void)hipGetLastError();                             // the copy is an optimisation: without it every row is pulled over PCIe, nothing fails
       dfree(e->d_rows_hbm);
       return BANG_OK;
     }
   e->n_rows_hbm = (uint32_t)n;
-  if (env_flag("BANG_DEBUG")) fprintf(stderr, "[bang] %zu of %u adjacency rows (%.1f GB) also in HBM\n", n, e->N, n * 256 / 1e9);
+  if (env_flag("BANG_DEBUG")) fprintf(stderr, "[bang] %zu of %u adjacency rows (%.1f GB) also in HBM, from row %llu\n", n, e->N, n * 256 / 1e9, (unsigned long long)e->rows_first);
   return BANG_OK;
+}
+
+// padded rows off for the rest of this load (a form that cannot read them was allocated; peer rows): the HBM copy, unless it is out of our hands
+// (exported, or part of a slice table), starts over at row 0
+void drop_pad_rows(bang_engine* e) {
+  if (e->n_rows_pad == 0) return;
+  e->rows_pad_dropped = true;
+  if (e->rows_exported || e->n_slices != 0 || e->rows_first != e->n_rows_pad) { e->n_rows_pad = 0; return; }      // (the copy stays the slice it is)
+  dfree(e->d_rows_hbm);
+  (void)cache_rows_in_hbm(e);            // (rows_pad_dropped: no padded rows; never an error then)
 }
 
 // ---------------------------------------------------------------------------------------------------------------- peer rows
 // (include/bang_c.h: the node's adjacency rows in the node's spare HBM, read over xGMI)
 static const size_t kRowsKeepBack = (size_t)6 << 30;     // HBM left to the per-batch state, as cache_rows_in_hbm does
+
+// peer rows and padded rows do not go together (the slice table knows no padded rows, and a moved slice must not alias them): on auto the padded rows
+// are given up here, forced (rows_pad = 1) the call is refused
+static int peer_rows_without_pad(bang_engine* e, const char* call) {
+  if (e->n_rows_pad == 0) return BANG_OK;
+  if (e->rows_pad_opt == 1) { bang_set_error("%s: peer rows are not available with option rows_pad = 1 (padded rows)", call); return BANG_ERR_UNSUPPORTED; }
+  drop_pad_rows(e);
+  return BANG_OK;
+}
 
 }  // namespace bang
 using namespace bang;
@@ -308,6 +380,12 @@ extern "C" int bang_get_num_nodes(bang_engine_t* e, uint64_t* nodes_out) {
   if (!e || !nodes_out) return BANG_ERR_ARG;
   if (!e->loaded) { bang_set_error("bang_get_num_nodes: no index is loaded"); return BANG_ERR_ARG; }
   *nodes_out = e->N;
+  return BANG_OK;
+}
+
+extern "C" int bang_rows_pad_e(bang_engine_t* e, uint64_t* rows_out) {
+  if (!e || !rows_out) return BANG_ERR_ARG;
+  *rows_out = e->loaded ? e->n_rows_pad : 0;
   return BANG_OK;
 }
 
@@ -328,6 +406,7 @@ extern "C" int bang_rows_slice_e(bang_engine_t* e, uint64_t first_row, uint64_t 
   if (e->allocated) { bang_set_error("peer rows: set the slice before bang_alloc"); return BANG_ERR_ARG; }
   if (e->rows_exported || e->n_slices) { bang_set_error("peer rows: the slice has been exported / the slice table is set: unload first"); return BANG_ERR_ARG; }
   BANG_TRY(ensure_device(e));
+  BANG_TRY(peer_rows_without_pad(e, "bang_rows_slice_e"));
   if (first_row > e->N) first_row = e->N;
   if (rows > e->N - first_row) rows = e->N - first_row;
   dfree(e->d_rows_hbm);
@@ -345,6 +424,7 @@ extern "C" int bang_rows_export_e(bang_engine_t* e, void* handle64, uint64_t* fi
   if (!e || !handle64 || !first_row || !rows) return BANG_ERR_ARG;
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "the handle travels as 64 bytes");
   memset(handle64, 0, 64);
+  if (e->loaded) { BANG_TRY(ensure_device(e)); BANG_TRY(peer_rows_without_pad(e, "bang_rows_export_e")); }
   *first_row = e->rows_first; *rows = e->n_rows_hbm;
   if (!e->d_rows_hbm || e->n_rows_hbm == 0) return BANG_OK;             // nothing to share: the peers read these rows from the host
   BANG_TRY(ensure_device(e));
@@ -362,6 +442,7 @@ extern "C" int bang_rows_import_e(bang_engine_t* e, uint32_t slot, uint32_t n_sl
   if (n_slots == 0 || n_slots > BANG_MAX_ROW_SLICES || slot >= n_slots || slice_rows == 0 || slice_rows > 0xFFFFFFFFull) { bang_set_error("peer rows: bad slot / slice size"); return BANG_ERR_ARG; }
   if (e->n_slices && (e->n_slices != n_slots || e->slice_rows != (uint32_t)slice_rows)) { bang_set_error("peer rows: every slot of one table has the same geometry"); return BANG_ERR_ARG; }
   BANG_TRY(ensure_device(e));
+  BANG_TRY(peer_rows_without_pad(e, "bang_rows_import_e"));
   const uint64_t first = (uint64_t)slot * slice_rows;
   uint64_t base = 0;
   if (!handle64) {                                                         // this engine's own slice
@@ -1016,7 +1097,7 @@ int upload_index(bang_engine* e, const uint8_t* h_codes, const void* d_codes_ext
       return BANG_ERR_ARG;
     }
   }
-  if (e->pull) BANG_TRY(cache_rows_in_hbm(e));
+  BANG_TRY(cache_rows_in_hbm(e));                          // (outside the pull mode: nothing, or the refusal of rows_pad = 1)
   if (e->pull && e->graph_map)
     // nothing reads the mapped graph file while the kernel pulls its rows: let the page cache have the pages back (a later
     // change of the loop form -- "persistent" = 0 -- simply faults them in again)
@@ -1057,6 +1138,7 @@ void unload_index(bang_engine* e) {
   e->n_slices = 0; e->slice_rows = 0; e->own_slot = 0xFFFFFFFFu;
   dfree(e->d_rows_hbm);
   e->n_rows_hbm = 0; e->rows_first = 0; e->rows_exported = false;
+  e->n_rows_pad = 0; e->rows_pad_dropped = false;
   if (e->h_adj) { (void)hipHostUnregister(e->h_adj); (void)munmap(e->h_adj, e->adj_bytes); }
   e->h_adj = nullptr; e->d_adj = nullptr; e->adj_bytes = 0; e->pull = false;
   e->rows_path.clear();

@@ -52,6 +52,12 @@ static const OptionDef kOptions[] = {
     {"rows_hbm", "BANG_ROWS_HBM", &bang_engine::rows_hbm_opt, -1, 1 << 22, INT, BEFORE_LOAD,
      "pull mode: MB of HBM for a copy of the first adjacency rows, read from there instead of over PCIe (-1 = auto: what the index leaves beyond 6 GB, "
      "where the rows do not all fit; 0 = none)"},
+    {"rows_pad", "BANG_ROWS_PAD", &bang_engine::rows_pad_opt, -1, 1, INT, BEFORE_LOAD,
+     "pull mode, 70-chunk code rows 128 bytes apart: the bytes of a code line behind the code hold adjacency ids (14 per line), so the rows of the first N / 5 nodes "
+     "sit in HBM without a byte allocated and the rows_hbm copy holds the rows behind them.  Read by the self-paced PQ search kernel (bang_k_search, bang_k_search_wf) "
+     "alone.  -1 = auto: filled at load where the rows do not all fit HBM, given up at bang_alloc where another form runs; 0 = off; 1 = forced: a load or an allocation "
+     "that cannot use them is refused (other code layouts, option capacity, walker = 1 / the host-paced and per-iteration forms, distance = 1, peer rows).  "
+     "A caller's code table (bang_index_desc.d_codes) is WRITTEN to, bytes 72..127 of each line: 0 keeps the engine out of it"},
     // ---- loop shape: consumed by bang_alloc
     {"lanes", "BANG_LANES", &bang_engine::lanes_opt, 0, BANG_MAX_LANES, INT, BEFORE_ALLOC, "launch-per-iteration loop: independent query groups pipelined against each other (0 = auto)"},
     {"threads", "BANG_THREADS", &bang_engine::threads_opt, 0, 4096, INT, BEFORE_ALLOC, "host walker threads per lane (0 = auto from the CPU quota)"},
@@ -111,6 +117,7 @@ struct SwitchDef { const char* env; const char* help; };
 static const SwitchDef kSwitches[] = {
     {"BANG_PULL_ROWS_DIR", "directory (tmpfs) every rank of a node can see: ONE pull-rows file per index there, built by the first rank to load, mapped by the others"},
     {"BANG_PULL_ROWS_INTERLEAVE", "0 = leave the pages of a shared pull-rows file where first touch puts them (default 1: interleaved over the NUMA nodes)"},
+    {"BANG_ROWS_HBM_SPARE_ROWS", "test hook: the HBM the index leaves over counts as holding at most this many adjacency rows (what rows_hbm = auto and rows_pad = auto decide by)"},
     {"BANG_ROWS_HBM_MAX_ROWS", "test hook: cap on the adjacency rows copied to HBM (a partial copy of a small index)"},
     {"BANG_INSERT_SEARCH_CHUNK", "test hook: points per search + prune launch of an insert, clamped to [1, 1024] (default 1024)"},
     {"BANG_INSERT_TARGET_CHUNK", "test hook: back-edge targets per launch of an insert, clamped to [1, 8192] (default 8192)"},

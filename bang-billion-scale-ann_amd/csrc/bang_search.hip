@@ -51,6 +51,7 @@
 #include "bang_device.h"
 #include "bang_worklist.h"
 #include "bang_search_args.h"
+#include "bang_pad_rows.h"
 
 // BANG_SEARCH_INMEM (Makefile: bang_search_inmem.o / bang_search_inmem_b.o, BANG_SEARCH_PART 2 / 3): the same kernel under another name
 // (search_inmem_kernel), self-paced instances only, with the parent rule and the iteration cap of the reference's BANG_Inmemory variant
@@ -350,6 +351,11 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
   // together with their filter probes, one memory latency earlier; the distances of the ids the filter then drops are computed and thrown
   // away (every lane runs the reduce anyway), the survivors' are compacted behind it.  Same distances for the same ids: same results.
   static_assert(!SPEC || !HOST, "the speculative row request belongs to the self-paced form");
+  // padded rows: the hand-over of the long-row self-paced instances for dword-aligned code rows reads them (a stride of 128 is one); every other instance
+  // is the code it was, and the host side refuses n_rows_pad there
+  constexpr bool PAD_ROWS = search_has_pad_rows(NDW, HOST) && ALIGNED && !BANG_SEARCH_INMEM;
+  constexpr BangPadRowsLayout PAD_LAYOUT = bang_pad_rows_layout(128u, 4u * NDW);       // (lines of 128 bytes, the instance's 4 NDW code bytes in front)
+  static_assert(!PAD_ROWS || (PAD_LAYOUT.usable && PAD_LAYOUT.pad_off == 4u * NDW), "padded rows: the instance's layout");
 
   const uint32_t code_stride = p.code_stride ? p.code_stride : p.m;
 
@@ -788,14 +794,37 @@ __global__ __launch_bounds__(search_maxt(NDW, HOST)) void search_kernel(const Se
           // the rows of the first n_rows_hbm nodes also sit in HBM (whatever HBM the index left over): no PCIe read for those.  Peer rows
           // (n_slices > 1): slice parent / slice_rows of the node's HBM-resident rows -- this GPU's HBM or a peer's over xGMI; the table
           // holds biased base addresses (0: that slice is not there), read through the scalar cache
-          const uint32_t GAS* hb = nullptr;
-          const uint32_t nsl = IA32(IA_N_SLICES);
-          if (nsl > 1u) {
-            const uint32_t sl = parent / IA32(IA_SLICE_ROWS);                      // (uniform: scalar)
-            if (sl < nsl) hb = (const uint32_t GAS*)scalar_load_u64(IA64(IA_ROW_SLICES), sl);
-          } else if (parent < IA32(IA_N_ROWS_HBM)) hb = IAPTR(const uint32_t, IA_ROWS_HBM);
-          if (hb) x0 = hb[(uint64_t)parent * 64u + lane];        // (plain: with the non-temporal hint on the rows read from HBM the 10 K batch took 8.22 instead of 7.96 ms)
-          else x0 = __builtin_nontemporal_load((const uint32_t GAS*)gbase + (uint64_t)parent * 64u + lane);
+          if constexpr (!PAD_ROWS) {
+            const uint32_t GAS* hb = nullptr;
+            const uint32_t nsl = IA32(IA_N_SLICES);
+            if (nsl > 1u) {
+              const uint32_t sl = parent / IA32(IA_SLICE_ROWS);                      // (uniform: scalar)
+              if (sl < nsl) hb = (const uint32_t GAS*)scalar_load_u64(IA64(IA_ROW_SLICES), sl);
+            } else if (parent < IA32(IA_N_ROWS_HBM)) hb = IAPTR(const uint32_t, IA_ROWS_HBM);
+            if (hb) x0 = hb[(uint64_t)parent * 64u + lane];        // (plain: with the non-temporal hint on the rows read from HBM the 10 K batch took 8.22 instead of 7.96 ms)
+            else x0 = __builtin_nontemporal_load((const uint32_t GAS*)gbase + (uint64_t)parent * 64u + lane);
+          } else {
+            // Padded rows (the long-row instances; option rows_pad, bang_pad_rows.h; never together with peer rows): the rows of the nodes [0, n_pad) sit
+            // in the code table itself, in the bytes of its 128-byte lines behind the code -- lane i's id in line parent * lines_per_row + i / slots --
+            // and the HBM copy holds the rows of the nodes behind them, [n_pad, n_pad + n_rows_hbm).  A plain load, like the copy's.  The row's first
+            // byte is uniform (scalar registers); the lane's offset from it is made here, from the lane number, and lives no longer than the load
+            const uint8_t GAS* rb = nullptr;
+            uint32_t lo = (uint32_t)lane * 4u;
+            const uint32_t nsl = IA32(IA_N_SLICES);
+            const uint32_t npad = IA32(IA_N_PAD);
+            if (nsl > 1u) {
+              const uint32_t sl = parent / IA32(IA_SLICE_ROWS);                      // (uniform: scalar)
+              if (sl < nsl) {
+                const uint8_t GAS* hb = (const uint8_t GAS*)scalar_load_u64(IA64(IA_ROW_SLICES), sl);
+                if (hb) rb = hb + (uint64_t)parent * 256u;
+              }
+            } else if (parent < npad) {
+              rb = IAPTR(const uint8_t, IA_CODES) + (uint64_t)parent * (PAD_LAYOUT.lines_per_row * 128u);
+              lo = (uint32_t)bang_pad_row_byte(PAD_LAYOUT, 128u, 0u, (uint32_t)lane);
+            } else if (parent - npad < IA32(IA_N_ROWS_HBM)) rb = IAPTR(const uint8_t, IA_ROWS_HBM) + (uint64_t)(parent - npad) * 256u;
+            if (rb) x0 = *(const uint32_t GAS*)(rb + lo);
+            else x0 = __builtin_nontemporal_load((const uint32_t GAS*)(gbase + (uint64_t)parent * 256u + lo));
+          }
           cnt_in = 64u;                                      // counted when the row is consumed
         } else {
           const uint32_t GAS* nrow = (const uint32_t GAS*)(gbase + (uint64_t)parent * IA64(IA_ENTRY_LEN) + IA32(IA_VEC_BYTES));

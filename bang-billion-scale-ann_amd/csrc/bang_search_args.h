@@ -51,12 +51,12 @@ struct IterArgs {
   uint32_t vec_bytes, row_layout, n_rows_hbm, n_slices;                                         // 10, 11, 12, 13
   const uint32_t* d_rows_hbm; const uint64_t* d_row_slices;                                     // 14-15, 16-17
   uint32_t slice_rows, summ_iters;                                                              // 18, 19
-  uint32_t* d_bloom; uint32_t cap_iter, pad1;                                                   // 20-21, 22, 23
+  uint32_t* d_bloom; uint32_t cap_iter, n_pad;                                                   // 20-21, 22, 23
 };
 enum { IA_CODES = 0, IA_N_NODES = 2, IA_PRIO = 3, IA_CAND_IDS = 4, IA_GRAPH = 6, IA_ENTRY_LEN = 8, IA_VEC_BYTES = 10, IA_ROW_LAYOUT = 11, IA_N_ROWS_HBM = 12,
-       IA_N_SLICES = 13, IA_ROWS_HBM = 14, IA_ROW_SLICES = 16, IA_SLICE_ROWS = 18, IA_SUMM_ITERS = 19, IA_BLOOM = 20, IA_CAP_ITER = 22, IA_DWORDS = 24 };
+       IA_N_SLICES = 13, IA_ROWS_HBM = 14, IA_ROW_SLICES = 16, IA_SLICE_ROWS = 18, IA_SUMM_ITERS = 19, IA_BLOOM = 20, IA_CAP_ITER = 22, IA_N_PAD = 23, IA_DWORDS = 24 };
 static_assert(sizeof(IterArgs) == 4 * IA_DWORDS && offsetof(IterArgs, d_cand_ids) == 4 * IA_CAND_IDS && offsetof(IterArgs, vec_bytes) == 4 * IA_VEC_BYTES &&
-              offsetof(IterArgs, d_rows_hbm) == 4 * IA_ROWS_HBM && offsetof(IterArgs, slice_rows) == 4 * IA_SLICE_ROWS && offsetof(IterArgs, d_bloom) == 4 * IA_BLOOM && offsetof(IterArgs, cap_iter) == 4 * IA_CAP_ITER,
+              offsetof(IterArgs, d_rows_hbm) == 4 * IA_ROWS_HBM && offsetof(IterArgs, slice_rows) == 4 * IA_SLICE_ROWS && offsetof(IterArgs, d_bloom) == 4 * IA_BLOOM && offsetof(IterArgs, cap_iter) == 4 * IA_CAP_ITER && offsetof(IterArgs, n_pad) == 4 * IA_N_PAD,
               "IterArgs dword map");
 struct SearchArgs {
   bang_search_params p;
@@ -75,6 +75,10 @@ BANG_HD constexpr bool search_coop(int ndw, bool host_paced) { return ndw >= 12 
 // self-paced instances with the speculative row request (SPEC) exist for the long-row layouts of the BASELINE configs (70 / 74 chunks: 168-VGPR
 // instances); the 128-VGPR instance of the 32-chunk layout measured 2-5 % slower with it
 BANG_HD constexpr bool search_has_spec(int ndw) { return ndw == 18 || ndw == 19; }
+// The instances whose hand-over reads adjacency rows kept in the code table's padding (option rows_pad, bang_pad_rows.h; n_pad of IterArgs): the
+// self-paced instances of the 70-chunk layout for dword-aligned rows, at a code stride of 128 bytes.  The 74-chunk instances pay for the same branch
+// with 72-112 B of scratch per lane (profiles/rows_pad.md) and stay, like every other instance, the code they were without the option
+BANG_HD constexpr bool search_has_pad_rows(int ndw, bool host_paced) { return !host_paced && ndw == 18; }
 
 // MAXT: threads per workgroup the instance is compiled for -- 1024 (16 waves, 128 VGPRs each) or, for the instances of the long code
 // rows (>= 64 chunks), 768 (12 waves, 168 VGPRs each).  Build switch BANG_LONG_MAXT=1024: the self-paced long-row instances as 16-wave

@@ -8,6 +8,7 @@
 #include "bang_c.h"
 #include "bang_internal.h"
 #include "bang_search_args.h"
+#include "bang_pad_rows.h"
 
 static const uint32_t kWaveLanes = 64;
 namespace bang { const char* env_str(const char* name); }      // bang_options.cpp: environment switches are read when they are used
@@ -204,6 +205,18 @@ static int search_setup(const bang_search_params* p, bool inmem, SearchArgs* out
       bang_set_error("fused re-rank: bad arguments / unsupported vector layout"); return BANG_ERR_ARG;
     }
   }
+  if (p->n_rows_pad != 0u) {
+    // padded rows: only the instances of search_has_pad_rows read them, at the layout their hand-over is compiled for; the last padded row ends inside the table
+    const BangPadRowsLayout pl = bang_pad_rows_layout(p->code_stride, p->mp);
+    const char* no = inmem ? "semantics = 1" : !p->d_graph ? "the host-paced form" : p->row_layout != 1u ? "row_layout != 1" : p->n_slices > 1u ? "peer rows (n_slices > 1)"
+                   : !search_has_pad_rows((int)(p->mp / 4u), false) ? "this PQ layout (rows read as 72 chunks -- 65 to 72 of at most 2 dims -- only)"
+                   : (p->code_stride != 128u || !pl.usable || pl.pad_off != p->mp) ? "this code_stride (128 only)" : nullptr;
+    if (no) { bang_set_error("n_rows_pad = %u (option rows_pad): padded rows cannot be read with %s", p->n_rows_pad, no); return BANG_ERR_ARG; }
+    if (p->n_rows_pad > bang_pad_rows_count(pl, p->n_nodes)) {
+      bang_set_error("n_rows_pad = %u (option rows_pad) exceeds the %u rows the padding of n_nodes = %u code lines holds", p->n_rows_pad, bang_pad_rows_count(pl, p->n_nodes), p->n_nodes);
+      return BANG_ERR_ARG;
+    }
+  }
   SearchArgs& a = *out;
   a.p = *p;
   a.lds_piv_floats = pivot_table_floats(p->psz, p->mp, p->pq_nhi);
@@ -211,7 +224,7 @@ static int search_setup(const bang_search_params* p, bool inmem, SearchArgs* out
   a.iter.d_codes = p->d_codes; a.iter.n_nodes = p->n_nodes; a.iter.d_cand_ids = p->d_cand_ids; a.iter.d_graph = p->d_graph; a.iter.entry_len = p->entry_len;
   a.iter.vec_bytes = p->vec_bytes; a.iter.row_layout = p->row_layout; a.iter.n_rows_hbm = p->n_rows_hbm; a.iter.n_slices = p->n_slices;
   a.iter.d_rows_hbm = p->d_rows_hbm; a.iter.d_row_slices = p->d_row_slices; a.iter.slice_rows = p->slice_rows;
-  a.iter.d_bloom = p->d_bloom; a.iter.cap_iter = p->cap_iter;      // (summ_iters: below, once the policy is resolved)
+  a.iter.d_bloom = p->d_bloom; a.iter.cap_iter = p->cap_iter; a.iter.n_pad = p->n_rows_pad;      // (summ_iters: below, once the policy is resolved)
   uint32_t grid_n = 0, waves = 0, nctx = p->nctx, gs = p->group_waves;
   const int rc = bang_search_geometry(p->psz, p->mp, p->pq_nhi, p->L, p->Q, p->max_wgs, p->max_waves, p->d_graph ? 0 : 1, &grid_n, &waves, &nctx, &gs);
   if (rc != BANG_OK) return rc;

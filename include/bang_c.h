@@ -90,7 +90,9 @@ typedef struct {
   uint32_t D, R, N, m;
   const uint8_t* graph;      /* N * entry_len bytes */
   const uint8_t* codes;      /* N * m bytes (host) -- or NULL when d_codes is given */
-  const void* d_codes;       /* optional: codes already on the device (N*m + 256 bytes; N*code_stride + 256 with code_stride != 0) */
+  const void* d_codes;       /* optional: codes already on the device (N*m + 256 bytes; N*code_stride + 256 with code_stride != 0).  The engine reads the
+                                first m bytes of a row -- and, pull mode with option "rows_pad" != 0 (auto included), a 72-chunk pivot layout (m = 65..72, chunks of at most 2 dims) and code_stride = 128,
+                                WRITES adjacency ids into the bytes 72..127 of each row, which hold no code: set rows_pad = 0 to keep it out of them */
   const float* pivots;       /* [256][D] */
   const float* centroid;     /* [D] */
   const uint32_t* chunk_off; /* [m+1] */
@@ -136,6 +138,11 @@ int bang_get_rows_hash(bang_engine_t* e, uint64_t* out);
  * W = 4, all of them at W = 8.  Call order: load -> slice -> export / (exchange handles) / import -> bang_alloc.  Results never change.
  * bang_rows_slice_e replaces the default copy (rows [0, auto)); rows = 0 drops it.  A slice that has been exported is never freed before
  * bang_unload (bang_alloc does not take it back when HBM is short: BANG_ERR_NOMEM instead). */
+/* PADDED ROWS (option "rows_pad"): adjacency rows of the nodes [0, *rows_out) of the loaded index that sit in the padding of its PQ code table and are
+ * read there by the self-paced PQ search kernel; the HBM row copy holds the rows behind them.  0: none (option off, another code layout, the rows all
+ * fit HBM, given up for a form that cannot read them).  Peer rows and padded rows exclude each other: with rows_pad = -1 (auto) bang_rows_slice_e, _export_e and _import_e give
+ * the padded rows up, with rows_pad = 1 they are refused. */
+int bang_rows_pad_e(bang_engine_t* e, uint64_t* rows_out);
 #define BANG_MAX_ROW_SLICES 16
 int bang_get_num_nodes(bang_engine_t* e, uint64_t* nodes_out);    /* N of the loaded index (the reference reads it from <p>_disk_metadata.bin, bang_search.cu:176-189) */
 int bang_rows_capacity_e(bang_engine_t* e, uint64_t* rows_out);   /* rows of 256 B this engine's free HBM holds now (6 GB kept back for the batch state) + what its row copy holds */
@@ -578,6 +585,12 @@ typedef struct {
                                           requested together with their filter probes (1) -- one memory latency less per iteration, the rows of the ids the
                                           filter drops fetched in vain -- or behind the filter, survivors only (2); 0 = auto: 1 where the rows are pulled (row_layout), and
                                           for launches of <= 8 queries per CU where the graph is in HBM. */
+  uint32_t n_rows_pad;                 /* padded rows (engine option "rows_pad"; bang_k_search / bang_k_search_wf, self-paced form, row_layout = 1, n_slices <= 1, the
+                                          70-chunk layout -- mp = 72 -- at code_stride = 128): the adjacency rows of the nodes [0, n_rows_pad) sit in d_codes itself,
+                                          in the bytes of its lines behind the code (csrc/bang_pad_rows.h: 14 ids per line, 5 lines per row, 5 * n_rows_pad <=
+                                          n_nodes), and d_rows_hbm holds the rows of the nodes [n_rows_pad, n_rows_pad + n_rows_hbm).  Non-zero anywhere else is
+                                          BANG_ERR_ARG naming the member; the other entry points ignore it.  (It takes the four bytes of padding that lay between
+                                          spec_rows and the pointer below: no member moves, sizeof is what it was, and a caller zeroes the struct before filling it.) */
   /* K6 + K7 FUSED into the launch (self-paced form, 8-bit vectors; compute_L2Dist :1254-1299, compute_NearestNeighbours :1312-1368): the wave
    * that finishes a query re-ranks its candidate log on the spot -- exact distances to the full-precision vectors at rr_vec_base + id *
    * rr_vec_stride, stable rank by (distance, expansion order) -- and writes the query's k results; no second launch behind the search, and
