@@ -143,6 +143,14 @@ class ConsolidateClearParams(C.Structure):
                 ("n_nodes", C.c_uint32), ("medoid", C.c_uint32), ("d_excluded", C.c_void_p)]
 
 
+class ScanParams(C.Structure):
+    """bang_scan_params (include/bang_c.h): device addresses."""
+    _fields_ = [("d_vec_base", C.c_void_p), ("vec_stride", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("n_nodes", C.c_uint32),
+                ("d_queries", C.c_void_p), ("nq", C.c_uint32), ("k", C.c_uint32), ("d_excluded", C.c_void_p), ("d_removed", C.c_void_p),
+                ("d_labels", C.c_void_p), ("d_filters", C.c_void_p), ("stripes", C.c_uint32), ("d_scratch", C.c_void_p),
+                ("scratch_bytes", C.c_uint64), ("d_ids_out", C.c_void_p), ("d_dists_out", C.c_void_p), ("d_matched", C.c_void_p)]
+
+
 class PruneParams(C.Structure):
     """bang_prune_params (include/bang_c.h): device addresses."""
     _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("n_nodes", C.c_uint32),
@@ -628,6 +636,47 @@ class Engine:
         ms = (C.c_double * 4)()
         _check(lib().bang_get_consolidate_times(self._h, ms), "bang_get_consolidate_times")
         return dict(zip(("scan", "rows", "clear", "total"), (float(x) for x in ms)))
+
+    # ---- exact scan (bang_scan_e)
+    def scan(self, queries: np.ndarray, k: int, any=None, all=None):
+        """bang_scan_e: the k nearest of EVERY live point -- not excluded, not removed by a consolidation of this load, matching the query's
+        {any, all} filter if filters are given -- by brute force, in the distance bits the search returns; equal distances in id order.
+        Returns (ids [Q][k] u64, dists [k][Q] f32, matched [Q] u32: the candidates of each query); short answers are padded with
+        UINT64_MAX / 3.402823E+38.  With or without a live allocation."""
+        q = np.ascontiguousarray(queries, dtype=NP_DTYPE[self.dtype])
+        if q.ndim != 2:
+            raise BangError(f"scan: queries must be [Q][D] (got shape {q.shape})")
+        Q = q.shape[0]
+        words = []
+        for name, w in (("any", any), ("all", all)):
+            if w is None:
+                words.append(None)
+                continue
+            w = np.asarray(w).reshape(-1)
+            if w.dtype.kind not in "iu" or (w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF)):
+                raise BangError(f"scan: `{name}` must be 32-bit integer words")
+            if w.size != Q:
+                raise BangError(f"scan: {w.size} `{name}` words for {Q} queries")
+            words.append(np.ascontiguousarray(w, dtype=np.uint32))
+        kk = max(int(k), 0)
+        ids = np.empty((Q, kk), dtype=np.uint64)
+        dists = np.empty((kk, Q), dtype=np.float32)
+        matched = np.zeros(Q, dtype=np.uint32)
+        fn = lib().bang_scan_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        spare = np.zeros(2, dtype=np.uint64)              # an empty array still hands over an address: the library names what is wrong (k = 0, nq = 0)
+        _check(fn(self._h, _vp(q) if q.size else _vp(spare), Q, kk, None if words[0] is None else _vp(words[0]),
+                  None if words[1] is None else _vp(words[1]), _vp(ids) if ids.size else _vp(spare), _vp(dists) if dists.size else _vp(spare),
+                  _vp(matched) if Q else None), "bang_scan")
+        return ids, dists, matched
+
+    def scan_times(self) -> dict:
+        """bang_get_scan_times: milliseconds of the last scan -- the scan launches and the merge of the stripes' lists (GPU time), the whole call."""
+        ms = (C.c_double * 3)()
+        fn = lib().bang_get_scan_times
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        _check(fn(self._h, ms), "bang_get_scan_times")
+        return dict(zip(("scan", "merge", "total"), ms))
 
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the

@@ -343,6 +343,7 @@ extern "C" int bang_destroy(bang_engine_t* e) {
   if (e->allocated) free_batch(e);
   drop_excluded(e);
   drop_labels(e);
+  dfree(e->d_removed);
   if (e->loaded) unload_index(e);
   delete e;
   return BANG_OK;
@@ -783,7 +784,7 @@ extern "C" int bang_free_e(bang_engine_t* e) {
 extern "C" int bang_unload_e(bang_engine_t* e) {
   if (!e) return BANG_ERR_ARG;
   if (e->allocated) free_batch(e);
-  if (e->loaded) { (void)hipSetDevice(e->device); drop_excluded(e); drop_labels(e); unload_index(e); }
+  if (e->loaded) { (void)hipSetDevice(e->device); drop_excluded(e); drop_labels(e); dfree(e->d_removed); unload_index(e); }
   return BANG_OK;
 }
 

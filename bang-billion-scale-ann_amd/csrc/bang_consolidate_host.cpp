@@ -4,7 +4,7 @@
 //   bang_k_consolidate_scan, the affected bitmap down, bang_consolidate_group (no HIP call), the list up
 //   per chunk of <= 8192 affected nodes: bang_k_consolidate_gather -> bang_k_range_sort -> bang_k_prune (the insert's back-edge sequence and
 //   its scratch sizes)
-//   bang_k_consolidate_clear, the seed list, the exclusion bitmap
+//   bang_k_consolidate_clear, the seed list, bang_k_bitmap_or (the removed nodes into d_removed), the exclusion bitmap
 #include "bang_engine.h"
 
 #include <cmath>
@@ -115,8 +115,16 @@ int consolidate(bang_engine* e, float alpha2, uint64_t st[4]) {
   BANG_TRY(rebuild_seed(e));
   uint32_t dropped = 0;
   HIP_TRY(hipMemcpy(&dropped, d_ctl + 1, 4, hipMemcpyDeviceToHost));
+  const size_t nodes_cap = std::max<size_t>(N, e->capacity > 0 ? (size_t)e->capacity : 0);
+  const size_t excl_words = (nodes_cap + 31) / 32 + 1;
+  // the removed set D = X \ {med} joins d_removed (what an exact scan leaves out: the removed nodes keep their vectors) before X is reduced
+  if (!e->d_removed) {
+    BANG_TRY(dmalloc(&e->d_removed, excl_words));
+    HIP_TRY(hipMemset(e->d_removed, 0, excl_words * 4));
+  }
+  BANG_TRY(bang_k_bitmap_or(e->d_removed, e->d_excl, excl_words, med >> 5, 1u << (med & 31u), s));
+  HIP_TRY(hipStreamSynchronize(s));
   if (med_excluded) {
-    const size_t nodes_cap = std::max<size_t>(N, e->capacity > 0 ? (size_t)e->capacity : 0);
     const uint32_t bit = 1u << (med & 31u);
     HIP_TRY(hipMemset(e->d_excl, 0, ((nodes_cap + 31) / 32 + 1) * 4));
     HIP_TRY(hipMemcpy(e->d_excl + (med >> 5), &bit, 4, hipMemcpyHostToDevice));

@@ -8,6 +8,8 @@
 //   bang_cabi.cpp     the engine-level C-ABI of include/bang_c.h
 //   bang_insert_host.cpp  bang_insert_e: the launches of an insert (option capacity), the entry / code downloads; bang_insert_group.cpp: its
 //                     host-side grouping of the new rows by target (no HIP call, no engine)
+//   bang_scan_engine.cpp  bang_scan_e: the launches of an exact scan over the live points, chunked; bang_scan_host.cpp: bang_k_scan's checks, grid
+//                     and scratch size (no HIP call, no engine)
 //   bang_consolidate_host.cpp  bang_consolidate_e: the launches that fold the exclusion set into the graph; bang_consolidate_group.cpp: the
 //                     affected bitmap as a list of ids (no HIP call, no engine)
 #ifndef BANG_ENGINE_H_
@@ -347,6 +349,9 @@ struct bang_engine {
   double insert_ms[6] = {0, 0, 0, 0, 0, 0};   // the last bang_insert_e: {search, prune, rows down + host grouping, back-edges, encode} on the stream / host, the whole call
   // consolidation (bang_consolidate_e)
   uint64_t stat_cons_rows = 0, stat_cons_removed = 0, stat_cons_dropped = 0;   // bang_stats_ext6: totals since the load
+  uint32_t* d_removed = nullptr;       // bitmap, the shape of d_excl: the nodes consolidations of this load removed (X \ {med} ORed in where X is emptied); read by
+                                       // bang_scan_e alone, dropped by bang_unload_e, not persisted; NULL = nothing was removed
+  double scan_ms[3] = {0, 0, 0};       // the last bang_scan_e: {scan launches, merge} GPU time, the whole call (host)
   double consolidate_ms[4] = {0, 0, 0, 0};    // the last bang_consolidate_e: {scan + list, gather / sort / prune, clear + seed, the whole call}, host wall time
 };
 

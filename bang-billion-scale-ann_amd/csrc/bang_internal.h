@@ -108,6 +108,9 @@ int bang_k_search_exact_range_pull(const bang_search_params* p, const bang_range
 // run (bang_set_query_filters_e); no-op without the variable.  The file is read once per allocation
 int bang_apply_query_filter_file_e(bang_engine_t* e, int num_queries);
 
+// bang_k_scan with a HIP event (hipEvent_t, or NULL) recorded between the scan launch and the merge of the stripes' lists (bang_scan_e's times)
+int bang_k_scan_marked(const bang_scan_params* p, void* stream, void* ev_merge);
+
 #ifdef __cplusplus
 }
 #endif

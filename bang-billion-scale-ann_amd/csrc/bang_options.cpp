@@ -123,6 +123,8 @@ static const SwitchDef kSwitches[] = {
     {"BANG_INSERT_TARGET_CHUNK", "test hook: back-edge targets per launch of an insert, clamped to [1, 8192] (default 8192)"},
     {"BANG_INSERT_ENCODE_CHUNK", "test hook: points per table launch of an insert's PQ encode, clamped to [1, 256] (default 256)"},
     {"BANG_CONSOLIDATE_CHUNK", "test hook: affected nodes per gather / sort / prune launch of a consolidation, clamped to [1, 8192] (default 8192)"},
+    {"BANG_SCAN_STRIPES", "test hook: stripes of the points per launch of an exact scan, clamped to [1, the largest a launch accepts] (default: bang_scan_geometry's choice)"},
+    {"BANG_SCAN_QUERY_CHUNK", "test hook: queries per launch of an exact scan, clamped to [1, 4096] (default 4096)"},
     {"BANG_STREAM_LOAD", "0 = bang_load maps <prefix>_disk.bin up front instead of streaming it through (pull mode)"},
     {"BANG_GRAPH_MMAP", "0 = private copy of the graph file (transparent huge pages) instead of a shared read-only mapping"},
     {"BANG_EXCLUDE_FILE", ".bin file (i32 count, i32 1, count u32 ids) of node ids no query returns: read as the last step of every load (bang_set_excluded_e)"},

@@ -285,7 +285,9 @@ int bang_get_codes_e(bang_engine_t* e, uint64_t first, uint64_t n, void* out);
  * finite or outside [1, 8] (BANG_ERR_ARG); MIPS search parameters; a layout outside bang_search_can_rerank (BANG_ERR_UNSUPPORTED).  A label table
  * may stay set.  An empty exclusion set is BANG_OK with zero statistics and writes nothing.  A row that lists an id >= N: the id is never
  * dereferenced, the call returns BANG_ERR_IO and names the step.  A call that fails before the rows of D are cleared leaves a graph that every
- * walk may run on -- rewritten rows list live nodes only, the others nodes that still exist -- and the exclusion set untouched. */
+ * walk may run on -- rewritten rows list live nodes only, the others nodes that still exist -- and the exclusion set untouched.
+ * The nodes of D are also ORed into the engine's REMOVED bitmap (the shape of the exclusion bitmap), which bang_scan_e alone reads -- the removed
+ * nodes keep their vectors, and X no longer names them -- and bang_unload_e drops; it is not part of an index file. */
 int bang_consolidate_e(bang_engine_t* e, float alpha, uint64_t* out_stats4);
 int bang_unload_e(bang_engine_t* e);                                                        /* bang.h:82 */
 
@@ -958,6 +960,59 @@ int bang_k_consolidate_clear(const bang_consolidate_clear_params* p, void* strea
  * bitmap holds ceil(n_nodes / 32) words; bits of the last word at or behind n_nodes are ignored.  ids holds up to n_nodes words.  BANG_ERR_ARG
  * (no message) on a null argument. */
 int bang_consolidate_group(const uint32_t* bitmap, uint32_t n_nodes, uint32_t* ids, uint32_t* n_ids);
+
+/* EXACT SCAN (csrc/bang_scan.hip, bang_scan_host.cpp, bang_scan_engine.cpp; DESIGN.md section 2 CANON 23, section 4.17): the k nearest of EVERY
+ * live point, by brute force.  The CANDIDATES of query q are the node ids x < N that are not in the exclusion set, were not removed by a
+ * consolidation of this load and match q's filter by the rule of bang_set_query_filters_e (any = all = 0, or any == all == NULL: every node).
+ * A candidate's distance is the exact one of the narrow layouts (8-bit: the integer as a float; float: the ascending fmaf chain); the answer is the
+ * k smallest keys (distance bits << 32) | id, ascending -- equal distances in id order --, whatever the tiling; ids_out [nq][k] u64 and
+ * dists_out [k][nq] f32 as bang_query_e's, a short answer padded with UINT64_MAX / 3.402823E+38f; matched_out[q] (may be NULL) = the number of
+ * candidates.  The call reads the engine's tables only, allocates and frees its own scratch and runs with or without a live allocation; batches
+ * are cut into chunks inside.  Vectors come from the graph entries in HBM or, host placement, from the packed vector table.
+ * Refused before any HIP call, nothing written: a null engine, nothing loaded, null queries / outputs, nq = 0 or > BANG_SCAN_MAX_QUERIES, k = 0 or
+ * > BANG_SCAN_MAX_K, exactly one of any / all, filters without a label table, float queries that bang_check_floats refuses (BANG_ERR_ARG); MIPS
+ * search parameters, an fp16 vector table, no resident vectors, a layout outside bang_search_can_rerank (BANG_ERR_UNSUPPORTED).
+ * The removed set is not part of an index file: a reloaded index is scanned with its removed nodes. */
+#define BANG_SCAN_MAX_K 128u
+#define BANG_SCAN_MAX_QUERIES (1u << 20)
+#define BANG_SCAN_MAX_KEYS 4096u              /* stripes * k: what bang_k_range_sort merges per query */
+int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq, uint32_t k, const uint32_t* any, const uint32_t* all, uint64_t* ids_out,
+                float* dists_out, uint32_t* matched_out);
+int bang_get_scan_times(bang_engine_t* e, double* ms3);        /* the last bang_scan_e: scan launches, merge (GPU time), the whole call (host) */
+/* Kernel level: device pointers only, every argument checked before any HIP call with the member named.  Workgroups take a tile of queries (32 for
+ * 8-bit vectors, on the i8 MFMA; 16 for float vectors) and one of `stripes` stripes of the points [0, n_nodes); each (query, stripe) leaves at most
+ * k keys in d_scratch, bang_k_range_sort merges a query's stripes and a last kernel writes the outputs.  stripes = 0: bang_scan_geometry's choice;
+ * else 1 <= stripes, stripes * k <= BANG_SCAN_MAX_KEYS and stripes <= ceil(n_nodes / points per round) (128 for 8-bit, 256 for float vectors).
+ * d_excluded / d_removed: bitmaps of ceil(n_nodes / 32) words or NULL; d_labels [n_nodes] with d_filters [nq][2] {any, all}, or both NULL.
+ * d_scratch: bang_scan_scratch_bytes(nq, k, stripes) bytes, 8-byte aligned.  vec_stride % 4 == 0 holds the vector; layouts as
+ * bang_search_can_rerank (others: BANG_ERR_UNSUPPORTED). */
+typedef struct {
+  const uint8_t* d_vec_base;   /* vector of node x at d_vec_base + x * vec_stride */
+  uint64_t vec_stride;
+  uint32_t dtype, D, n_nodes;
+  const void* d_queries;       /* [nq][D] */
+  uint32_t nq, k;
+  const uint32_t* d_excluded;
+  const uint32_t* d_removed;
+  const uint32_t* d_labels;
+  const uint32_t* d_filters;
+  uint32_t stripes;
+  void* d_scratch;
+  uint64_t scratch_bytes;
+  uint64_t* d_ids_out;         /* [nq][k] */
+  float* d_dists_out;          /* [k][nq] */
+  uint32_t* d_matched;         /* [nq] */
+} bang_scan_params;
+int bang_k_scan(const bang_scan_params* p, void* stream);
+/* Host side, no HIP call in it (csrc/bang_scan_host.cpp): the grid of a scan -- query tiles and the default number of stripes (BANG_ERR_ARG on a
+ * zero or null argument, BANG_ERR_UNSUPPORTED on a layout outside bang_search_can_rerank) --, the largest `stripes` a launch accepts (0 where
+ * none), the scratch a launch needs, and bang_k_scan's argument checks on their own */
+int bang_scan_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes);
+uint32_t bang_scan_max_stripes(int dtype, uint32_t n_nodes, uint32_t k);
+uint64_t bang_scan_scratch_bytes(uint32_t nq, uint32_t k, uint32_t stripes);
+int bang_scan_check(const bang_scan_params* p);
+/* dst[w] |= src[w] for w < words, except the bits skip_mask of word skip_word (bang_consolidate_e: the removed set, without the medoid) */
+int bang_k_bitmap_or(uint32_t* d_dst, const uint32_t* d_src, uint64_t words, uint64_t skip_word, uint32_t skip_mask, void* stream);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
