@@ -637,6 +637,54 @@ class Engine:
         _check(lib().bang_get_consolidate_times(self._h, ms), "bang_get_consolidate_times")
         return dict(zip(("scan", "rows", "clear", "total"), (float(x) for x in ms)))
 
+    # ---- re-use of removed ids (bang_insert_reuse_e, bang_get_removed_e, bang_set_removed_e)
+    def insert_reuse(self, vectors: np.ndarray, L_build: int, alpha: float = 1.2) -> np.ndarray:
+        """bang_insert_reuse_e: add the rows of `vectors` as ONE batch, at the ids of removed nodes that are not excluded again (lowest first)
+        and, when those run out, behind N -> uint64 [n], the ids in input order (strictly ascending).  Needs what insert needs; capacity == N
+        is enough for a batch that fits its free slots."""
+        v = np.ascontiguousarray(vectors, dtype=NP_DTYPE[self.dtype])
+        if v.ndim != 2:
+            raise BangError(f"insert_reuse: vectors must be [n][D] (got shape {v.shape})")
+        ids = np.zeros(max(v.shape[0], 1), np.uint64)
+        fn = lib().bang_insert_reuse_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
+        _check(fn(self._h, _vp(v) if v.size else None, C.c_uint32(v.shape[0]), C.c_uint32(int(L_build)), C.c_float(alpha), _vp(ids)), "bang_insert_reuse")
+        return ids[:v.shape[0]]
+
+    def free_slots(self) -> dict:
+        """bang_get_free_slots_e -> dict(free: removed nodes, eligible: those not excluded again, reused: slots handed out since the load)"""
+        out = (C.c_uint64 * 3)()
+        fn = lib().bang_get_free_slots_e
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        _check(fn(self._h, out), "bang_get_free_slots")
+        return dict(zip(("free", "eligible", "reused"), (int(x) for x in out)))
+
+    def removed_ids(self) -> np.ndarray:
+        """bang_get_removed_e -> uint32, ascending: the nodes consolidations removed and no insert_reuse has taken since (formats.write_removed
+        persists them beside an export)."""
+        fn = lib().bang_get_removed_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        n = C.c_uint64(0)
+        _check(fn(self._h, None, C.c_uint64(0), C.byref(n)), "bang_get_removed")
+        out = np.zeros(int(n.value), np.uint32)
+        if out.size:
+            _check(fn(self._h, _vp(out), C.c_uint64(out.size), C.byref(n)), "bang_get_removed")
+        return out[:int(n.value)]
+
+    def set_removed(self, ids):
+        """bang_set_removed_e: REPLACE the set of removed nodes (an empty one clears it) -- after loading an exported index, with the ids
+        formats.read_removed returns.  Refused (BangError, the old set stays) unless every id is a node other than the medoid whose row is empty
+        and that no other node's row names."""
+        a = np.asarray(ids).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise BangError(f"set_removed: ids must be integers (got {a.dtype})")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise BangError(f"set_removed: an id is out of range for a node id ({int(a.min())} .. {int(a.max())})")
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        fn = lib().bang_set_removed_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        _check(fn(self._h, _vp(a) if a.size else None, C.c_uint64(a.size)), "bang_set_removed")
+
     # ---- exact scan (bang_scan_e)
     def scan(self, queries: np.ndarray, k: int, any=None, all=None):
         """bang_scan_e: the k nearest of EVERY live point -- not excluded, not removed by a consolidation of this load, matching the query's

@@ -199,6 +199,38 @@ def read_index(prefix: str, dtype: str, mmap_graph: bool = False) -> Index:
                  codes=codes, pivots=pivots, centroid=centroid, chunk_off=chunk_off)
 
 
+REMOVED_SUFFIX = "_removed.bin"
+
+
+def write_removed(prefix: str, ids) -> None:
+    """`<prefix>_removed.bin`: the ids of the removed nodes (Engine.removed_ids) beside an exported index, in the .bin layout {u32 count, u32 1,
+    u32 ids}, ascending and distinct.  A sidecar: write_index / read_index and the four index files do not know it; a caller loads the index and
+    then hands read_removed's ids to Engine.set_removed."""
+    a = np.asarray(ids).reshape(-1)
+    if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        raise ValueError(f"write_removed: ids must be 32-bit node ids (got {a.dtype})")
+    a = np.unique(a.astype(np.uint32))
+    os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+    with open(prefix + REMOVED_SUFFIX, "wb") as f:
+        f.write(struct.pack("<II", a.size, 1))
+        f.write(a.tobytes())
+
+
+def read_removed(prefix: str) -> np.ndarray:
+    """-> uint32 [count]; an index without the sidecar has no removed node: an empty array"""
+    path = prefix + REMOVED_SUFFIX
+    if not os.path.exists(path):
+        return np.zeros(0, np.uint32)
+    with open(path, "rb") as f:
+        n, d = struct.unpack("<II", f.read(8))
+        if d != 1:
+            raise ValueError(f"{path}: {d} columns, expected 1")
+        a = np.frombuffer(f.read(), dtype=np.uint32)
+    if a.size != n:
+        raise ValueError(f"{path}: the header names {n} ids, the file holds {a.size}")
+    return a.copy()
+
+
 def write_bin(path: str, data: np.ndarray) -> None:
     """{i32 n, i32 D, T[n][D]} -- query files, base files."""
     n, d = data.shape

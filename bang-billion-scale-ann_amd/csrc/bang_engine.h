@@ -12,6 +12,8 @@
 //                     and scratch size (no HIP call, no engine)
 //   bang_consolidate_host.cpp  bang_consolidate_e: the launches that fold the exclusion set into the graph; bang_consolidate_group.cpp: the
 //                     affected bitmap as a list of ids (no HIP call, no engine)
+//   bang_reuse_host.cpp  bang_insert_reuse_e: an insert that takes the ids of removed nodes first; the removed set out and in (bang_get_removed_e,
+//                     bang_set_removed_e); bang_reuse_group.cpp: the assignment of ids and the grouping by explicit source ids (no HIP call, no engine)
 #ifndef BANG_ENGINE_H_
 #define BANG_ENGINE_H_
 
@@ -350,7 +352,9 @@ struct bang_engine {
   // consolidation (bang_consolidate_e)
   uint64_t stat_cons_rows = 0, stat_cons_removed = 0, stat_cons_dropped = 0;   // bang_stats_ext6: totals since the load
   uint32_t* d_removed = nullptr;       // bitmap, the shape of d_excl: the nodes consolidations of this load removed (X \ {med} ORed in where X is emptied); read by
-                                       // bang_scan_e alone, dropped by bang_unload_e, not persisted; NULL = nothing was removed
+                                       // bang_scan_e and bang_insert_reuse_e (the free slots), dropped by bang_unload_e, handed out and taken back by
+                                       // bang_get_removed_e / bang_set_removed_e; NULL = nothing is removed
+  uint64_t stat_reused = 0;            // bang_get_free_slots_e: removed ids that bang_insert_reuse_e handed out again, since the load
   double scan_ms[3] = {0, 0, 0};       // the last bang_scan_e: {scan launches, merge} GPU time, the whole call (host)
   double consolidate_ms[4] = {0, 0, 0, 0};    // the last bang_consolidate_e: {scan + list, gather / sort / prune, clear + seed, the whole call}, host wall time
 };

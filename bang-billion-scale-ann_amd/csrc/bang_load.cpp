@@ -1153,6 +1153,7 @@ void unload_index(bang_engine* e) {
   e->insert_broken = false;
   e->stat_inserted = e->stat_be_appended = e->stat_be_pruned = e->stat_be_dropped = 0;
   e->stat_cons_rows = e->stat_cons_removed = e->stat_cons_dropped = 0;
+  e->stat_reused = 0;
   e->graph_mode = e->graph_opt;
 }
 // ---- file loading (bang_search.cu:138-362) ----

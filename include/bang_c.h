@@ -287,8 +287,31 @@ int bang_get_codes_e(bang_engine_t* e, uint64_t first, uint64_t n, void* out);
  * dereferenced, the call returns BANG_ERR_IO and names the step.  A call that fails before the rows of D are cleared leaves a graph that every
  * walk may run on -- rewritten rows list live nodes only, the others nodes that still exist -- and the exclusion set untouched.
  * The nodes of D are also ORed into the engine's REMOVED bitmap (the shape of the exclusion bitmap), which bang_scan_e alone reads -- the removed
- * nodes keep their vectors, and X no longer names them -- and bang_unload_e drops; it is not part of an index file. */
+ * nodes keep their vectors, and X no longer names them --, bang_insert_reuse_e hands out again and bang_unload_e drops; it is not part of an index
+ * file (bang_get_removed_e / bang_set_removed_e carry it across an export). */
 int bang_consolidate_e(bang_engine_t* e, float alpha, uint64_t* out_stats4);
+/* REUSE OF REMOVED IDS (DESIGN.md section 2 CANON 24, section 4.18).  F = the nodes x < N whose bit is set in the removed bitmap, X the exclusion
+ * set at the call, E = F \ X the eligible free slots.  bang_insert_reuse_e adds the n vectors as ONE batch like bang_insert_e, at the ids
+ * ids[i] = the i-th smallest element of E for i < f = min(n, |E|) and N + (i - f) behind: strictly ascending in input order, written to
+ * ids_out[n].  Everything else is bang_insert_e with "N + i" read as ids[i]: the searches run on the graph as it stood (n_nodes = N; no walk
+ * reaches a node of F), entry and code row go to slot ids[i], back-edge targets are old live nodes.  Last, and only after the last kernel
+ * succeeded, the removed bits of ids[0 .. f) are cleared and N grows by n - f.  With F empty (or f = 0) the bytes are bang_insert_e's.
+ * Refused with "bang_insert_reuse" in the message and no side effect: every refusal of bang_insert_e, with N + (n - f) > capacity in the place
+ * of N + n > capacity (a batch that fits its free slots succeeds at capacity == N), and ids_out NULL.  A new row that lists an id of the batch
+ * is BANG_ERR_IO.  A failure before the back-edge step leaves N, the bitmap and every reachable row as they were (the overwritten slots are
+ * still free); behind it the engine refuses further inserts as bang_insert_e does.  bang_insert_e itself never consults F.
+ * bang_get_insert_times reports the last call of either kind: here [2] also holds the select of E, the upload of the entries to their slots and
+ * the download of the new rows, [4] the copy of the code rows to their slots.
+ * bang_get_free_slots_e: out3 = {|F|, |E|, slots reused since the load}.
+ * bang_get_removed_e: the ids of F ascending into ids_out (room for cap ids; BANG_ERR_ARG if |F| > cap), *count = |F|; ids_out NULL: the count alone.
+ * bang_set_removed_e REPLACES F by the n ids (n = 0 clears it): what a caller persists beside an exported index (formats.write_removed) and
+ * restores after a load.  Needs the graph in HBM and no live allocation.  Checked on the GPU before anything changes: every id is < N and not
+ * the medoid, its row has degree 0, and no row of a node outside the list names a listed id; else BANG_ERR_ARG, the message names the first
+ * offending id, and the old F stays. */
+int bang_insert_reuse_e(bang_engine_t* e, const void* h_vectors, uint32_t n, uint32_t L_build, float alpha, uint64_t* ids_out);
+int bang_get_free_slots_e(bang_engine_t* e, uint64_t* out3);
+int bang_get_removed_e(bang_engine_t* e, uint32_t* ids_out, uint64_t cap, uint64_t* count);
+int bang_set_removed_e(bang_engine_t* e, const uint32_t* ids, uint64_t n);
 int bang_unload_e(bang_engine_t* e);                                                        /* bang.h:82 */
 
 /* statistics of the last bang_query_e */
@@ -972,7 +995,7 @@ int bang_consolidate_group(const uint32_t* bitmap, uint32_t n_nodes, uint32_t* i
  * Refused before any HIP call, nothing written: a null engine, nothing loaded, null queries / outputs, nq = 0 or > BANG_SCAN_MAX_QUERIES, k = 0 or
  * > BANG_SCAN_MAX_K, exactly one of any / all, filters without a label table, float queries that bang_check_floats refuses (BANG_ERR_ARG); MIPS
  * search parameters, an fp16 vector table, no resident vectors, a layout outside bang_search_can_rerank (BANG_ERR_UNSUPPORTED).
- * The removed set is not part of an index file: a reloaded index is scanned with its removed nodes. */
+ * The removed set is not part of an index file: a reloaded index is scanned with its removed nodes until bang_set_removed_e restores the set. */
 #define BANG_SCAN_MAX_K 128u
 #define BANG_SCAN_MAX_QUERIES (1u << 20)
 #define BANG_SCAN_MAX_KEYS 4096u              /* stripes * k: what bang_k_range_sort merges per query */
@@ -1013,6 +1036,40 @@ uint64_t bang_scan_scratch_bytes(uint32_t nq, uint32_t k, uint32_t stripes);
 int bang_scan_check(const bang_scan_params* p);
 /* dst[w] |= src[w] for w < words, except the bits skip_mask of word skip_word (bang_consolidate_e: the removed set, without the medoid) */
 int bang_k_bitmap_or(uint32_t* d_dst, const uint32_t* d_src, uint64_t words, uint64_t skip_word, uint32_t skip_mask, void* stream);
+
+/* REUSE OF REMOVED IDS, device side (csrc/bang_reuse.hip; engine: bang_insert_reuse_e, bang_set_removed_e; DESIGN.md section 2 CANON 24, section
+ * 4.18).  Every entry checks its arguments before any HIP call and names the offending one.
+ *
+ * bang_k_bitmap_select: d_ids_out receives the min(want, total) lowest set bit positions of a & ~not below n_bits (1 .. 2^32 - 2), ascending;
+ * *d_total the number of all such bits.  d_not may be NULL; both bitmaps hold ceil(n_bits / 32) words, bits of the last word at or behind n_bits
+ * are ignored.  Nothing is written behind d_ids_out[min(want, total)]; want = 0 only counts (d_ids_out may be NULL).  The result is a function
+ * of the bitmaps alone (no atomic decides a position).  d_scratch: bang_bitmap_select_scratch_words(n_bits) words, one per span of
+ * BANG_SELECT_SPAN_BITS bits (a workgroup's share). */
+#define BANG_SELECT_SPAN_BITS 32768u
+uint64_t bang_bitmap_select_scratch_words(uint32_t n_bits);
+int bang_k_bitmap_select(const uint32_t* d_a, const uint32_t* d_not, uint32_t n_bits, uint32_t want, uint32_t* d_ids_out, uint32_t* d_total,
+                         uint32_t* d_scratch, void* stream);
+/* bang_k_copy_rows_by_id: `bytes` bytes between row d_ids[i] of a strided table (d_table + id * table_stride + byte_offset) and row i of a packed
+ * buffer (d_packed + i * packed_stride), i < n, one wave per row; to_table != 0 writes the table, else the packed buffer.  16-byte pieces where
+ * bases, strides and offset are all divisible by 16, dwords where by 4, bytes otherwise (and for what is left of a row).  An id >= n_nodes is
+ * skipped, never dereferenced, and *d_abort = 2 (d_abort may be NULL).  On the write side the ids must be distinct. */
+int bang_k_copy_rows_by_id(void* d_table, uint64_t table_stride, uint64_t byte_offset, const uint32_t* d_ids, uint32_t n, uint32_t n_nodes,
+                           void* d_packed, uint64_t packed_stride, uint32_t bytes, int to_table, uint32_t* d_abort, void* stream);
+/* bit d_ids[i] of d_bitmap (ceil(n_bits / 32) words) cleared / set for every i < n, one atomic AND / OR each; an id >= n_bits is skipped */
+int bang_k_bitmap_clear_ids(uint32_t* d_bitmap, uint32_t n_bits, const uint32_t* d_ids, uint64_t n, void* stream);
+int bang_k_bitmap_set_ids(uint32_t* d_bitmap, uint32_t n_bits, const uint32_t* d_ids, uint64_t n, void* stream);
+/* bang_k_rows_check: *d_first (SET TO 0xFFFFFFFF BY THE CALLER) becomes the lowest i < n whose d_ids[i] is >= n_nodes, is `medoid`, or names a
+ * node whose degree word (d_graph + id * entry_len + byte_offset) is not 0; it stays 0xFFFFFFFF where there is none. */
+int bang_k_rows_check(const uint8_t* d_graph, uint64_t entry_len, uint64_t byte_offset, const uint32_t* d_ids, uint64_t n, uint32_t n_nodes,
+                      uint32_t medoid, uint32_t* d_first, void* stream);
+/* Host side, no HIP call in it (csrc/bang_reuse_group.cpp).  bang_reuse_assign: the ids of a batch of n points from the n_free eligible free
+ * slots (strictly ascending, each < N): f = min(n, n_free), ids_out[i] = free_ids[i] for i < f, N + (i - f) behind; *appended_out = n - f.
+ * bang_insert_group_ids: bang_insert_group with explicit source ids -- row i belongs to node ids[i]; ids strictly ascending.  BANG_ERR_ARG (no
+ * message) on a null argument, ids that are not strictly ascending (free_ids likewise, or one >= N), row_stride < 2, a degree > R, a listed
+ * id >= n_old, or a row that lists an id of the batch. */
+int bang_reuse_assign(const uint32_t* free_ids, uint32_t n_free, uint32_t n, uint32_t N, uint32_t* ids_out, uint32_t* appended_out);
+int bang_insert_group_ids(const uint32_t* rows, uint32_t n, uint32_t row_stride, const uint32_t* ids, uint32_t n_old, uint32_t* targets,
+                          uint32_t* offs, uint32_t* srcs, uint32_t* n_targets);
 
 /* 1 if bang_k_search_exact (engine option "distance" = 1) evaluates vectors of this layout, else 0: float vectors with D % 4 == 0, 8-bit vectors
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
