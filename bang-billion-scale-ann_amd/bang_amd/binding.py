@@ -239,6 +239,12 @@ def device_count() -> int:
     return int(lib().bang_device_count())
 
 
+def host_register_supported() -> bool:
+    """bang_host_register_supported: the engine's own answer -- True: the pull rows are a registered mapping (hipHostRegister); False (virtual
+    machines): they are allocated pinned, and an engine reads a pinned copy of a rows file, so nothing written to the file afterwards reaches it."""
+    return bool(lib().bang_host_register_supported())
+
+
 def _vp(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 

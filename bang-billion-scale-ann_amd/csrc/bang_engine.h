@@ -276,7 +276,8 @@ struct bang_engine {
   bool pull = false;                   // resolved at load
   uint32_t* h_adj = nullptr;           // [N][64]
   size_t adj_bytes = 0;
-  std::string rows_path;               // the rows file the mapping h_adj belongs to ("" = anonymous memory): re-checked at bang_alloc
+  bool adj_pinned = false;             // h_adj is pinned memory of its own (hipHostMalloc), not a registered mapping of the rows file
+  std::string rows_path;               // the rows file the mapping h_adj belongs to ("" = memory of the engine's own): re-checked at bang_alloc
   std::string rows_key;                // names the shared rows file (BANG_PULL_ROWS_DIR): basename of the index prefix
   // STREAMED load: the graph entries pass through in chunks (vectors -> HBM, adjacency -> pull rows) and are not kept
   bang_entry_source entry_fn = nullptr;   // set for the duration of a streamed load

@@ -83,17 +83,34 @@ static inline void pull_row_from_entry(const bang_engine* e, uint32_t* row, cons
 // Pull mode: the adjacency lists of the host graph, re-laid as 256-byte rows the GPU can fetch with one PCIe read each.
 // One copy per NODE when BANG_PULL_ROWS_DIR names a directory every rank can see (tmpfs): the rows live in the file
 // <dir>/<index name>_pull_rows.bin, built by whichever rank loads first (write to a temporary name, rename) and mapped shared by
-// the others; every rank registers the mapping with its own device.  Without the variable: private anonymous memory.
+// the others; every rank registers the mapping with its own device.  Without the variable: private anonymous memory, registered.
+// Where the platform registers no memory the process already has (hipHostRegister fails: virtual machines; host_register_works), the rows
+// are ALLOCATED pinned (hipHostMalloc), and a rank keeps the rows of a rows file in a pinned copy of its own -- the file still spares the
+// next rank the index, not the memory.
+static bool host_register_works() {
+  static const bool works = []() {
+    void* m = mmap(nullptr, 1 << 16, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+    if (m == MAP_FAILED) return false;
+    const bool ok = hipHostRegister(m, 1 << 16, hipHostRegisterMapped | hipHostRegisterPortable) == hipSuccess;
+    if (ok) (void)hipHostUnregister(m); else (void)hipGetLastError();
+    (void)munmap(m, 1 << 16);
+    return ok;
+  }();
+  return works;
+}
 struct PullRows {
   void* m = MAP_FAILED;
   size_t bytes = 0, sig_off = 0;
   bool fill = true;                    // false: an existing rows file was mapped (its signature is checked in pull_rows_finish)
   bool keep_stale = false;             // a mapped file with another signature is left alone (shared load: it is another rank's)
+  bool pinned = false;                 // m is hipHostMalloc memory, not a mapping
   std::string path, tmp;
 };
+static const unsigned kPinnedRowsFlags = hipHostMallocMapped | hipHostMallocPortable;
 static void pull_rows_abandon(PullRows& pr) {
-  if (pr.m != MAP_FAILED) (void)munmap(pr.m, pr.bytes);
+  if (pr.m != MAP_FAILED) { if (pr.pinned) (void)hipHostFree(pr.m); else (void)munmap(pr.m, pr.bytes); }
   pr.m = MAP_FAILED;
+  pr.pinned = false;
   if (!pr.tmp.empty()) (void)unlink(pr.tmp.c_str());
   pr.tmp.clear();
 }
@@ -142,10 +159,21 @@ static int pull_rows_open(bang_engine* e, PullRows& pr, const PullRowsSig* expec
       if (pr.m == MAP_FAILED) { (void)unlink(pr.tmp.c_str()); pr.tmp.clear(); }
     } else pr.tmp.clear();
   }
-  if (pr.m == MAP_FAILED) {
+  if (pr.m == MAP_FAILED && host_register_works()) {
     pr.m = mmap(nullptr, pr.bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
     if (pr.m == MAP_FAILED) { bang_set_error("pull rows: cannot map %.1f GB of host memory", pr.bytes / 1e9); return BANG_ERR_NOMEM; }
     (void)madvise(pr.m, pr.bytes, MADV_HUGEPAGE);
+    pr.tmp.clear();
+  }
+  if (pr.m == MAP_FAILED) {                         // no registering here: allocated pinned
+    void* p = nullptr;
+    if (hipHostMalloc(&p, pr.bytes, kPinnedRowsFlags) != hipSuccess) {
+      (void)hipGetLastError();
+      bang_set_error("pull rows: cannot allocate %.1f GB of pinned host memory", pr.bytes / 1e9);
+      return BANG_ERR_NOMEM;
+    }
+    pr.m = p;
+    pr.pinned = true;
     pr.tmp.clear();
   }
   // ONE rows file serves every GPU of the node: its pages are spread over the NUMA nodes page by page (first touch would place
@@ -166,7 +194,35 @@ static int pull_rows_open(bang_engine* e, PullRows& pr, const PullRowsSig* expec
   }
   return BANG_OK;
 }
-// the rows are complete: signature written (built here) or checked (mapped), file published, mapping registered with the device
+// the mapped rows file moves into pinned memory of this rank (the file stays as it is, for the ranks to come)
+static int pull_rows_pin_copy(PullRows& pr) {
+  const size_t avail = host_bytes_available();
+  if (pr.bytes + ((size_t)8 << 30) > avail) {
+    bang_set_error("pull rows: a pinned copy of %.1f GB does not fit the %.1f GB of host memory left", pr.bytes / 1e9, avail / 1e9);
+    return BANG_ERR_NOMEM;
+  }
+  void* p = nullptr;
+  if (hipHostMalloc(&p, pr.bytes, kPinnedRowsFlags) != hipSuccess) {
+    (void)hipGetLastError();
+    bang_set_error("pull rows: cannot allocate %.1f GB of pinned host memory", pr.bytes / 1e9);
+    return BANG_ERR_NOMEM;
+  }
+  const int T = std::max(1, std::min(16, usable_cpus()));
+  const uint8_t* src = (const uint8_t*)pr.m;
+  const size_t bytes = pr.bytes;
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; ++t)
+    th.emplace_back([=]() {
+      const size_t a = bytes / T * t, z = t + 1 == T ? bytes : bytes / T * (t + 1);
+      memcpy((uint8_t*)p + a, src + a, z - a);
+    });
+  for (auto& x : th) x.join();
+  (void)munmap(pr.m, pr.bytes);
+  pr.m = p;
+  pr.pinned = true;
+  return BANG_OK;
+}
+// the rows are complete: signature written (built here) or checked (mapped), file published, rows pinned for the device
 static int pull_rows_finish(bang_engine* e, PullRows& pr, const PullRowsSig& sig) {
   if (pr.fill) {
     memset((uint8_t*)pr.m + (size_t)e->N * 256, 0xFF, 4096);
@@ -179,7 +235,11 @@ static int pull_rows_finish(bang_engine* e, PullRows& pr, const PullRowsSig& sig
     bang_set_error("pull rows: %s belonged to another index", pr.path.c_str());
     return BANG_ERR_STALE_ROWS;
   }
-  if (hipHostRegister(pr.m, pr.bytes, hipHostRegisterMapped | hipHostRegisterPortable) != hipSuccess) {
+  if (!pr.pinned && !host_register_works()) {              // (a mapped rows file where nothing can be registered: a pinned copy of its rows)
+    const int rc = pull_rows_pin_copy(pr);
+    if (rc != BANG_OK) { pull_rows_abandon(pr); return rc; }
+  }
+  if (!pr.pinned && hipHostRegister(pr.m, pr.bytes, hipHostRegisterMapped | hipHostRegisterPortable) != hipSuccess) {
     (void)hipGetLastError();
     pull_rows_abandon(pr);
     bang_set_error("pull rows: hipHostRegister of %.1f GB failed", pr.bytes / 1e9);
@@ -188,14 +248,14 @@ static int pull_rows_finish(bang_engine* e, PullRows& pr, const PullRowsSig& sig
   void* dp = nullptr;
   if (hipHostGetDevicePointer(&dp, pr.m, 0) != hipSuccess) {
     (void)hipGetLastError();
-    (void)hipHostUnregister(pr.m);
+    if (!pr.pinned) (void)hipHostUnregister(pr.m);
     pull_rows_abandon(pr);
-    bang_set_error("pull rows: no device address for the registered rows");
+    bang_set_error("pull rows: no device address for the pinned rows");
     return BANG_ERR_HIP;
   }
-  e->h_adj = (uint32_t*)pr.m; e->adj_bytes = pr.bytes; e->d_adj = (const uint32_t*)dp; e->pull = true;
+  e->h_adj = (uint32_t*)pr.m; e->adj_bytes = pr.bytes; e->adj_pinned = pr.pinned; e->d_adj = (const uint32_t*)dp; e->pull = true;
   e->rows_hash = sig.adj_hash;
-  e->rows_path = pr.path;
+  e->rows_path = pr.pinned ? std::string() : pr.path;      // (a pinned copy no longer depends on the file)
   pr.m = MAP_FAILED;
   return BANG_OK;
 }
@@ -375,6 +435,8 @@ static int peer_rows_without_pad(bang_engine* e, const char* call) {
 
 }  // namespace bang
 using namespace bang;
+
+extern "C" int bang_host_register_supported(void) { return host_register_works() ? 1 : 0; }
 
 extern "C" int bang_get_num_nodes(bang_engine_t* e, uint64_t* nodes_out) {
   if (!e || !nodes_out) return BANG_ERR_ARG;
@@ -1139,8 +1201,11 @@ void unload_index(bang_engine* e) {
   dfree(e->d_rows_hbm);
   e->n_rows_hbm = 0; e->rows_first = 0; e->rows_exported = false;
   e->n_rows_pad = 0; e->rows_pad_dropped = false;
-  if (e->h_adj) { (void)hipHostUnregister(e->h_adj); (void)munmap(e->h_adj, e->adj_bytes); }
-  e->h_adj = nullptr; e->d_adj = nullptr; e->adj_bytes = 0; e->pull = false;
+  if (e->h_adj) {
+    if (e->adj_pinned) (void)hipHostFree(e->h_adj);
+    else { (void)hipHostUnregister(e->h_adj); (void)munmap(e->h_adj, e->adj_bytes); }
+  }
+  e->h_adj = nullptr; e->d_adj = nullptr; e->adj_bytes = 0; e->adj_pinned = false; e->pull = false;
   e->rows_path.clear();
   e->graph_path.clear(); e->graph_streamed = false; e->entry_fn = nullptr; e->entry_ctx = nullptr;
   e->rows_key.clear();

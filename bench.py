@@ -2,8 +2,14 @@
 """bench.py -- queries/sec @ 10-recall@10 >= 0.9 on a 10K-query batch (BASELINE.json metric), the roofline of the search
 kernel and of the PQ-distance stage (K2) alone, and the CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sift1b_shape|sift1m|sift10m|deep100m_shape|small|tiny]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--workload sift1b_shape|sift1m|sift10m|deep100m_shape|small|tiny]
                     [--graph host|device|auto] [--pull -1|0|1] [--batches B] [--no-legs] [--legs k2,sift1m,...] [--dump-outputs DIR]
+
+A plain run measures the headline figure and nothing else: the primary configuration is built, loaded, timed and checked, `roofline` comes
+from the timed launches themselves (roofline.traffic: quoted from the committed PMC passes where those are of the same index, else left
+out with a note), `config.side_measurements` says what was left out, and the line is printed.  `--full` adds the side
+measurements described below -- the live PMC passes, the legs and the CPU baseline, minutes of work that `value` does not depend on;
+`--legs LIST` is a full run restricted to the legs of LIST.
 
 One process per GPU.  `--gpus N` IS the rank count: under a launcher (torchrun sets RANK / LOCAL_RANK / WORLD_SIZE) WORLD_SIZE must equal N;
 without one, N > 1 makes this process start its N ranks itself (tools/bench_legs/launch.py: fresh children before anything touches the GPU,
@@ -16,7 +22,7 @@ rank 0's line relayed, the children's status returned); fewer visible devices th
   PCIe.  N is scaled to what the box's host memory holds (stated in config.workload).  `value`, `config`, `roofline` (that launch +
   `k2_alone` at m = 70) and `cpu_baseline` (the oracle on the same layout at reduced N, where the HIP engine is also checked
   against it) all belong to this configuration.
-* N = 1 also carries LEGS (tools/bench_legs/), as nested objects `config.at_*` and -- because the driver's record keeps scalars only --
+* N = 1 with --full also carries LEGS (tools/bench_legs/), as nested objects `config.at_*` and -- because the driver's record keeps scalars only --
   flattened into `config.<leg>_qps`, `_recall`, `_L`, `_frac` ...  On the primary engine (ONE load of the 1e9-point index): `shards`
   (Q / 2, Q / 4, Q / 8 queries of the batch = one rank's shard of a 2 / 4 / 8-GPU job, the world-size-1 RCCL gather, and the projected
   speed-ups WITH the gather) and `walker` (the north-star data flow: C++ walker threads serve the host-paced kernel from the same
@@ -33,7 +39,7 @@ A "step" = one bang_query over the whole batch.  bang_init (visited-filter / wor
 exactly as in the reference harness (BANG_Base/test_driver.cpp:432-439); the init-inclusive rate is reported beside it.  Every
 step is bracketed by barrier + cuda.synchronize on both sides and the MAX over ranks is taken.
 
-roofline.traffic (N = 1, default run): HBM bytes per launch of the search kernel, measured by two child runs of the primary
+roofline.traffic (N = 1, --full): HBM bytes per launch of the search kernel, measured by two child runs of the primary
 configuration under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE: separate passes) before this process touches the GPU -- live_traffic().
 """
 import argparse
@@ -119,6 +125,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: the live PMC passes (roofline.traffic), the legs and the CPU baseline.  Without it "
+                         "(and without --legs) the run measures the headline figure only")
     ap.add_argument("--workload", default="sift1b_shape", choices=sorted(WORKLOADS) + ["sift1b_shape", "deep100m_shape"],
                     help="default: sift1b_shape = BASELINE.json configs[3] / [4], the configuration the target number is quoted on")
     ap.add_argument("--shape-n", type=int, default=0, help="override N of a *_shape workload")
@@ -139,12 +148,12 @@ def main():
     ap.add_argument("--host-codes", action="store_true",
                     help="shape-only workloads: generate the PQ codes in HOST memory too (resident graph image, N must fit) so that the "
                          "oracle can check the results -- parity runs of the sharded job at reduced N")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the side measurements (other configs, K2 alone)")
-    ap.add_argument("--legs", default="", help="comma list of legs to run (default: shards,walker,ceiling,k2,sift300m,sift1m,deep100m,sift10m; on request: sift100m, sift1b)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the side measurements (other configs, K2 alone)")
+    ap.add_argument("--legs", default="", help="comma list of legs to run; implies --full (default of --full: shards,walker,ceiling,k2,sift300m,sift1m,deep100m,sift10m; on request: sift100m, sift1b)")
     ap.add_argument("--leg-budget-s", type=float, default=600.0,
                     help="a leg is skipped (and listed in config.legs_skipped) once the run -- counted from the start of the process -- has "
-                         "taken this long: the default run stays within minutes")
+                         "taken this long: the full run stays within minutes")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend (nccl = RCCL over xGMI; gloo only for dry runs of the N>1 logic)")
     ap.add_argument("--no-events", action="store_true", help="do not stamp the launches of the timed steps")
@@ -155,6 +164,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.legs:
+        args.full = True
+    if not args.full:                                    # the headline figure only: no leg, no profiled child run, no CPU baseline
+        args.no_legs = args.no_live_traffic = args.no_cpu_baseline = True
 
     # --gpus N is the rank count, whoever starts the ranks (tools/bench_legs/launch.py).  Without a launcher and N > 1 this process starts the N
     # ranks itself -- before it or anything it imported has touched the GPU --, relays rank 0's line and exits with their status; with a launcher
@@ -284,8 +297,12 @@ def main():
         shape_only = not prim["structured"]
         # (the driver's record keeps ~120 characters of a string: the facts first)
         metric = (f"queries/sec, 10K-query batch; SHAPE-ONLY index, L={L}, {agg['iterations']} iterations/query (cap-bound), recall n/a; recall-gated: "
-                  "config.recall_gated_* (structured index, 10-recall@10 >= 0.9). A shape-only batch is heavier per query than real data at recall 0.9"
+                  + ("config.recall_gated_*" if args.full else "run with --full (config.recall_gated_*)") +
+                  " (structured index, 10-recall@10 >= 0.9). A shape-only batch is heavier per query than real data at recall 0.9"
                   if shape_only else "queries/sec @ 10-recall@10 >= 0.9, 10K-query batch")
+        # what this run left out, in the record itself: a plain run carries no leg, no live PMC pass and no CPU baseline
+        cfg["side_measurements"] = ("full" if args.full else
+                                    "none (plain run: --full adds roofline.traffic measured live, the legs -- recall_gated_*, shards, walker ... -- and cpu_baseline)")
         out = {"metric": metric, "value": res["queries_per_s"], "unit": "queries/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
                "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": ARITH_DTYPE,

@@ -58,6 +58,9 @@ typedef struct bang_engine bang_engine_t;
 
 const char* bang_last_error(void);          /* thread-local message of the last failure */
 int bang_device_count(void);                /* 0 if no HIP device */
+int bang_host_register_supported(void);     /* 1: the HIP runtime pins memory the process already has (hipHostRegister) and the pull rows are a
+                                               registered mapping; 0 (virtual machines): they are allocated pinned (hipHostMalloc), a rows file
+                                               (BANG_PULL_ROWS_DIR) copied into such an allocation per engine.  Asked of the runtime once per process */
 
 int bang_create(int dtype, bang_engine_t** out);             /* BANGSearch<T>() bang.h:42 */
 int bang_destroy(bang_engine_t* e);                          /* ~BANGSearch()   bang.h:43 */

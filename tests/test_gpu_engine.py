@@ -441,7 +441,10 @@ def test_pull_form_failures_are_reported_not_faults(libbang, small_u8, tmp_path,
     truncated between bang_load and bang_alloc is refused at bang_alloc."""
     import os
     import bang_amd
+    from bang_amd import binding
     from oracle import oracle as O
+    if not binding.host_register_supported():           # (the engine then reads a pinned copy of the rows: nothing written to the file reaches it)
+        pytest.skip("hipHostRegister is not supported here: the rows file's mapping cannot be registered with the GPU")
     monkeypatch.setenv("BANG_PULL_ROWS_DIR", str(tmp_path))
     ix, q, _, _ = small_u8
     ids_o, dists_o = O.Oracle(ix).search(q, 10, 40)
@@ -477,6 +480,42 @@ def test_pull_form_failures_are_reported_not_faults(libbang, small_u8, tmp_path,
         with pytest.raises(bang_amd.BangError, match="signature"):
             e.alloc(q.shape[0])
         e.unload()
+
+
+@pytest.mark.gpu
+def test_rows_file_with_ids_out_of_range_ends_the_batch_with_an_error(libbang, small_u8, tmp_path, monkeypatch):
+    """The pull form's guard against ids out of range, wherever the engine keeps its rows (a registered mapping of the rows file or a pinned
+    copy of it): the signature behind the last row hashes the INDEX's adjacency lists, not the file's rows, so a rows file with the right
+    trailer and wrong rows is taken at bang_load as it is.  The batch then ends with an error naming the cause -- no wild read of the code
+    table, no hang -- and with the file's rows back the next load answers correctly."""
+    import bang_amd
+    from oracle import oracle as O
+    monkeypatch.setenv("BANG_PULL_ROWS_DIR", str(tmp_path))
+    ix, q, _, _ = small_u8
+    ids_o, dists_o = O.Oracle(ix).search(q, 10, 40)
+    path = tmp_path / "index_pull_rows.bin"
+
+    def run():
+        with bang_amd.Engine(ix.dtype, graph=0, pull=1) as e:
+            e.load_index(ix)
+            e.set_searchparams(10, 40)
+            e.alloc(q.shape[0])
+            e.init(q.shape[0])
+            out = e.query(q)
+            assert e.stats()["graph_pull"] == 1
+            return out
+    ids, _ = run()                                                             # builds the file
+    assert np.array_equal(ids, ids_o)
+    good = path.read_bytes()
+    rows = np.memmap(path, np.uint32, "r+", shape=(ix.N, 64))
+    rows[:, 0] = np.uint32(ix.N + 7)                                           # (the trailer behind the rows stays as it is)
+    rows.flush()
+    del rows
+    with pytest.raises(bang_amd.BangError, match="out of range"):
+        run()
+    path.write_bytes(good)
+    ids2, dists2 = run()
+    assert np.array_equal(ids2, ids_o) and np.array_equal(dists2.view(np.uint32), dists_o.view(np.uint32))
 
 
 # -------------------------------------------------------------------------------------------------------------- streamed load

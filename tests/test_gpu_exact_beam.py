@@ -248,6 +248,9 @@ def test_overwritten_rows_are_reported_not_followed(small_u8, tmp_path, monkeypa
     """Pulled rows overwritten behind the engine's back (a well-formed row whose first id is out of range): the id is compared, never turned
     into an address; the batch ends with an error naming the cause, and with the rows back the engine answers correctly again."""
     import bang_amd
+    from bang_amd import binding
+    if not binding.host_register_supported():           # (the engine then reads a pinned copy of the rows: nothing written to the file reaches it)
+        pytest.skip("hipHostRegister is not supported here: the rows file's mapping cannot be registered with the GPU")
     monkeypatch.setenv("BANG_PULL_ROWS_DIR", str(tmp_path))
     ix, q, _, _ = small_u8
     q = q[:NQ]

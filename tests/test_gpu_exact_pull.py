@@ -261,6 +261,9 @@ def test_overwritten_rows_are_reported_not_followed(small_u8, tmp_path, monkeypa
     """Rows overwritten behind the engine's back (an id out of range in column 0 of every row) end the batch with an error naming the cause;
     the id is never turned into an address.  Once the rows are back the engine answers correctly again."""
     import bang_amd
+    from bang_amd import binding
+    if not binding.host_register_supported():           # (the engine then reads a pinned copy of the rows: nothing written to the file reaches it)
+        pytest.skip("hipHostRegister is not supported here: the rows file's mapping cannot be registered with the GPU")
     monkeypatch.setenv("BANG_PULL_ROWS_DIR", str(tmp_path))
     ix, q, _, _ = small_u8
     k, L = 10, 37

@@ -285,6 +285,13 @@ def check_properties(ix, my_q, ids, dists, k):
     return ok
 
 
+def _scaled_shape(wl):
+    """a shape-only workload whose N is not the shape's own (scaled to the box, or --shape-n)"""
+    from tools import shape_workload
+    sh = shape_workload.SHAPES.get(wl.get("key"))
+    return sh is not None and int(wl["ix"].N) != sh["N"]
+
+
 def measure(eng, wl, my_q, L, steps, warmup, ctx, graph, traffic_key=None, batches=1):
     """Times `steps` steps of `batches` bang_query calls each at worklist length L on an allocated engine.  Returns a dict with
     the rate, the per-step times, the engine statistics and the roofline of the search kernel."""
@@ -292,6 +299,11 @@ def measure(eng, wl, my_q, L, steps, warmup, ctx, graph, traffic_key=None, batch
     import torch.distributed as dist
     ix, k = wl["ix"], ctx.k
     Qr = my_q.shape[0]
+    # A full collection of Python's cyclic collector takes 35-40 ms once torch is loaded -- four times a step -- and starts wherever the
+    # allocation counters happen to stand: collected once here, switched off for the warm-up and the timed steps, switched on again behind them
+    import gc
+    gc.collect()
+    gc.disable()
     for _ in range(warmup):
         run_once(eng, my_q, ctx, timed=True)
     step_s, init_s, search_s, gather_s = [], [], [], []
@@ -318,6 +330,7 @@ def measure(eng, wl, my_q, L, steps, warmup, ctx, graph, traffic_key=None, batch
         step_s.append(el)
         search_s.append(e_s)
         gather_s.append(e_g)
+    gc.enable()
     times = torch.tensor([step_s, init_s, search_s, gather_s], dtype=torch.float64, device=ctx.cdev)
     if ctx.world > 1:
         dist.all_reduce(times, op=dist.ReduceOp.MAX)
@@ -361,6 +374,10 @@ def measure(eng, wl, my_q, L, steps, warmup, ctx, graph, traffic_key=None, batch
             by_stream = {"code_rows": int(rows_b), "adjacency_rows_from_hbm": int(adj_b),
                          "filter_reads": int(max(0.0, live["hbm_read"] - rows_b - adj_b)), "filter_writes": int(live["hbm_write"]),
                          "pcie_adjacency_rows": int(live.get("pcie_read", 0))}
+        elif tf and os.path.exists(tf) and ctx.world == 1 and _scaled_shape(wl):
+            # (the committed passes were taken on the unscaled index: they are not this index's)
+            traffic_note = (f"HBM traffic not measured in this run (--full measures it), and the committed PMC passes (profiles/traffic_{traffic_key}.json) "
+                            f"are those of the unscaled index, not of this one (N = {ix.N})")
         elif tf and os.path.exists(tf) and ctx.world == 1:
             try:
                 tj = json.load(open(tf))

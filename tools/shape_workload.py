@@ -100,9 +100,60 @@ HOST_RESERVE = 40 << 30    # streamed load: host memory left to the process besi
                            # the box -- 0.94e9 rows on a 320 GB box, whose 256 GB for N = 1e9 do fit
 
 
-def stream_rows_budget():
-    """pull rows a streamed load may pin in host memory on this box, and the bytes a 1e9-row index would be short of"""
-    return max(0, usable_host_bytes() - HOST_RESERVE) // PULL_ROW_BYTES
+PIN_RESERVE = 2 << 30      # pinned memory left beside the pull rows.  Counted from the allocations: the streamed load's two staging buffers (2^20
+                           # entries x 128 B each = 256 MiB), the engine's result / parent / staging words of a 10 000-query batch (under 10 MiB)
+                           # and the bench's pinned query and result tensors (a few MiB) -- under 0.3 GiB; the cap below is known to 1 GiB only,
+                           # so one further GiB is left as slack
+
+
+_pin = {"fits": 0, "fails": None}      # bytes: the largest single hipHostMalloc seen to succeed / the smallest seen to fail, in this process
+
+
+def _pin_fits(nbytes: int) -> bool:
+    """does ONE pinned allocation of nbytes succeed?  (allocated and freed at once; what earlier calls learnt is not tried again)"""
+    if nbytes <= _pin["fits"]:
+        return True
+    if _pin["fails"] is not None and nbytes >= _pin["fails"]:
+        return False
+    from bang_amd import binding
+    hip = binding.lib()                                          # (libbang.so links the HIP runtime: its symbols resolve through this handle)
+    p = C.c_void_p()
+    if hip.hipHostMalloc(C.byref(p), C.c_size_t(nbytes), C.c_uint(0x1 | 0x2)) == 0:      # hipHostMallocPortable | hipHostMallocMapped
+        hip.hipHostFree(p)
+        _pin["fits"] = nbytes
+        return True
+    hip.hipGetLastError()                                        # (the refusal must not be reported by the next launch)
+    _pin["fails"] = nbytes
+    return False
+
+
+def pinnable_rows(n_rows: int) -> int:
+    """How many of n_rows pull rows the engine can pin on this box.  Where the engine registers mapped memory (bang_host_register_supported): all
+    of them -- registered host memory is bounded by the host memory alone.  Where it does not, the rows are ONE hipHostMalloc allocation, and a
+    virtual machine can cap those far below what /proc/meminfo shows, with nothing a guest can read saying where -- tried, not read: all of them
+    where they fit; else the largest whole number of GiB that does (bisection between what is known to fit and to fail), less PIN_RESERVE.
+    Raises where not even PIN_RESERVE + 1 GiB can be pinned."""
+    from bang_amd import binding
+    if n_rows <= 0 or binding.host_register_supported():
+        return max(0, n_rows)
+    want = n_rows * PULL_ROW_BYTES + 4096                        # (+ the trailer behind the last row)
+    if _pin_fits(want):
+        return n_rows
+    lo, hi = _pin["fits"] >> 30, min(want, _pin["fails"]) + (1 << 30) - 1 >> 30      # GiB: lo fits (0: nothing tried yet), hi does not
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if _pin_fits(mid << 30):
+            lo = mid
+        else:
+            hi = mid
+    if (lo << 30) <= PIN_RESERVE:
+        raise MemoryError(f"pull rows: this box pins no more than {lo} GiB of host memory in one allocation (hipHostMalloc)")
+    return min(n_rows, ((lo << 30) - PIN_RESERVE) // PULL_ROW_BYTES)
+
+
+def stream_rows_budget(n_rows):
+    """how many of n_rows pull rows a load may pin in host memory on this box"""
+    return pinnable_rows(int(min(n_rows, max(0, usable_host_bytes() - HOST_RESERVE) // PULL_ROW_BYTES)))
 
 
 CODE_STRIDE = {"sift1b_shape": 128, "deep100m_shape": 128}   # device-generated code tables: rows padded to their own 128-byte line
@@ -124,9 +175,12 @@ def plan_n(name, dev, n_override=0, reserve_rows=True, stream=False, shared_byte
     N = n_override or int(os.environ.get("BANG_SHAPE_N", "0")) or sh["N"]
     if sh["graph"] == "host" and stream:
         free, _ = torch.cuda.mem_get_info(dev)
-        N = min(N, stream_rows_budget(), (free - (28 << 30)) // (sh["D"] * isz + code_stride(name)))
+        N = min(N, (free - (28 << 30)) // (sh["D"] * isz + code_stride(name)))
+        N = min(N, stream_rows_budget(N))
     elif sh["graph"] == "host":
         N = min(N, int(usable_host_bytes() * 0.75) // (entry + (PULL_ROW_BYTES if reserve_rows else 0)))
+        if reserve_rows:
+            N = min(N, pinnable_rows(int(N)))
     else:
         free, _ = torch.cuda.mem_get_info(dev)
         N = min(N, (int(free * 0.85) - (8 << 30)) // (entry + code_stride(name)), int(usable_host_bytes() * 0.75) // entry)
@@ -190,12 +244,12 @@ def make(name, dev, n_override=0, Q=10_000, seed=20240711, log=print, host_codes
         # STREAMED: the graph image never exists -- the engine pulls the generator's entries through in chunks (vectors -> HBM,
         # adjacency lists -> 256-byte pull rows in host memory).  Host budget: the rows; HBM budget: codes + vectors + 28 GB.
         free, _total = torch.cuda.mem_get_info(dev)
-        n_host, n_hbm = stream_rows_budget(), (free - (28 << 30)) // (D * isz + cs)
+        n_host, n_hbm = stream_rows_budget(N), (free - (28 << 30)) // (D * isz + cs)
         N2 = min(N, n_host, n_hbm)
         if N2 < N:
             short_host = max(0, N - n_host) * PULL_ROW_BYTES / 1e9
             short_hbm = max(0, N - n_hbm) * (D * isz + cs) / 1e9
-            note = (f" (N scaled {N} -> {N2}: the box is {short_host:.1f} GB of host memory short of the {N * PULL_ROW_BYTES / 1e9:.0f} GB of pull rows "
+            note = (f" (N scaled {N} -> {N2}: the box is {short_host:.1f} GB of pinnable host memory short of the {N * PULL_ROW_BYTES / 1e9:.0f} GB of pull rows "
                     f"[{usable_host_bytes() / 1e9:.0f} GB usable, {HOST_RESERVE >> 30} GB kept free] and {short_hbm:.1f} GB of HBM short of vectors + codes + 28 GB)")
             N = N2
     elif sh["graph"] == "host":
@@ -205,6 +259,10 @@ def make(name, dev, n_override=0, Q=10_000, seed=20240711, log=print, host_codes
             N2 = budget // per_node
             note = (f" (N scaled {N} -> {N2}: host memory budget {budget / 2**30:.0f} GiB for {entry}-byte graph entries"
                     + (f" + {PULL_ROW_BYTES}-byte pull rows" if reserve_rows else "") + ")")
+            N = N2
+        if reserve_rows and pinnable_rows(int(N)) < N:
+            N2 = pinnable_rows(int(N))
+            note += f" (N scaled to {N2}: the pull rows that can be pinned in host memory here)"
             N = N2
     else:
         free, _total = torch.cuda.mem_get_info(dev)
