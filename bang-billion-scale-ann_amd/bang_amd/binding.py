@@ -54,13 +54,16 @@ class SearchParams(C.Structure):
     _fields_ = [
         ("Q", C.c_uint32), ("R", C.c_uint32), ("m", C.c_uint32), ("L", C.c_uint32), ("medoid", C.c_uint32), ("cap_iter", C.c_uint32),
         ("psz", C.c_uint32), ("mp", C.c_uint32), ("pq_nhi", C.c_uint32), ("max_wgs", C.c_uint32), ("max_waves", C.c_uint32),
+        ("any_dim", C.c_uint32),             # bang_k_search_exact: 1 = the any-dimension layouts too (in the former padding: no member moved)
         ("d_seed", C.c_void_p), ("d_codes", C.c_void_p), ("d_pivots_packed", C.c_void_p), ("d_qc", C.c_void_p),
         ("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("vec_bytes", C.c_uint32), ("row_layout", C.c_uint32),
         ("d_bloom", C.c_void_p), ("d_cand_ids", C.c_void_p), ("d_cand_cnt", C.c_void_p), ("d_qstats", C.c_void_p),
         ("d_qiters", C.c_void_p), ("d_next_query", C.c_void_p), ("d_ktime", C.c_void_p),
         ("d_rows", C.c_void_p), ("d_ctl", C.c_void_p), ("h_done", C.c_void_p), ("h_parents", C.c_void_p), ("h_pub_q", C.c_void_p),
         ("h_pub_c", C.c_void_p), ("d_abort", C.c_void_p), ("ship_vectors", C.c_uint32), ("nctx", C.c_uint32),
-        ("group_waves", C.c_uint32), ("d_prof", C.c_void_p), ("code_stride", C.c_uint32), ("n_rows_hbm", C.c_uint32), ("d_rows_hbm", C.c_void_p),
+        ("group_waves", C.c_uint32),
+        ("rr_qdim", C.c_uint32),             # any_dim = 1: elements per query row, D or D - 1 (MIPS); 0 = D (in the former padding: no member moved)
+        ("d_prof", C.c_void_p), ("code_stride", C.c_uint32), ("n_rows_hbm", C.c_uint32), ("d_rows_hbm", C.c_void_p),
         ("d_row_slices", C.c_void_p), ("n_slices", C.c_uint32), ("slice_rows", C.c_uint32), ("go_timeout_ticks", C.c_uint64), ("d_qskip", C.c_void_p),
         ("n_nodes", C.c_uint32), ("summ_iters", C.c_uint32), ("spec_rows", C.c_uint32),
         ("n_rows_pad", C.c_uint32),          # padded rows: the rows of the nodes [0, n_rows_pad) sit in d_codes' padding (in the former padding: no member moved)

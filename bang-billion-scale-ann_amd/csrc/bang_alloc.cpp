@@ -137,14 +137,26 @@ static int resolve_form(bang_engine* e) {
       bang_set_error("option distance = 1 (exact) runs on the query-resident search kernel only (search = %d, persistent = %d)", e->search_opt, e->persistent);
       return BANG_ERR_UNSUPPORTED;
     }
-    if (e->distfn != BANG_DIST_L2) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
+    // option any_dim = 1: MIPS parameters and the layouts of bang_search_exact_anydim_supported run on the any-dimension instances -- the plain
+    // one-parent walk on float / 8-bit rows alone; everything else is refused on such an index, by name (refuse_on_anydim)
+    const bool any = e->any_dim == 1;
+    if (e->distfn != BANG_DIST_L2 && !any) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
     const uint64_t vec_stride = dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e);     // (pulled rows: the packed vector table d_vecs)
+    if (any && e->vecs_f16 && !dev_graph && e->distfn != BANG_DIST_L2) BANG_TRY(refuse_on_anydim(e, "option vectors_fp16 = 1"));
+    if (any && e->beam > 1) { char what[32]; snprintf(what, sizeof(what), "option beam = %d", e->beam); BANG_TRY(refuse_on_anydim(e, what)); }
+    if (any && e->range_hits > 0) { char what[48]; snprintf(what, sizeof(what), "option range_hits = %d (range search)", e->range_hits); BANG_TRY(refuse_on_anydim(e, what)); }
+    if (any && !(e->vecs_f16 && !dev_graph) && !bang_search_exact_anydim_supported(e->dtype, e->D, vec_stride)) {
+      bang_set_error("options distance = 1 (exact) and any_dim = 1: unsupported vector layout (dtype %d, D = %u, %s stride %llu): 8-bit vectors need D %% 4 == 0 "
+                     "(packed rows of any other length are not dword aligned); 1 <= D <= %u; %s stride divisible by 4", e->dtype, e->D,
+                     dev_graph ? "entry" : "vector", (unsigned long long)vec_stride, BANG_EXACT_MAX_D, dev_graph ? "an entry" : "a vector");
+      return BANG_ERR_UNSUPPORTED;
+    }
     if (!dev_graph && e->vecs_f16 && (e->D % 8u != 0 || e->D > 256u)) {
       bang_set_error("options distance = 1 (exact) and vectors_fp16 = 1: the exact-distance kernel reads an fp16 vector table of D %% 8 == 0, D <= 256 only "
                      "(D = %u; the wide layouts keep float rows: vectors_fp16 = 0)", e->D);
       return BANG_ERR_UNSUPPORTED;
     }
-    if (!(e->vecs_f16 && !dev_graph) && !bang_search_exact_supported(e->dtype, e->D, vec_stride)) {
+    if (!any && !(e->vecs_f16 && !dev_graph) && !bang_search_exact_supported(e->dtype, e->D, vec_stride)) {
       bang_set_error("option distance = 1 (exact): unsupported vector layout (dtype %d, D = %u, %s stride %llu): 8-bit vectors need D %% 16 == 0, "
                      "float vectors D %% 4 == 0; D <= %u; %s stride divisible by 4", e->dtype, e->D, dev_graph ? "entry" : "vector",
                      (unsigned long long)vec_stride, BANG_EXACT_MAX_D, dev_graph ? "an entry" : "a vector");

@@ -164,6 +164,7 @@ extern "C" int bang_set_query_filters_e(bang_engine_t* e, const uint32_t* any, c
   if (!e) return BANG_ERR_ARG;
   const char* what = "bang_set_query_filters";
   if (!e->allocated) { bang_set_error("%s: the filters of a batch live in its allocation: call bang_alloc first", what); return BANG_ERR_ARG; }
+  if (nq > 0 && e->form == LoopForm::Exact) BANG_TRY(refuse_on_anydim(e, "bang_set_query_filters: a batch with filters on labels"));
   if (nq < 0 || nq > e->Qcap) { bang_set_error("%s: %d filters exceed the allocation of %d queries", what, nq, e->Qcap); return BANG_ERR_ARG; }
   if (nq == 0) { (void)hipSetDevice(e->device); drop_query_filters(e); return BANG_OK; }
   if (!any || !all) { bang_set_error("%s: any / all is null", what); return BANG_ERR_ARG; }
@@ -243,6 +244,7 @@ extern "C" int bang_set_query_radii_e(bang_engine_t* e, const float* radii, int 
   if (!e) return BANG_ERR_ARG;
   const char* what = "bang_set_query_radii";
   if (!e->allocated) { bang_set_error("%s: the radii of a batch live in its allocation: call bang_alloc first", what); return BANG_ERR_ARG; }
+  if (nq > 0 && e->form == LoopForm::Exact) BANG_TRY(refuse_on_anydim(e, "bang_set_query_radii: a batch with radii"));
   if (e->range_hits <= 0 || !e->d_radius) { bang_set_error("%s: range search is off: option range_hits = 0 (set it before bang_alloc)", what); return BANG_ERR_UNSUPPORTED; }
   if (nq < 0 || nq > e->Qcap) { bang_set_error("%s: %d radii exceed the allocation of %d queries", what, nq, e->Qcap); return BANG_ERR_ARG; }
   if (nq == 0) { e->n_radii = 0; return BANG_OK; }

@@ -145,6 +145,7 @@ int consolidate(bang_engine* e, float alpha2, uint64_t st[4]) {
 extern "C" int bang_consolidate_e(bang_engine_t* e, float alpha, uint64_t* out_stats4) {
   if (!e) { bang_set_error("bang_consolidate: the engine is null"); return BANG_ERR_ARG; }
   if (!e->loaded) { bang_set_error("bang_consolidate: no index is loaded"); return BANG_ERR_ARG; }
+  BANG_TRY(refuse_on_anydim(e, "bang_consolidate"));
   if (e->allocated) { bang_set_error("bang_consolidate: an allocation is live (call bang_free first): a batch may be reading the tables"); return BANG_ERR_ARG; }
   if (e->insert_broken) { bang_set_error("bang_consolidate: an earlier insert failed half-way and old rows may list ids beyond N: unload this engine (bang_unload) and load the index again"); return BANG_ERR_ARG; }
   if (e->capacity <= 0 || !e->d_graph) { bang_set_error("bang_consolidate: the index was loaded without option capacity: only an engine whose tables may change (graph = device, capacity >= N) consolidates"); return BANG_ERR_ARG; }

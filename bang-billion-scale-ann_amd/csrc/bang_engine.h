@@ -336,6 +336,7 @@ struct bang_engine {
   // range search (option range_hits + bang_set_query_radii_e): the hit buffers live from bang_alloc to bang_free, the radii from
   // bang_set_query_radii_e to bang_free
   int range_hits = 0;                  // option "range_hits": capacity of a query's hit log, 0 = off
+  int any_dim = 0;                     // option "any_dim": 1 = distance = 1 also takes float vectors of any D, 8-bit vectors with D % 4 == 0 and MIPS parameters
   uint32_t* d_hit_ids = nullptr;       // [Qcap][range_hits] the hit log's ids; sorted and de-duplicated in place by bang_k_range_sort
   float* d_hit_dists = nullptr;        // [Qcap][range_hits] ... and distances
   float* d_radius = nullptr;           // [Qcap] the batch's radii
@@ -373,6 +374,20 @@ inline uint32_t rows_direct(const bang_engine* e) { return e->rows_first == e->n
 inline size_t vec_bytes(const bang_engine* e) { return (size_t)e->D * e->tsize; }
 // bytes between the rows of the HBM vector table d_vecs: the vector as the index holds it, or its fp16 image padded to whole dwords
 inline size_t vec_table_stride(const bang_engine* e) { return e->vecs_f16 ? (((size_t)2 * e->D + 3) & ~(size_t)3) : vec_bytes(e); }
+
+// option any_dim = 1 on an index that only the any-dimension instances of the exact-distance kernel evaluate (a layout bang_search_exact_supported
+// refuses, or MIPS search parameters): nothing but the plain one-parent walk of distance = 1 serves it -- `what` is refused by name, BANG_ERR_UNSUPPORTED.
+// BANG_OK where the option is off or the layout is one of today's: every refusal of today then stays word for word
+inline int refuse_on_anydim(const bang_engine* e, const char* what) {
+  if (e->any_dim != 1 || !e->loaded) return BANG_OK;
+  const bool dev_graph = (e->graph_mode == BANG_GRAPH_DEVICE);
+  const bool mips = e->params_set && e->distfn == BANG_DIST_MIPS;
+  const bool f16_table = e->vecs_f16 && !dev_graph;                  // (fp16 rows have their own layout rule and instance: bang_alloc.cpp)
+  if (!mips && (f16_table || bang_search_exact_supported(e->dtype, e->D, dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e)))) return BANG_OK;
+  bang_set_error("%s is not available with option any_dim = 1 on this index (dtype %d, D = %u%s): the any-dimension instances of the exact-distance kernel "
+                 "run the one-parent walk of distance = 1 alone", what, e->dtype, e->D, mips ? ", MIPS" : "");
+  return BANG_ERR_UNSUPPORTED;
+}
 
 inline int ensure_device(bang_engine* e) {
   if (bang_device_count() == 0) {

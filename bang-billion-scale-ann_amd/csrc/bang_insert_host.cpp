@@ -209,6 +209,7 @@ int bang::rebuild_seed(bang_engine* e) {
 extern "C" int bang_insert_e(bang_engine_t* e, const void* h_vectors, uint32_t n, uint32_t L_build, float alpha, uint64_t* first_id) {
   if (!e) { bang_set_error("bang_insert: the engine is null"); return BANG_ERR_ARG; }
   if (!e->loaded) { bang_set_error("bang_insert: no index is loaded"); return BANG_ERR_ARG; }
+  BANG_TRY(refuse_on_anydim(e, "bang_insert"));
   if (e->allocated) { bang_set_error("bang_insert: an allocation is live (call bang_free first): a batch may be reading the tables"); return BANG_ERR_ARG; }
   if (e->insert_broken) { bang_set_error("bang_insert: an earlier insert failed half-way and old rows may list ids beyond N: unload this engine (bang_unload) and load the index again"); return BANG_ERR_ARG; }
   if (e->capacity <= 0 || !e->d_graph) { bang_set_error("bang_insert: the index was loaded without option capacity: its tables hold no further node"); return BANG_ERR_ARG; }

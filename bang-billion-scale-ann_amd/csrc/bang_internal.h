@@ -93,7 +93,12 @@ int bang_search_exact_wide_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint
 // the pulled-rows instance on an fp16 vector table (rr_vec_f16 = 1; the same source built with BANG_EXACT_PULL and BANG_EXACT_F16 as
 // bang_search_exact_pull_f16.o), handed bang_k_search_exact's checked arguments
 int bang_k_search_exact_pull_f16(const bang_search_params* p, void* stream);
-// the pulled-rows instances of the beam form (bang_search_beam.hip built with BANG_EXACT_PULL as bang_search_beam_pull.o), handed
+// the any-dimension instances (bang_search_params.any_dim = 1; the same source built with BANG_EXACT_ANYDIM as bang_search_exact_anydim.o and, with
+// BANG_EXACT_PULL, bang_search_exact_anydim_pull.o): the layouts of bang_search_exact_anydim_supported that the instances above refuse, and queries
+// of rr_qdim < rr_D elements; handed bang_k_search_exact's checked arguments
+int bang_k_search_exact_anydim(const bang_search_params* p, void* stream);
+int bang_k_search_exact_anydim_pull(const bang_search_params* p, void* stream);
+// the pulled-rows instances of the beam form(bang_search_beam.hip built with BANG_EXACT_PULL as bang_search_beam_pull.o), handed
 // bang_k_search_exact_beam's checked arguments
 int bang_k_search_exact_beam_pull(const bang_search_params* p, uint32_t beam, void* stream);
 // the label-filter instances of the exact-distance search kernel (the same source built with BANG_EXACT_LABELS as bang_search_exact_labels.o and, with

@@ -114,7 +114,12 @@ static int derive_facts(bang_engine* e, const Lane& ln, int Q, RunFacts& r) {
                    "re-rank holds %d candidates per query", e->L, BANG_MAX_L + BANG_EXTRA_ITERS);
     return BANG_ERR_UNSUPPORTED;
   }
-  if (e->form == LoopForm::Exact && r.dim_adjust != 0) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
+  if (e->form == LoopForm::Exact && r.dim_adjust != 0 && e->any_dim == 1) {          // MIPS on the any-dimension instances: the plain walk alone
+    if (e->beam > 1) BANG_TRY(refuse_on_anydim(e, "option beam > 1"));
+    if (e->n_qfilters != 0) BANG_TRY(refuse_on_anydim(e, "a batch with filters on labels"));
+    if (e->n_radii != 0) BANG_TRY(refuse_on_anydim(e, "a batch with radii"));
+    if (e->vecs_f16 && !r.dev_graph) BANG_TRY(refuse_on_anydim(e, "option vectors_fp16 = 1"));
+  } else if (e->form == LoopForm::Exact && r.dim_adjust != 0) { bang_set_error("option distance = 1 (exact) supports L2 distance only (no MIPS)"); return BANG_ERR_UNSUPPORTED; }
   r.whole = ln.q0 == 0 && (int)ln.nq == Q && (int)ln.nq == e->Qcur;
   const size_t mailbox_max = (size_t)env_long("BANG_MAILBOX_BYTES", BANG_RESULT_MAILBOX_BYTES);
   r.to_device = e->pool.d_ids_user != nullptr;
@@ -218,6 +223,9 @@ static int run_exact(bang_engine* e, Lane& ln, const RunFacts& r, const bang_ite
     sp.rr_vec_base = e->d_vecs; sp.rr_vec_stride = vec_table_stride(e); sp.rr_vec_f16 = e->vecs_f16 ? 1u : 0u;
   }
   result_sinks(e, ln, r, sp);
+  // option any_dim: the launch may take the any-dimension instances (bang_k_search_exact routes on the layout); the queries are rr_qdim elements long
+  sp.any_dim = e->any_dim == 1 ? 1u : 0u;
+  sp.rr_qdim = e->D - r.dim_adjust;
   // per-query label filters (bang_set_query_filters_e): the kernel collects the results itself, from every node the walk evaluates,
   // and tests the exclusion bitmap on the way -- no pick behind it
   const bool filtered = e->n_qfilters != 0;

@@ -82,6 +82,11 @@ static const OptionDef kOptions[] = {
      "the same walk and returns, beside its k results, every evaluated node within the query's radius (squared L2), sorted by distance then id "
      "(bang_get_range_results); the first range_hits hits in evaluation order are kept, bang_get_range_counts tells when there were more.  Refused: "
      "distance = 0, beam > 1, vectors_fp16 = 1 and the wide layouts (D > 256, 8-bit D / 16 not a power of two).  0 = off (default)"},
+    {"any_dim", "BANG_ANY_DIM", &bang_engine::any_dim, 0, 1, INT, BEFORE_ALLOC,
+     "distance = 1 only: 1 = the exact-distance walk also takes float vectors of any D, 8-bit vectors with D % 4 == 0 (D <= 1024; SPACEV's 100 bytes) and MIPS "
+     "search parameters (queries of D - 1 elements, the last coordinate read as 0), with graph = device and with the pulled rows; such an index runs on the "
+     "any-dimension instances of the kernel, a layout that 0 accepts keeps today's instances bit for bit.  Refused on such an index, by name: beam > 1, "
+     "labels, radii, vectors_fp16, inserts, consolidation, the scan and semantics = 1 (distance = 0 is what it was: the PQ walk's re-rank stays a launch of its own there).  0 = today's layouts only (default)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

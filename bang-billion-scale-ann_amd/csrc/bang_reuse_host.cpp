@@ -256,6 +256,7 @@ int mutable_engine(bang_engine* e, const char* what, bool need_free) {
 extern "C" int bang_insert_reuse_e(bang_engine_t* e, const void* h_vectors, uint32_t n, uint32_t L_build, float alpha, uint64_t* ids_out) {
   if (!e) { bang_set_error("bang_insert_reuse: the engine is null"); return BANG_ERR_ARG; }
   if (!e->loaded) { bang_set_error("bang_insert_reuse: no index is loaded"); return BANG_ERR_ARG; }
+  BANG_TRY(refuse_on_anydim(e, "bang_insert_reuse"));
   if (e->allocated) { bang_set_error("bang_insert_reuse: an allocation is live (call bang_free first): a batch may be reading the tables"); return BANG_ERR_ARG; }
   if (e->insert_broken) { bang_set_error("bang_insert_reuse: an earlier insert failed half-way and old rows may list ids beyond N or free slots: unload this engine (bang_unload) and load the index again"); return BANG_ERR_ARG; }
   if (e->capacity <= 0 || !e->d_graph) { bang_set_error("bang_insert_reuse: the index was loaded without option capacity: only an engine whose tables may change (graph = device, capacity >= N) inserts"); return BANG_ERR_ARG; }

@@ -90,6 +90,7 @@ extern "C" int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq,
                            float* dists_out, uint32_t* matched_out) {
   if (!e) { bang_set_error("bang_scan: the engine is null"); return BANG_ERR_ARG; }
   if (!e->loaded) { bang_set_error("bang_scan: no index is loaded"); return BANG_ERR_ARG; }
+  BANG_TRY(refuse_on_anydim(e, "bang_scan"));
   if (!h_queries) { bang_set_error("bang_scan: the queries are null"); return BANG_ERR_ARG; }
   if (!ids_out || !dists_out) { bang_set_error("bang_scan: an output buffer (ids, dists) is null"); return BANG_ERR_ARG; }
   if (nq == 0 || nq > BANG_SCAN_MAX_QUERIES) { bang_set_error("bang_scan: nq = %u is outside [1, %u]", nq, BANG_SCAN_MAX_QUERIES); return BANG_ERR_ARG; }

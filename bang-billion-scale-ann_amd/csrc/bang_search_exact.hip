@@ -49,6 +49,10 @@
 //    compacted in input order (__ballot + lanes_below, element 64 behind the first 64) and written, id and distance bits, to the query's row of
 //    d_hit_ids / d_hit_dists while positions < cap last; d_offered counts them all.  Two plain vector stores per hit, nothing waits for them, no
 //    LDS (CANON 19; bang_range.hip sorts the rows behind the launch).  Everything it adds sits under BANG_EXACT_RANGE.
+//  * ANY DIMENSION (BANG_EXACT_ANYDIM, with and without BANG_EXACT_PULL; bang_search_params.any_dim = 1; entries bang_k_search_exact_anydim[_pull]).
+//    The same walk; float vectors of any D <= 1024, 8-bit vectors with D % 4 == 0, and queries one element shorter than the vectors (MIPS: the
+//    last coordinate reads as 0).  One instance per type holds a narrow routine (D <= 256) and the tile routine; rows and query are zero beyond
+//    their ends and no load touches a byte outside a row.  Everything it adds sits under BANG_EXACT_ANYDIM.
 //
 // Reference line numbers: the reference's BANG_Base/bang_search.cu unless a file is named.
 
@@ -86,7 +90,15 @@
 #error "BANG_EXACT_RANGE and BANG_EXACT_LABELS are builds of their own: radii and label filters do not combine"
 #endif
 
-#if defined(BANG_EXACT_WIDE) && defined(BANG_EXACT_PULL)
+#if defined(BANG_EXACT_ANYDIM) && (defined(BANG_EXACT_WIDE) || defined(BANG_EXACT_LABELS) || defined(BANG_EXACT_RANGE) || defined(BANG_EXACT_F16))
+#error "BANG_EXACT_ANYDIM is a build of its own (with or without BANG_EXACT_PULL): it holds its narrow and its tile routines, and has no label, range or fp16 form"
+#endif
+
+#if defined(BANG_EXACT_ANYDIM) && defined(BANG_EXACT_PULL)
+#define EXACT_TAG _anydim_pull
+#elif defined(BANG_EXACT_ANYDIM)
+#define EXACT_TAG _anydim
+#elif defined(BANG_EXACT_WIDE) && defined(BANG_EXACT_PULL)
 #define EXACT_TAG _wide_pull
 #elif defined(BANG_EXACT_WIDE)
 #define EXACT_TAG _wide
@@ -181,7 +193,109 @@ __device__ __forceinline__ void exact_dist_f16(const uint8_t GAS* tab, uint64_t 
 }
 #endif
 
-#ifdef BANG_EXACT_WIDE
+#ifdef BANG_EXACT_ANYDIM
+// ---------------------------------------------------------------------------------------------------------------------
+// any-dimension layouts (BANG_EXACT_ANYDIM; bang_search_params.any_dim = 1): float vectors of any D, 8-bit vectors of whole dwords, queries of
+// rr_qdim <= D elements (MIPS: the last coordinate is read as 0).  Three distance routines: anydim_dist8 (8-bit, D <= 256: the lane groups of
+// exact_dist8 with G the power of two at or above ceil(D / 16)), anydim_dist_f32 (float, D <= 256: the chain of exact_dist_f32 with a tail of
+// single dwords) and, past 256, exact_dist_wide below with a tail-aware fetch.  A row element that does not exist is a ZERO against a query
+// element that is zero: fmaf(0, 0, acc) == acc for acc >= +0, and nothing in vv - 2 vq.  ONE RULE: no load touches a byte outside
+// [row, row + vec_bytes) -- the last row of a packed table ends its allocation.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
+
+// the first nd (0..4) dwords at p, zeros behind them (three dwords as 2 + 1: a three-element vector type is loaded as four)
+__device__ __forceinline__ u32x4a load_dwords(const uint8_t GAS* p, uint32_t nd) {
+  u32x4a v = {0u, 0u, 0u, 0u};
+  if (nd >= 4u) v = *(const u32x4a GAS*)p;
+  else {
+    if (nd >= 2u) { const u32x2a t = *(const u32x2a GAS*)p; v.x = t.x; v.y = t.y; }
+    if (nd == 3u) v.z = *(const uint32_t GAS*)(p + 8);
+    if (nd == 1u) v.x = *(const uint32_t GAS*)p;
+  }
+  return v;
+}
+
+// dwords of the 16-byte piece at byte offset o of a row of vec_bytes bytes (a multiple of 4) that exist: 0..4
+__device__ __forceinline__ uint32_t piece_dwords(uint32_t o, uint32_t vec_bytes) {
+  if (o >= vec_bytes) return 0u;
+  const uint32_t left = (vec_bytes - o) >> 2;
+  return left < 4u ? left : 4u;
+}
+
+// exact_dist8 for any D % 4 == 0, D <= 256: P = ceil(D / 16) pieces, G (a power of two >= P) adjacent lanes per survivor; a lane whose piece
+// lies behind the row holds zeros and issues no load, the lane of the last piece loads its (D % 16) / 4 dwords.  qw / qq: anydim_load_query
+template <bool SIGNED>
+__device__ __forceinline__ void anydim_dist8(const uint8_t GAS* graph, uint64_t entry_len, uint32_t D, uint32_t G, const uint32_t* sid, uint32_t n,
+                                             float* dist, u32x4a qw, int qq, int lane) {
+  constexpr int U = 4;                                            // vector fetches in flight per lane
+  const uint32_t per = 64u / G;                                   // survivors per wave instruction
+  const uint32_t sub = (uint32_t)lane & (G - 1u), slot = (uint32_t)lane / G;
+  const uint32_t nd = piece_dwords(16u * sub, D);
+  for (uint32_t i0 = 0; i0 < n; i0 += per * U) {                  // (uniform)
+    u32x4a v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t i = i0 + (uint32_t)u * per + slot;
+      const uint32_t id = sid[i < n ? i : 0u];
+      v[u] = load_dwords(graph + (uint64_t)id * entry_len + 16u * sub, nd);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t i = i0 + (uint32_t)u * per + slot;
+      int vv = xdot4<SIGNED>(v[u].x, v[u].x, xdot4<SIGNED>(v[u].y, v[u].y, xdot4<SIGNED>(v[u].z, v[u].z, xdot4<SIGNED>(v[u].w, v[u].w, qq))));
+      const int vq = xdot4<SIGNED>(v[u].x, qw.x, xdot4<SIGNED>(v[u].y, qw.y, xdot4<SIGNED>(v[u].z, qw.z, xdot4<SIGNED>(v[u].w, qw.w, 0))));
+      vv -= 2 * vq;                                               // < 2^24: 256 x 255^2
+      for (uint32_t off = 1; off < G; off <<= 1) vv += __shfl_xor(vv, (int)off);
+      if (i < n && sub == 0u) dist[i] = (float)vv;
+    }
+  }
+}
+
+// exact_dist_f32 for any D <= 256: whole 16-byte pieces as there, the last D % 4 elements as single dwords, chained in ascending order.  qr[t]:
+// lane l holds query element 64 t + l, +0.0f from rr_qdim up (the MIPS coordinate costs no branch)
+template <int NQ>
+__device__ __forceinline__ void anydim_dist_f32(const uint8_t GAS* graph, uint64_t entry_len, uint32_t D, const uint32_t* sid, uint32_t n, float* dist,
+                                                const float (&qr)[NQ], int lane) {
+  constexpr int RF = 4;                                           // 16-byte loads in flight per lane
+  for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform)
+    const uint32_t i = i0 + (uint32_t)lane;
+    const uint32_t id = sid[i < n ? i : 0u];
+    const uint8_t GAS* v = graph + (uint64_t)id * entry_len;
+    float acc = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t jt = (uint32_t)t * 64u;
+      if (jt >= D) break;                                         // (uniform)
+      const uint32_t dt = D - jt < 64u ? D - jt : 64u;
+      for (uint32_t jl = 0; jl < dt; jl += 4u * RF) {             // (uniform)
+        u32x4a w[RF];
+#pragma unroll
+        for (int u = 0; u < RF; ++u) {
+          const uint32_t j = jl + 4u * (uint32_t)u;
+          w[u] = load_dwords(v + 4u * (jt + j), j < dt ? (dt - j < 4u ? dt - j : 4u) : 0u);     // (uniform count)
+        }
+#pragma unroll
+        for (int u = 0; u < RF; ++u) {
+          const uint32_t j = jl + 4u * (uint32_t)u;
+          const uint32_t ww[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            if (j + (uint32_t)d < dt) {                           // (uniform)
+              const float qv = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qr[t]), (int)(j + (uint32_t)d)));
+              const float diff = __uint_as_float(ww[d]) - qv;     // orc_exact_dist: vector - query
+              acc = __builtin_fmaf(diff, diff, acc);              // ascending dimension
+            }
+          }
+        }
+      }
+    }
+    if (i < n) dist[i] = acc;
+  }
+}
+#endif
+
+#if defined(BANG_EXACT_WIDE) || defined(BANG_EXACT_ANYDIM)
 // ---------------------------------------------------------------------------------------------------------------------
 // wide layouts: rows fetched cooperatively through an LDS tile (one per wave: 64 rows x 64 bytes)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -208,6 +322,19 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
   for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform; a second pass for the 65th id of the seed list only)
     const uint32_t np = n - i0 < WAVE ? n - i0 : WAVE;
     u32x4a st[4] = {};
+#ifdef BANG_EXACT_ANYDIM
+    // vec_bytes need not be a multiple of 16: the lane of a row's last piece loads the dwords that exist and stages zeros behind them, a lane
+    // behind the row's end stages zeros and loads nothing; the chains below then run over ceil(D / 4) or ceil(D / 16) pieces against a query
+    // that is zero there too
+    auto fetch = [&](uint32_t t) {
+      const uint32_t o = 64u * t + 16u * lc, nd = piece_dwords(o, vec_bytes);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t i = 16u * (uint32_t)u + ls;
+        if (16u * (uint32_t)u < np) st[u] = load_dwords(graph + (uint64_t)sid[i0 + (i < np ? i : 0u)] * entry_len + o, nd);   // (uniform)
+      }
+    };
+#else
     auto fetch = [&](uint32_t t) {                                // tile t of up to 64 rows: four loads of 16 rows x 64 B
       uint32_t o = 64u * t + 16u * lc;
       if (o >= vec_bytes) o = 0;                                  // (behind the vector's end: a piece again, never used)
@@ -217,6 +344,7 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
         if (16u * (uint32_t)u < np) st[u] = *(const u32x4a GAS*)(graph + (uint64_t)sid[i0 + (i < np ? i : 0u)] * entry_len + o);   // (uniform)
       }
     };
+#endif
     auto turn = [&](uint32_t t) {                                 // staged tile t -> LDS; tile t + 1 requested
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -252,7 +380,11 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
     } else {
       int sum = 0;                                                // the chain's value while it is an integer <= 2^24
       bool chain = false;                                         // (uniform) the wave has left the integers
+#ifdef BANG_EXACT_ANYDIM
+      const uint32_t P = (D + 15u) >> 4;                          // 16-byte pieces per vector, the last one zero-filled from D % 16 up
+#else
       const uint32_t P = D >> 4;                                  // 16-byte pieces per vector
+#endif
       for (uint32_t t = 0; t < T; ++t) {
         turn(t);
 #pragma unroll
@@ -291,8 +423,47 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
 }
 // the float instance keeps 16 query registers across the whole loop and needs a few registers more than the 128 that 16 waves per CU leave a
 // wave: 12 waves per CU, no scratch (bang_search_exact_wide_geometry reads both figures off the instance)
+#ifdef BANG_EXACT_ANYDIM                                          // (its float instances fit 128 registers: 121 / 123, no scratch -- 16 waves per CU)
+#define EXACT_MAX_THREADS(DT) 1024
+#else
 #define EXACT_MAX_THREADS(DT) ((DT) == BANG_F32 ? 768 : 1024)
+#endif
 #define EXACT_EXTRA_WORDS EXACT_TILE_WORDS                        // the wave's row tile, behind its scratch
+#ifdef BANG_EXACT_ANYDIM
+// The raw query of an any-dimension launch, in registers: row qabs of rr_queries, qd = rr_qdim elements long, read as 0 from qd up.  Float: qr[t]
+// of lane l holds element 64 t + l.  8-bit: qw = this lane's 16-byte piece -- piece lane % G where D <= 256 (G lanes per survivor: anydim_dist8),
+// piece `lane` past that (exact_dist_wide) -- gathered byte by byte (a row of qd = D - 1 bytes starts at any address), qq the sum of its squares
+// (the float registers are the caller's array: a member of a returned struct that exact_dist_wide picks by index ends up in scratch)
+struct AnyQuery8 { u32x4a qw; int qq; uint32_t G; };
+template <int DT>
+__device__ __forceinline__ AnyQuery8 anydim_load_query(const void* queries, size_t qabs, uint32_t D, uint32_t qd, float (&qr)[EXACT_QREGS], int lane) {
+  AnyQuery8 a;
+  a.qw = (u32x4a){0u, 0u, 0u, 0u};
+  a.qq = 0;
+  a.G = 1;
+#pragma unroll
+  for (int t = 0; t < EXACT_QREGS; ++t) qr[t] = 0.0f;
+  if (DT == BANG_F32) {
+    const float GAS* qsrc = (const float GAS*)queries + qabs * qd;
+#pragma unroll
+    for (int t = 0; t < EXACT_QREGS; ++t) { const uint32_t j = (uint32_t)t * 64u + (uint32_t)lane; if (j < qd) qr[t] = qsrc[j]; }
+  } else {
+    const uint32_t P = (D + 15u) >> 4;
+    while (a.G < P) a.G <<= 1;                                    // (uniform)
+    const uint32_t piece = D > 256u ? (uint32_t)lane : (uint32_t)lane & (a.G - 1u);
+    const uint8_t GAS* qsrc = (const uint8_t GAS*)queries + qabs * qd;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      const uint32_t j = 16u * piece + (uint32_t)b;
+      if (j < qd) w[b >> 2] |= (uint32_t)qsrc[j] << (8 * (b & 3));
+    }
+    a.qw = (u32x4a){w[0], w[1], w[2], w[3]};
+    a.qq = query_sumsq<DT == BANG_I8>(a.qw);
+  }
+  return a;
+}
+#endif
 #else
 #define EXACT_MAX_THREADS(DT) 1024
 #define EXACT_EXTRA_WORDS 0u
@@ -350,7 +521,10 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 
     // the raw query, in registers
     const uint32_t D = p.rr_D;
-#ifdef BANG_EXACT_WIDE
+#if defined(BANG_EXACT_ANYDIM)
+    float qr[EXACT_QREGS];
+    const AnyQuery8 aq = anydim_load_query<DT>(p.rr_queries, qabs, D, p.rr_qdim ? p.rr_qdim : D, qr, lane);
+#elif defined(BANG_EXACT_WIDE)
     u32x4a qw = {0u, 0u, 0u, 0u};
     int qq = 0;
     float qr[EXACT_QREGS];
@@ -418,7 +592,11 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 
       // ---------------- exact distances (CANON 10: replaces K2) ----------------
       if (n > 0) {
-#ifdef BANG_EXACT_WIDE
+#if defined(BANG_EXACT_ANYDIM)
+        if (D > 256u) exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, w.scratch + WAVE_SCRATCH_WORDS, qr, aq.qw, aq.qq, lane);   // (uniform)
+        else if (DT == BANG_F32) anydim_dist_f32(graph, entry_len, D, sc, n, sdist, qr, lane);
+        else anydim_dist8<DT == BANG_I8>(graph, entry_len, D, aq.G, sc, n, sdist, aq.qw, aq.qq, lane);
+#elif defined(BANG_EXACT_WIDE)
         exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, w.scratch + WAVE_SCRATCH_WORDS, qr, qw, qq, lane);
 #else
 #ifdef BANG_EXACT_F16
@@ -610,6 +788,11 @@ extern "C" int EXACT_ENTRY(const bang_search_params* p, void* stream) {
 #if defined(BANG_EXACT_F16)
   if (p->row_layout != 1u || p->rr_vec_f16 != 1u || p->rr_dtype != BANG_F32 || p->rr_D % 8u != 0u || p->rr_D > 256u || (p->rr_vec_stride & 3u) ||
       p->rr_vec_stride < 2ull * p->rr_D) return BANG_ERR_ARG;
+#elif defined(BANG_EXACT_ANYDIM)
+  const uint32_t qd = p->rr_qdim ? p->rr_qdim : p->rr_D;
+  if (p->any_dim != 1u || p->row_layout != (uint32_t)EXACT_PULL || p->rr_vec_f16 != 0u || qd > p->rr_D || qd + 1u < p->rr_D ||
+      p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
+      !bang_search_exact_anydim_supported((int)p->rr_dtype, p->rr_D, EXACT_PULL ? p->rr_vec_stride : p->entry_len)) return BANG_ERR_ARG;
 #elif EXACT_PULL
   if (p->row_layout != 1u || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) return BANG_ERR_ARG;
 #else

@@ -51,6 +51,22 @@ extern "C" int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry
   return 0;
 }
 
+// The layouts of an any_dim = 1 launch (bang_search_params.any_dim; engine option "any_dim"): float vectors of any D, 8-bit vectors of whole dwords;
+// 1 <= D <= 1024; a 4-byte-aligned stride that holds the vector.  A superset of the above; what the above refuses runs on the any-dimension instances.
+extern "C" int bang_search_exact_anydim_supported(int dtype, uint32_t D, uint64_t entry_len) {
+  if (D == 0 || D > BANG_EXACT_MAX_D || (entry_len & 3u)) return 0;
+  if (dtype == BANG_F32) return entry_len >= 4ull * D;
+  if (dtype == BANG_U8 || dtype == BANG_I8) return D % 4u == 0 && entry_len >= D;
+  return 0;
+}
+
+// any_dim = 1: the elements per query row (0: rr_D), and whether the launch belongs to the any-dimension instances
+static uint32_t exact_qdim(const bang_search_params* p) { return p->rr_qdim ? p->rr_qdim : p->rr_D; }
+static bool exact_takes_anydim(const bang_search_params* p) {
+  if (p->any_dim != 1u || p->rr_vec_f16 == 1u) return false;
+  return exact_qdim(p) != p->rr_D || !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->row_layout == 1u ? p->rr_vec_stride : p->entry_len);
+}
+
 extern "C" int bang_exact_check_args(const bang_search_params* p, const char* prefix) {
   if (p->R == 0 || p->R > BANG_MAX_R || p->L == 0 || p->L > BANG_MAX_L) { bang_set_error("%s: bad R/L", prefix); return BANG_ERR_ARG; }
   if (p->row_layout > 1u) { bang_set_error("%s: row_layout = %u: the adjacency lists are graph entries in HBM (0) or 256-byte rows (1)", prefix, p->row_layout); return BANG_ERR_UNSUPPORTED; }
@@ -64,7 +80,7 @@ extern "C" int bang_exact_check_args(const bang_search_params* p, const char* pr
   return BANG_OK;
 }
 
-extern "C" int bang_exact_check_layout(const bang_search_params* p, const char* prefix) {
+static int exact_check_layout(const bang_search_params* p, const char* prefix, bool anydim) {
   if (p->row_layout == 1u) {
     // the pulled-rows form: adjacency rows in d_graph (pinned host memory; 4-byte aligned), vectors at rr_vec_base + id * rr_vec_stride
     if (!p->d_graph || (((uintptr_t)p->d_graph) & 3u)) { bang_set_error("%s, row_layout = 1: d_graph (the 256-byte adjacency rows) is null or not 4-byte aligned", prefix); return BANG_ERR_ARG; }
@@ -75,7 +91,13 @@ extern "C" int bang_exact_check_layout(const bang_search_params* p, const char* 
                      (unsigned long long)p->rr_vec_stride, p->rr_D);
       return BANG_ERR_ARG;
     }
-    if (p->rr_vec_f16 != 1u && !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
+    if (p->rr_vec_f16 != 1u && anydim && !bang_search_exact_anydim_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
+      bang_set_error("%s, row_layout = 1, any_dim = 1: rr_vec_stride = %llu does not describe vectors the kernel evaluates (dtype %u, D = %u): 8-bit vectors need "
+                     "D %% 4 == 0; 1 <= D <= %u; a stride divisible by 4 that holds the vector", prefix, (unsigned long long)p->rr_vec_stride, p->rr_dtype, p->rr_D,
+                     BANG_EXACT_MAX_D);
+      return BANG_ERR_ARG;
+    }
+    if (p->rr_vec_f16 != 1u && !anydim && !bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->rr_vec_stride)) {
       bang_set_error("%s, row_layout = 1: rr_vec_stride = %llu does not describe vectors the kernel evaluates (dtype %u, D = %u): 8-bit vectors need "
                      "D %% 16 == 0, float vectors D %% 4 == 0; D <= %u; a stride divisible by 4 that holds the vector", prefix,
                      (unsigned long long)p->rr_vec_stride, p->rr_dtype, p->rr_D, BANG_EXACT_MAX_D);
@@ -88,6 +110,15 @@ extern "C" int bang_exact_check_layout(const bang_search_params* p, const char* 
     if (p->n_rows_hbm != 0u && !p->d_rows_hbm) { bang_set_error("%s, row_layout = 1: n_rows_hbm = %u needs d_rows_hbm", prefix, p->n_rows_hbm); return BANG_ERR_ARG; }
     return BANG_OK;
   }
+  if (anydim) {
+    if (!bang_search_exact_anydim_supported((int)p->rr_dtype, p->rr_D, p->entry_len) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
+        (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
+      bang_set_error("%s, any_dim = 1: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 4 == 0; 1 <= D <= %u; an entry "
+                     "stride divisible by 4", prefix, p->rr_dtype, p->rr_D, (unsigned long long)p->entry_len, BANG_EXACT_MAX_D);
+      return BANG_ERR_UNSUPPORTED;
+    }
+    return BANG_OK;
+  }
   if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, p->entry_len) || p->vec_bytes != p->rr_D * (p->rr_dtype == BANG_F32 ? 4u : 1u) ||
       (((uintptr_t)p->d_graph) & 3u) || (((uintptr_t)p->rr_queries) & 3u)) {
     bang_set_error("%s: unsupported vector layout (dtype %u, D = %u, entry stride %llu): 8-bit vectors need D %% 16 == 0, float vectors "
@@ -97,8 +128,10 @@ extern "C" int bang_exact_check_layout(const bang_search_params* p, const char* 
   return BANG_OK;
 }
 
-// every check of a bang_k_search_exact launch (bang_k_search_exact_labels and _range make them too)
-static int exact_check(const bang_search_params* p) {
+extern "C" int bang_exact_check_layout(const bang_search_params* p, const char* prefix) { return exact_check_layout(p, prefix, false); }
+
+// every check of a bang_k_search_exact launch (bang_k_search_exact_labels and _range make them too, without the any-dimension layouts: any_dim = false)
+static int exact_check(const bang_search_params* p, bool anydim = false) {
   static const char* const prefix = "distance = 1";
   int rc = bang_exact_check_args(p, prefix);
   if (rc != BANG_OK) return rc;
@@ -108,14 +141,21 @@ static int exact_check(const bang_search_params* p) {
     if (p->rr_dtype != BANG_F32) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs rr_dtype = BANG_F32 (rr_dtype = %u)", p->rr_dtype); return BANG_ERR_ARG; }
     if (p->rr_D == 0u || p->rr_D % 8u != 0u || p->rr_D > 256u) { bang_set_error("distance = 1: rr_vec_f16 = 1 needs rr_D %% 8 == 0 and rr_D <= 256 (rr_D = %u)", p->rr_D); return BANG_ERR_ARG; }
   }
-  return bang_exact_check_layout(p, prefix);
+  return exact_check_layout(p, prefix, anydim);
 }
 
 extern "C" int bang_k_search_exact(const bang_search_params* p, void* stream) {
   if (!p) return BANG_ERR_ARG;
   if (p->Q == 0) return BANG_OK;
-  const int rc = exact_check(p);
+  if (p->any_dim > 1u) { bang_set_error("distance = 1: any_dim = %u (0 = today's layouts, 1 = those of bang_search_exact_anydim_supported too)", p->any_dim); return BANG_ERR_ARG; }
+  const bool anydim = p->any_dim == 1u && p->rr_vec_f16 != 1u;
+  const int rc = exact_check(p, anydim);
   if (rc != BANG_OK) return rc;
+  if (anydim && (exact_qdim(p) > p->rr_D || exact_qdim(p) + 1u < p->rr_D)) {
+    bang_set_error("distance = 1, any_dim = 1: rr_qdim = %u is neither rr_D = %u nor rr_D - 1 (queries without the MIPS coordinate)", p->rr_qdim, p->rr_D);
+    return BANG_ERR_ARG;
+  }
+  if (exact_takes_anydim(p)) return p->row_layout == 1u ? bang_k_search_exact_anydim_pull(p, stream) : bang_k_search_exact_anydim(p, stream);
   if (p->row_layout == 1u) {
     if (p->rr_vec_f16 == 1u) return bang_k_search_exact_pull_f16(p, stream);
     if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, p->rr_vec_stride, 0)) return bang_k_search_exact_pull(p, stream);

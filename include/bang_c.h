@@ -554,7 +554,12 @@ typedef struct {
   uint32_t cap_iter;                   /* last iteration a query may run: L + BANG_EXTRA_ITERS - 1 (bang_search.cu:950) */
   uint32_t psz, mp, pq_nhi;            /* pivot layout (bang_pq_layout / bang_pack_pivots[_ragged]); psz != 0 */
   uint32_t max_wgs, max_waves;         /* 0 = one workgroup per CU / as many waves per workgroup as LDS holds (<= 16) */
-  const uint32_t* d_seed;              /* [2 + R + 1] {count, MEDOID, adj(MEDOID)...} */
+  uint32_t any_dim;                    /* bang_k_search_exact only (engine option "any_dim"): 1 = the layouts of bang_search_exact_anydim_supported are accepted, and those
+                                          that bang_search_exact_supported refuses -- or whose queries are shorter than the vectors (rr_qdim != rr_D) -- run on the any-dimension
+                                          instances; a layout today's instances accept with rr_qdim == rr_D keeps them.  0 = today's layouts only; > 1 is BANG_ERR_ARG.  Every
+                                          other entry point ignores it.  (It takes the four bytes of padding that lay between max_waves and the pointer below, as
+                                          n_rows_pad and rr_vec_f16 took theirs: no member moves, sizeof is what it was, and a caller zeroes the struct before filling it.) */
+  const uint32_t* d_seed;             /* [2 + R + 1] {count, MEDOID, adj(MEDOID)...} */
   const uint8_t* d_codes;              /* [N][m] + 256 B slack */
   const float* d_pivots_packed;
   const float* d_qc;                   /* [Q][mp*psz] centred queries (bang_k_center_queries) */
@@ -590,7 +595,10 @@ typedef struct {
   uint32_t nctx;                       /* 0 = auto (bang_search_geometry) */
   uint32_t group_waves;                /* waves per pacing group, 4..16 (0 = 8): a workgroup's W waves form ceil(W / group_waves) groups that
                                           advance independently; pacing group index = (g * groups_per_workgroup + group) * nctx + c */
-  unsigned long long* d_prof;          /* diagnostic, host-paced form: [G][8] 100 MHz ticks thread 0 of each workgroup spent {waiting for
+  uint32_t rr_qdim;                    /* bang_k_search_exact with any_dim = 1 only: elements per row of rr_queries -- rr_D, or rr_D - 1 where the queries come without
+                                          the MIPS coordinate (the engine's D - dim_adjust); the kernel reads the elements from rr_qdim up as 0.  0 means rr_D.  (In
+                                          the four bytes of padding that lay between group_waves and the pointer below: no member moves.) */
+  unsigned long long* d_prof;         /* diagnostic, host-paced form: [G][8] 100 MHz ticks thread 0 of each workgroup spent {waiting for
                                           rows, in the front half up to the publish barrier, publishing, in sort/merge}, [4] = half-rounds; or NULL */
   uint32_t code_stride;                /* bytes between code rows in d_codes; 0 = m (see bang_iter_params) */
   uint32_t n_rows_hbm;                 /* row_layout = 1: the adjacency rows of the nodes [0, n_rows_hbm) are ALSO in device memory at d_rows_hbm */
@@ -1078,6 +1086,13 @@ int bang_insert_group_ids(const uint32_t* rows, uint32_t n, uint32_t row_stride,
  * with D % 16 == 0; D <= BANG_EXACT_MAX_D; a graph-entry stride divisible by 4 that holds the vector.  L2 only (no MIPS padding). */
 #define BANG_EXACT_MAX_D 1024u
 int bang_search_exact_supported(int dtype, uint32_t D, uint64_t entry_len);
+/* The same with bang_search_params.any_dim = 1 (engine option "any_dim"), the one statement of that layout set: float vectors of any D, 8-bit vectors
+ * with D % 4 == 0 (a packed 8-bit row of any other length is not dword aligned); 1 <= D <= BANG_EXACT_MAX_D; a stride divisible by 4 that holds the
+ * vector.  Every layout of bang_search_exact_supported is one of these.  The queries may come without the last coordinate (MIPS, rr_qdim = D - 1). */
+int bang_search_exact_anydim_supported(int dtype, uint32_t D, uint64_t entry_len);
+/* grid of a bang_k_search_exact launch that runs on the any-dimension instances (graph entries / pulled rows), as bang_search_exact_geometry */
+int bang_search_exact_anydim_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+int bang_search_exact_anydim_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 
 #ifdef __cplusplus
 }
