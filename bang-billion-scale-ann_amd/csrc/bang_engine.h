@@ -337,6 +337,7 @@ struct bang_engine {
   // bang_set_query_radii_e to bang_free
   int range_hits = 0;                  // option "range_hits": capacity of a query's hit log, 0 = off
   int any_dim = 0;                     // option "any_dim": 1 = distance = 1 also takes float vectors of any D, 8-bit vectors with D % 4 == 0 and MIPS parameters
+  int scan_any = 0;                    // option "scan_any": 1 = bang_scan_e also serves float vectors of any D, 8-bit vectors with D % 4 == 0 (D <= 1024) and MIPS parameters
   uint32_t* d_hit_ids = nullptr;       // [Qcap][range_hits] the hit log's ids; sorted and de-duplicated in place by bang_k_range_sort
   float* d_hit_dists = nullptr;        // [Qcap][range_hits] ... and distances
   float* d_radius = nullptr;           // [Qcap] the batch's radii

@@ -115,6 +115,7 @@ int bang_apply_query_filter_file_e(bang_engine_t* e, int num_queries);
 
 // bang_k_scan with a HIP event (hipEvent_t, or NULL) recorded between the scan launch and the merge of the stripes' lists (bang_scan_e's times)
 int bang_k_scan_marked(const bang_scan_params* p, void* stream, void* ev_merge);
+int bang_k_scan_any_marked(const bang_scan_params* p, uint32_t qdim, void* stream, void* ev_merge);     // the same for bang_k_scan_any
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,11 @@ static const OptionDef kOptions[] = {
      "search parameters (queries of D - 1 elements, the last coordinate read as 0), with graph = device and with the pulled rows; such an index runs on the "
      "any-dimension instances of the kernel, a layout that 0 accepts keeps today's instances bit for bit.  Refused on such an index, by name: beam > 1, "
      "labels, radii, vectors_fp16, inserts, consolidation, the scan and semantics = 1 (distance = 0 is what it was: the PQ walk's re-rank stays a launch of its own there).  0 = today's layouts only (default)"},
+    {"scan_any", "BANG_SCAN_ANY", &bang_engine::scan_any, 0, 1, INT, ANY,
+     "the exact scan (bang_scan_e): 1 = it also serves float vectors of any D, 8-bit vectors with D % 4 == 0 (1 <= D <= 1024), on both placements, and MIPS "
+     "search parameters (queries of D - 1 elements, the last coordinate read as 0), with any_dim = 1 or not; every distance is the ascending fmaf chain of "
+     "(vector - query).  A layout that 0 serves, under L2, keeps today's kernels bit for bit.  Still refused, by name: an fp16 vector table, D > 1024, 8-bit "
+     "D % 4 != 0, no resident vectors, k > 128, a distance function that is neither L2 nor MIPS.  0 = today's layouts and refusals (default)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

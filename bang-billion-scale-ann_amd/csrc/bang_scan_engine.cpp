@@ -1,7 +1,8 @@
 // bang_scan_engine.cpp -- bang_scan_e: the exact scan of a loaded index (DESIGN.md section 2 CANON 23, section 4.17).  It reads the engine's tables
 // -- the graph entries in HBM or the packed vector table, the exclusion bitmap, the removed bitmap, the label table -- and writes none of them; its
 // device temporaries live for the call.  Per chunk of <= 4096 queries, in stream order: the queries (and filters) up, bang_k_scan (the scan launch,
-// bang_k_range_sort over the stripes' lists, the output kernel), the results down.
+// bang_k_range_sort over the stripes' lists, the output kernel), the results down.  With option scan_any = 1 (CANON 25) a launch that bang_scan_check
+// refuses, or MIPS search parameters (queries of D - 1 elements), go to bang_k_scan_any instead; everything around the launch is the same.
 #include "bang_engine.h"
 
 using namespace bang;
@@ -24,16 +25,17 @@ struct Scratch {                            // device temporaries of one call, f
   }
 };
 
-int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, const void* h_queries, uint32_t nq, uint32_t k, const uint32_t* any,
-         const uint32_t* all, uint64_t* ids_out, float* dists_out, uint32_t* matched_out) {
+// any_entry: the launches go to bang_k_scan_any with queries of qdim elements (else qdim = D)
+int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, bool any_entry, uint32_t qdim, const void* h_queries, uint32_t nq, uint32_t k,
+         const uint32_t* any, const uint32_t* all, uint64_t* ids_out, float* dists_out, uint32_t* matched_out) {
   const Clock::time_point t_call = Clock::now();
-  const size_t qbytes = vec_bytes(e);
+  const size_t qbytes = (size_t)qdim * e->tsize;
   hipStream_t s = nullptr;
   Scratch sc;
   const uint32_t chunk = (uint32_t)std::min((long)QUERY_CHUNK, std::max(1L, env_long("BANG_SCAN_QUERY_CHUNK", QUERY_CHUNK)));   // test hook, clamped
   const uint32_t QC = std::min(nq, chunk);
   uint32_t tiles = 0, stripes = 0;
-  if (bang_scan_geometry(e->dtype, e->D, QC, e->N, k, &tiles, &stripes) != BANG_OK) { bang_set_error("bang_scan: no launch geometry"); return BANG_ERR_ARG; }
+  if ((any_entry ? bang_scan_any_geometry : bang_scan_geometry)(e->dtype, e->D, QC, e->N, k, &tiles, &stripes) != BANG_OK) { bang_set_error("bang_scan: no launch geometry"); return BANG_ERR_ARG; }
   const long want = env_long("BANG_SCAN_STRIPES", 0);                      // test hook, clamped
   if (want > 0) stripes = (uint32_t)std::min<long>(want, std::max<uint32_t>(1u, bang_scan_max_stripes(e->dtype, e->N, k)));
   const uint64_t scratch_bytes = bang_scan_scratch_bytes(QC, k, stripes);
@@ -68,7 +70,8 @@ int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, const voi
     p.stripes = stripes; p.d_scratch = d_scratch; p.scratch_bytes = scratch_bytes;
     p.d_ids_out = d_ids; p.d_dists_out = d_dists; p.d_matched = d_matched;
     HIP_TRY(hipEventRecord(sc.ev[0], s));
-    BANG_TRY(bang_k_scan_marked(&p, s, sc.ev[1]));
+    if (any_entry) BANG_TRY(bang_k_scan_any_marked(&p, qdim, s, sc.ev[1]));
+    else BANG_TRY(bang_k_scan_marked(&p, s, sc.ev[1]));
     HIP_TRY(hipEventRecord(sc.ev[2], s));
     // the results of this chunk: ids [n][k] are a contiguous piece of the caller's rows, distances [k][n] one piece per rank
     HIP_TRY(hipMemcpyAsync(ids_out + (size_t)q0 * k, d_ids, (size_t)n * k * 8, hipMemcpyDeviceToHost, s));
@@ -90,34 +93,54 @@ extern "C" int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq,
                            float* dists_out, uint32_t* matched_out) {
   if (!e) { bang_set_error("bang_scan: the engine is null"); return BANG_ERR_ARG; }
   if (!e->loaded) { bang_set_error("bang_scan: no index is loaded"); return BANG_ERR_ARG; }
-  BANG_TRY(refuse_on_anydim(e, "bang_scan"));
+  const bool scan_any = e->scan_any == 1;                                  // CANON 25; 0: every refusal below is what it was
+  if (!scan_any) BANG_TRY(refuse_on_anydim(e, "bang_scan"));
   if (!h_queries) { bang_set_error("bang_scan: the queries are null"); return BANG_ERR_ARG; }
   if (!ids_out || !dists_out) { bang_set_error("bang_scan: an output buffer (ids, dists) is null"); return BANG_ERR_ARG; }
   if (nq == 0 || nq > BANG_SCAN_MAX_QUERIES) { bang_set_error("bang_scan: nq = %u is outside [1, %u]", nq, BANG_SCAN_MAX_QUERIES); return BANG_ERR_ARG; }
   if (k == 0 || k > BANG_SCAN_MAX_K) { bang_set_error("bang_scan: k = %u is outside [1, %u]", k, BANG_SCAN_MAX_K); return BANG_ERR_ARG; }
   if ((any == nullptr) != (all == nullptr)) { bang_set_error("bang_scan: exactly one of any / all is given: a filter batch is both arrays, or neither"); return BANG_ERR_ARG; }
   if (any && !e->d_labels) { bang_set_error("bang_scan: filters without labels: the index has no label table (bang_set_labels_e)"); return BANG_ERR_ARG; }
-  if (e->params_set && e->distfn == BANG_DIST_MIPS) { bang_set_error("bang_scan: MIPS search parameters are set: the scan runs on L2 distances only"); return BANG_ERR_UNSUPPORTED; }
+  if (scan_any && e->params_set && e->distfn != BANG_DIST_L2 && e->distfn != BANG_DIST_MIPS) {
+    bang_set_error("bang_scan: the distance function of the search parameters is neither L2 nor MIPS: the scan has no distance for it");
+    return BANG_ERR_UNSUPPORTED;
+  }
+  const uint32_t dim_adjust = (scan_any && e->params_set && e->distfn == BANG_DIST_MIPS) ? 1u : 0u;      // as a query: bang_lane.cpp
+  if (!scan_any && e->params_set && e->distfn == BANG_DIST_MIPS) { bang_set_error("bang_scan: MIPS search parameters are set: the scan runs on L2 distances only"); return BANG_ERR_UNSUPPORTED; }
   if (e->vecs_f16) { bang_set_error("bang_scan: the vector table holds fp16 rows (option vectors_fp16): their distances are not the exact ones"); return BANG_ERR_UNSUPPORTED; }
   const uint8_t* vec_base = e->d_graph ? e->d_graph : e->d_vecs;
   const uint64_t vec_stride = e->d_graph ? e->entry_len : (uint64_t)vec_bytes(e);
   if (!vec_base) { bang_set_error("bang_scan: no resident vectors: the graph is in host RAM and the vectors were left there (option vectors = 0)"); return BANG_ERR_UNSUPPORTED; }
-  if (!bang_search_can_rerank(e->dtype, e->D, vec_stride, 0)) {
+  bool any_entry = false;
+  const uint32_t qdim = e->D - dim_adjust;
+  if (scan_any) {
+    // today's entry where it accepts the launch and the metric is L2 (the same instances, the same bits), else the any-dimension entry
+    any_entry = dim_adjust != 0u || !bang_search_can_rerank(e->dtype, e->D, vec_stride, 0);
+    if (any_entry) {
+      if (e->D > BANG_SCAN_ANY_MAX_D) { bang_set_error("bang_scan: D = %u exceeds %u, the widest vector the scan serves (option scan_any)", e->D, BANG_SCAN_ANY_MAX_D); return BANG_ERR_UNSUPPORTED; }
+      if (e->dtype != BANG_F32 && (e->D & 3u) != 0u) { bang_set_error("bang_scan: D = %u: 8-bit vectors need D %% 4 == 0 (option scan_any)", e->D); return BANG_ERR_UNSUPPORTED; }
+      if (qdim == 0u || (vec_stride & 3u) != 0 || vec_stride < (uint64_t)vec_bytes(e)) {
+        bang_set_error("bang_scan: the vector layout (dtype %d, D = %u, stride %llu, queries of %u elements) is outside option scan_any: a stride divisible by 4 that "
+                       "holds the vector, a query of at least one element", e->dtype, e->D, (unsigned long long)vec_stride, qdim);
+        return BANG_ERR_UNSUPPORTED;
+      }
+    }
+  } else if (!bang_search_can_rerank(e->dtype, e->D, vec_stride, 0)) {
     bang_set_error("bang_scan: the vector layout (dtype %d, D = %u, stride %llu) is outside bang_search_can_rerank: 8-bit vectors need D %% 16 == 0 with D / 16 a "
                    "power of two, float vectors D %% 4 == 0; D <= 256", e->dtype, e->D, (unsigned long long)vec_stride);
     return BANG_ERR_UNSUPPORTED;
   }
   if (e->dtype == BANG_F32) {
     uint64_t bad = 0;
-    if (bang_check_floats((const float*)h_queries, (uint64_t)nq * e->D, &bad) != BANG_OK) {
+    if (bang_check_floats((const float*)h_queries, (uint64_t)nq * qdim, &bad) != BANG_OK) {
       bang_set_error("bang_scan: query %llu, dimension %llu holds %g: float queries must be finite with |x| <= 2^56 (nothing was launched)",
-                     (unsigned long long)(bad / e->D), (unsigned long long)(bad % e->D), (double)((const float*)h_queries)[bad]);
+                     (unsigned long long)(bad / qdim), (unsigned long long)(bad % qdim), (double)((const float*)h_queries)[bad]);
       return BANG_ERR_ARG;
     }
   }
   BANG_TRY(ensure_device(e));
   for (double& x : e->scan_ms) x = 0;
-  const int rc = scan(e, vec_base, vec_stride, h_queries, nq, k, any, all, ids_out, dists_out, matched_out);
+  const int rc = scan(e, vec_base, vec_stride, any_entry, qdim, h_queries, nq, k, any, all, ids_out, dists_out, matched_out);
   if (rc != BANG_OK) (void)hipDeviceSynchronize();
   return rc;
 }

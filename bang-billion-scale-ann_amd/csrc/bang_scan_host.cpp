@@ -1,5 +1,6 @@
 // bang_scan_host.cpp -- the host side of bang_scan.hip (the exact scan, DESIGN.md section 2 CANON 23, section 4.17): the argument checks of a
-// bang_k_scan launch, the grid (query tiles x stripes) and the scratch size.  No HIP call and no engine in this file: the tests build it alone.
+// bang_k_scan launch, the grid (query tiles x stripes) and the scratch size; the same for bang_k_scan_any (bang_scan_any.hip, option scan_any: CANON 25).
+// No HIP call and no engine in this file: the tests build it alone.
 #include <stdint.h>
 #include <stddef.h>
 
@@ -15,6 +16,12 @@ bool scan_layout(int dtype, uint32_t D, uint64_t stride) {
   if (dtype == BANG_F32) return D >= 4u && (D & 3u) == 0u && stride >= 4ull * D;
   return (dtype == BANG_U8 || dtype == BANG_I8) && D >= 16u && (D & 15u) == 0u && (G & (G - 1u)) == 0u && stride >= D;
 }
+// the layouts of option scan_any: float vectors of any D, 8-bit vectors of whole dwords, D <= BANG_SCAN_ANY_MAX_D
+bool scan_any_layout(int dtype, uint32_t D, uint64_t stride) {
+  if ((stride & 3u) != 0 || D == 0u || D > BANG_SCAN_ANY_MAX_D) return false;
+  if (dtype == BANG_F32) return stride >= 4ull * D;
+  return (dtype == BANG_U8 || dtype == BANG_I8) && (D & 3u) == 0u && stride >= D;
+}
 uint32_t query_tile(int dtype) { return dtype == BANG_F32 ? 16u : 32u; }       // queries per workgroup
 uint32_t round_points(int dtype) { return dtype == BANG_F32 ? 256u : 128u; }   // points a workgroup takes between two cuts of its lists
 
@@ -28,9 +35,8 @@ extern "C" uint32_t bang_scan_max_stripes(int dtype, uint32_t n_nodes, uint32_t 
   return by_points < by_keys ? by_points : by_keys;
 }
 
-extern "C" int bang_scan_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes) {
-  if (!tiles || !stripes || nq == 0u || n_nodes == 0u || k == 0u || k > BANG_SCAN_MAX_K || nq > BANG_SCAN_MAX_QUERIES) return BANG_ERR_ARG;
-  if (!scan_layout(dtype, D, dtype == BANG_F32 ? 4ull * D : (uint64_t)D)) return BANG_ERR_UNSUPPORTED;
+// the grid of a launch whose layout the caller has accepted
+static void scan_grid(int dtype, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes) {
   const uint32_t qt = query_tile(dtype);
   const uint32_t t = (nq + qt - 1u) / qt;
   // about four workgroups per CU of a 256-CU device, and no stripe shorter than 16 rounds: a stripe's lists cost a sort however short it is
@@ -43,6 +49,19 @@ extern "C" int bang_scan_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n
   if (s < 1u) s = 1u;
   *tiles = t;
   *stripes = s;
+}
+
+extern "C" int bang_scan_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes) {
+  if (!tiles || !stripes || nq == 0u || n_nodes == 0u || k == 0u || k > BANG_SCAN_MAX_K || nq > BANG_SCAN_MAX_QUERIES) return BANG_ERR_ARG;
+  if (!scan_layout(dtype, D, dtype == BANG_F32 ? 4ull * D : (uint64_t)D)) return BANG_ERR_UNSUPPORTED;
+  scan_grid(dtype, nq, n_nodes, k, tiles, stripes);
+  return BANG_OK;
+}
+
+extern "C" int bang_scan_any_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes) {
+  if (!tiles || !stripes || nq == 0u || n_nodes == 0u || k == 0u || k > BANG_SCAN_MAX_K || nq > BANG_SCAN_MAX_QUERIES) return BANG_ERR_ARG;
+  if (!scan_any_layout(dtype, D, dtype == BANG_F32 ? 4ull * D : (uint64_t)D)) return BANG_ERR_UNSUPPORTED;
+  scan_grid(dtype, nq, n_nodes, k, tiles, stripes);
   return BANG_OK;
 }
 
@@ -85,5 +104,41 @@ extern "C" int bang_scan_check(const bang_scan_params* p) {
   if (!p->d_ids_out) { bang_set_error("bang_k_scan: d_ids_out is null"); return BANG_ERR_ARG; }
   if (!p->d_dists_out) { bang_set_error("bang_k_scan: d_dists_out is null"); return BANG_ERR_ARG; }
   if (!p->d_matched) { bang_set_error("bang_k_scan: d_matched is null"); return BANG_ERR_ARG; }
+  return BANG_OK;
+}
+
+extern "C" int bang_scan_any_check(const bang_scan_params* p, uint32_t qdim) {
+  if (!p) { bang_set_error("bang_k_scan_any: the parameter block is null"); return BANG_ERR_ARG; }
+  if (!p->d_vec_base || (((uintptr_t)p->d_vec_base) & 3u)) { bang_set_error("bang_k_scan_any: d_vec_base is null or not 4-byte aligned"); return BANG_ERR_ARG; }
+  if (!p->d_queries || (((uintptr_t)p->d_queries) & 3u)) { bang_set_error("bang_k_scan_any: d_queries is null or not 4-byte aligned"); return BANG_ERR_ARG; }
+  if (p->n_nodes == 0u) { bang_set_error("bang_k_scan_any: n_nodes = 0"); return BANG_ERR_ARG; }
+  if (p->nq == 0u || p->nq > BANG_SCAN_MAX_QUERIES) { bang_set_error("bang_k_scan_any: nq = %u is outside [1, %u]", p->nq, BANG_SCAN_MAX_QUERIES); return BANG_ERR_ARG; }
+  if (p->k == 0u || p->k > BANG_SCAN_MAX_K) { bang_set_error("bang_k_scan_any: k = %u is outside [1, %u]", p->k, BANG_SCAN_MAX_K); return BANG_ERR_ARG; }
+  if (p->dtype != BANG_F32 && p->dtype != BANG_U8 && p->dtype != BANG_I8) { bang_set_error("bang_k_scan_any: dtype = %u is none of uint8, int8, float", p->dtype); return BANG_ERR_UNSUPPORTED; }
+  if (p->D == 0u || p->D > BANG_SCAN_ANY_MAX_D) { bang_set_error("bang_k_scan_any: D = %u is outside [1, %u]", p->D, BANG_SCAN_ANY_MAX_D); return BANG_ERR_UNSUPPORTED; }
+  if (p->dtype != BANG_F32 && (p->D & 3u) != 0u) { bang_set_error("bang_k_scan_any: D = %u: 8-bit vectors need D %% 4 == 0 (whole dwords)", p->D); return BANG_ERR_UNSUPPORTED; }
+  if (!scan_any_layout((int)p->dtype, p->D, p->vec_stride)) {
+    bang_set_error("bang_k_scan_any: vec_stride = %llu: a stride divisible by 4 that holds the vector (D = %u)", (unsigned long long)p->vec_stride, p->D);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  if (qdim == 0u || (qdim != p->D && qdim + 1u != p->D)) { bang_set_error("bang_k_scan_any: qdim = %u: a query holds D or D - 1 (MIPS) elements, D = %u", qdim, p->D); return BANG_ERR_ARG; }
+  if ((p->d_labels == nullptr) != (p->d_filters == nullptr)) { bang_set_error("bang_k_scan_any: d_labels and d_filters come together: exactly one of them is null"); return BANG_ERR_ARG; }
+  const uint32_t most = bang_scan_max_stripes((int)p->dtype, p->n_nodes, p->k);
+  if (p->stripes > most) {
+    bang_set_error("bang_k_scan_any: stripes = %u exceeds %u: stripes * k <= %u and no stripe without a round of points", p->stripes, most, BANG_SCAN_MAX_KEYS);
+    return BANG_ERR_ARG;
+  }
+  uint32_t tiles = 0, stripes = p->stripes;
+  if (stripes == 0u) scan_grid((int)p->dtype, p->nq, p->n_nodes, p->k, &tiles, &stripes);
+  if (!p->d_scratch || (((uintptr_t)p->d_scratch) & 7u)) { bang_set_error("bang_k_scan_any: d_scratch is null or not 8-byte aligned"); return BANG_ERR_ARG; }
+  const uint64_t need = bang_scan_scratch_bytes(p->nq, p->k, stripes);
+  if (p->scratch_bytes < need) {
+    bang_set_error("bang_k_scan_any: scratch_bytes = %llu, %u stripes of %u queries at k = %u need %llu", (unsigned long long)p->scratch_bytes, stripes, p->nq, p->k,
+                   (unsigned long long)need);
+    return BANG_ERR_ARG;
+  }
+  if (!p->d_ids_out) { bang_set_error("bang_k_scan_any: d_ids_out is null"); return BANG_ERR_ARG; }
+  if (!p->d_dists_out) { bang_set_error("bang_k_scan_any: d_dists_out is null"); return BANG_ERR_ARG; }
+  if (!p->d_matched) { bang_set_error("bang_k_scan_any: d_matched is null"); return BANG_ERR_ARG; }
   return BANG_OK;
 }

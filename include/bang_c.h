@@ -293,7 +293,7 @@ int bang_get_codes_e(bang_engine_t* e, uint64_t first, uint64_t n, void* out);
  * nodes keep their vectors, and X no longer names them --, bang_insert_reuse_e hands out again and bang_unload_e drops; it is not part of an index
  * file (bang_get_removed_e / bang_set_removed_e carry it across an export). */
 int bang_consolidate_e(bang_engine_t* e, float alpha, uint64_t* out_stats4);
-/* REUSE OF REMOVED IDS (DESIGN.md section 2 CANON 24, section 4.18).  F = the nodes x < N whose bit is set in the removed bitmap, X the exclusion
+/* REUSE OF REMOVED IDS (DESIGN.md section 2 CANON 25, section 4.18).  F = the nodes x < N whose bit is set in the removed bitmap, X the exclusion
  * set at the call, E = F \ X the eligible free slots.  bang_insert_reuse_e adds the n vectors as ONE batch like bang_insert_e, at the ids
  * ids[i] = the i-th smallest element of E for i < f = min(n, |E|) and N + (i - f) behind: strictly ascending in input order, written to
  * ids_out[n].  Everything else is bang_insert_e with "N + i" read as ids[i]: the searches run on the graph as it stood (n_nodes = N; no walk
@@ -1006,7 +1006,11 @@ int bang_consolidate_group(const uint32_t* bitmap, uint32_t n_nodes, uint32_t* i
  * Refused before any HIP call, nothing written: a null engine, nothing loaded, null queries / outputs, nq = 0 or > BANG_SCAN_MAX_QUERIES, k = 0 or
  * > BANG_SCAN_MAX_K, exactly one of any / all, filters without a label table, float queries that bang_check_floats refuses (BANG_ERR_ARG); MIPS
  * search parameters, an fp16 vector table, no resident vectors, a layout outside bang_search_can_rerank (BANG_ERR_UNSUPPORTED).
- * The removed set is not part of an index file: a reloaded index is scanned with its removed nodes until bang_set_removed_e restores the set. */
+ * The removed set is not part of an index file: a reloaded index is scanned with its removed nodes until bang_set_removed_e restores the set.
+ * Option scan_any = 1 (CANON 25): the call also serves float vectors of any D, 8-bit vectors with D % 4 == 0 (D <= 1024) and MIPS search parameters
+ * -- h_queries is then [nq][D - 1], the last coordinate read as 0 --, any_dim = 1 or not; the distance is orc_exact_dist's ascending fmaf chain.
+ * A layout the call serves with 0, under L2, runs on the same kernels and returns the same bits.  Still refused: an fp16 vector table, D > 1024,
+ * 8-bit D % 4 != 0, no resident vectors, k > BANG_SCAN_MAX_K, a distance function that is neither L2 nor MIPS. */
 #define BANG_SCAN_MAX_K 128u
 #define BANG_SCAN_MAX_QUERIES (1u << 20)
 #define BANG_SCAN_MAX_KEYS 4096u              /* stripes * k: what bang_k_range_sort merges per query */
@@ -1045,10 +1049,22 @@ int bang_scan_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uin
 uint32_t bang_scan_max_stripes(int dtype, uint32_t n_nodes, uint32_t k);
 uint64_t bang_scan_scratch_bytes(uint32_t nq, uint32_t k, uint32_t stripes);
 int bang_scan_check(const bang_scan_params* p);
+/* OPTION scan_any (csrc/bang_scan_any.hip; DESIGN.md section 2 CANON 25): the scan of the layouts bang_k_scan refuses -- float vectors of any D,
+ * 8-bit vectors with D % 4 == 0, 1 <= D <= BANG_SCAN_ANY_MAX_D, vec_stride % 4 == 0 holding the vector -- and of MIPS queries: d_queries is
+ * [nq][qdim] with qdim = D, or D - 1 where the last coordinate of every query is read as 0.  A candidate's distance is the ascending
+ * fmaf(diff, diff, acc) chain from 0.0f over (float)(vector - query), for every dtype and D (an 8-bit sum beyond 2^24 is that chain's rounded value,
+ * not the integer's float image).  Everything else -- bang_scan_params, stripes, scratch, candidates, keys, outputs -- is bang_k_scan's, and a layout
+ * bang_k_scan accepts is answered with the same bits.  Refused before any HIP call with the member named: what bang_k_scan refuses (BANG_ERR_ARG), a
+ * qdim that is neither D nor D - 1 (BANG_ERR_ARG); D = 0 or > BANG_SCAN_ANY_MAX_D, 8-bit D % 4 != 0, another dtype, a stride that does not hold the
+ * vector (BANG_ERR_UNSUPPORTED).  bang_scan_any_geometry / bang_scan_any_check: the host side (csrc/bang_scan_host.cpp), as the two above. */
+#define BANG_SCAN_ANY_MAX_D 1024u
+int bang_k_scan_any(const bang_scan_params* p, uint32_t qdim, void* stream);
+int bang_scan_any_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes);
+int bang_scan_any_check(const bang_scan_params* p, uint32_t qdim);
 /* dst[w] |= src[w] for w < words, except the bits skip_mask of word skip_word (bang_consolidate_e: the removed set, without the medoid) */
 int bang_k_bitmap_or(uint32_t* d_dst, const uint32_t* d_src, uint64_t words, uint64_t skip_word, uint32_t skip_mask, void* stream);
 
-/* REUSE OF REMOVED IDS, device side (csrc/bang_reuse.hip; engine: bang_insert_reuse_e, bang_set_removed_e; DESIGN.md section 2 CANON 24, section
+/* REUSE OF REMOVED IDS, device side (csrc/bang_reuse.hip; engine: bang_insert_reuse_e, bang_set_removed_e; DESIGN.md section 2 CANON 25, section
  * 4.18).  Every entry checks its arguments before any HIP call and names the offending one.
  *
  * bang_k_bitmap_select: d_ids_out receives the min(want, total) lowest set bit positions of a & ~not below n_bits (1 .. 2^32 - 2), ascending;

@@ -9,6 +9,10 @@ alternately, one warm-up and five timed runs each, medians recorded:
   * the exact-distance walk at the smallest L of the list that reaches 90 % 10-recall@10 against the scan
   * label shares 50 / 10 / 1 % (tools/labels_sweep.py's table): the scan's time beside the filtered walk's time and its recall against the scan
   * the 8-bit kernel's share of the i8 MFMA rate: 2 N Q D operations over the scan launches' time, against 2 x the dense BF16 rate of the chip
+
+--any [--out profiles/scan_any.md]: the layouts of option scan_any instead, through the kernel entry bang_k_scan_any on a packed table of 10^6
+structured vectors (synth.make_vectors / make_queries; no graph is built, so no engine is loaded: the times are the launches' -- scan, merge, outputs --
+without the engine's copies of queries and results), against synth.knn on the same GPU; and uint8 D = 256 on scan8_any_kernel beside scan8_kernel.
 """
 import argparse
 import datetime
@@ -154,6 +158,101 @@ def one(name, log):
     return rows
 
 
+ANY_LAYOUTS = (("u8_784", 784, "uint8", 0), ("i8_100", 100, "int8", 0), ("f32_960", 960, "float", 0), ("f32_201_mips", 201, "float", 1))
+
+
+def k_scan(entry, vec, stride, dtype, D, q, qdim, k):
+    """one launch of bang_k_scan / bang_k_scan_any on device tensors -> a function that runs it and waits, and its outputs (ids [Q][k], dists [k][Q])"""
+    import ctypes as C
+    import torch
+    from bang_amd import binding as B
+    lib, Q, N = B.lib(), q.shape[0], vec.shape[0]
+    lib.bang_scan_any_geometry.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.bang_scan_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.bang_scan_scratch_bytes.restype = C.c_uint64
+    t, st = C.c_uint32(0), C.c_uint32(0)
+    assert lib.bang_scan_any_geometry(B.DTYPE_CODE[dtype], D, Q, N, k, C.byref(t), C.byref(st)) == 0
+    nbytes = int(lib.bang_scan_scratch_bytes(Q, k, st.value))
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device="cuda")
+    ids, dists = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((k, Q), dtype=torch.float32, device="cuda")
+    matched = torch.empty(Q, dtype=torch.int32, device="cuda")
+    p = B.ScanParams()
+    p.d_vec_base, p.vec_stride, p.dtype, p.D, p.n_nodes = vec.data_ptr(), stride, B.DTYPE_CODE[dtype], D, N
+    p.d_queries, p.nq, p.k, p.stripes = q.data_ptr(), Q, k, st.value
+    p.d_scratch, p.scratch_bytes, p.d_ids_out, p.d_dists_out, p.d_matched = scratch.data_ptr(), nbytes, ids.data_ptr(), dists.data_ptr(), matched.data_ptr()
+    fn = getattr(lib, entry)
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p] if entry == "bang_k_scan_any" else [C.c_void_p, C.c_void_p]
+    args = (C.byref(p), qdim, None) if entry == "bang_k_scan_any" else (C.byref(p), None)
+
+    def run():
+        assert fn(*args) == 0, lib.bang_last_error().decode()
+        torch.cuda.synchronize()
+    return run, (ids, dists), (p, scratch, matched)
+
+
+def any_rows(log):
+    import torch
+    rows = []
+    for name, D, dtype, drop in ANY_LAYOUTS:
+        x = synth.make_vectors(1_000_000, D, dtype, n_clusters=256, seed=77, device="cuda")
+        q_all = synth.make_queries(x, 10000, dtype, seed=77)
+        vec = x.contiguous() if dtype == "float" else x.to(torch.uint8 if dtype == "uint8" else torch.int8).contiguous()
+        for Q in (100, 10000):
+            qk = q_all[:Q].clone()
+            if drop:
+                qk[:, D - 1] = 0                          # the MIPS coordinate: synth.knn sees the 0 the scan reads
+            q = (qk if dtype == "float" else qk.to(vec.dtype))[:, :D - drop].contiguous()
+            for k in (10, 100):
+                run, out, keep = k_scan("bang_k_scan_any", vec, vec.shape[1] * vec.element_size(), dtype, D, q, D - drop, k)
+                res = {}
+
+                def knn():
+                    res["knn"] = synth.knn(x, qk, k)[0].cpu().numpy()
+                ms_scan, ms_knn = alternate_ms([run, knn])
+                ids, d = out[0].cpu().numpy().astype(np.uint64), out[1].cpu().numpy()
+                row = dict(workload=name, Q=Q, k=k, scan_ms=round(ms_scan, 3), knn_ms=round(ms_knn, 3), knn_ids_missed=missed(ids, d, res["knn"]), results=Q * k)
+                if dtype != "float":
+                    row["i8_mfma_share"] = round(2.0 * 1e6 * Q * D / (ms_scan * 1e-3) / I8_PEAK_OPS, 4)
+                log(json.dumps(row))
+                rows.append(row)
+        del x, vec, q_all
+        torch.cuda.empty_cache()
+    # the price of queries in LDS and a runtime KS: uint8 D = 256 and D = 1024 (the share of the MFMA rate at the widest layout)
+    for D in (256, 1024):
+        x = synth.make_vectors(1_000_000, D, "uint8", n_clusters=256, seed=78, device="cuda")
+        vec = x.to(torch.uint8).contiguous()
+        q = synth.make_queries(x, 10000, "uint8", seed=78).to(torch.uint8).contiguous()
+        runs = [k_scan("bang_k_scan_any", vec, D, "uint8", D, q, D, 10)]
+        if D == 256:
+            runs.append(k_scan("bang_k_scan", vec, D, "uint8", D, q, D, 10))
+        ms = alternate_ms([r[0] for r in runs])
+        same = len(runs) == 1 or bool(torch.equal(runs[0][1][0], runs[1][1][0]) and torch.equal(runs[0][1][1], runs[1][1][1]))
+        row = dict(workload=f"u8_{D}", Q=10000, k=10, any_ms=round(ms[0], 3), narrow_ms=round(ms[1], 3) if len(ms) > 1 else None, same_bits=same,
+                   i8_mfma_share=round(2.0 * 1e6 * 10000 * D / (ms[0] * 1e-3) / I8_PEAK_OPS, 4))
+        log(json.dumps(row))
+        rows.append(row)
+        del x, vec, q, runs
+        torch.cuda.empty_cache()
+    return rows
+
+
+def markdown_any(rows, commit):
+    out = ["# Exact scan, option scan_any (tools/scan_sweep.py --any)", "",
+           f"Commit {commit}, {datetime.date.today().isoformat()}, one MI355X, one process, contenders alternated, one warm-up and the median of {RUNS} runs.  "
+           "10^6 structured vectors in a packed table, through bang_k_scan_any: host wall time in ms of the launches (scan, merge, outputs) up to their "
+           "completion, queries and results staying on the device.", "",
+           "| layout | Q | k | scan ms | synth.knn ms | knn ids missed (tie-aware) | share of the i8 MFMA rate |", "|---|---|---|---|---|---|---|"]
+    for r in rows:
+        if "knn_ms" in r:
+            out.append(f"| {r['workload']} | {r['Q']} | {r['k']} | {r['scan_ms']} | {r['knn_ms']} | {r['knn_ids_missed']} of {r['results']} | {r.get('i8_mfma_share', '-')} |")
+    out += ["", "## scan8_any_kernel beside scan8_kernel (uint8, Q = 10 000, k = 10)", "",
+            "| layout | scan8_any_kernel ms | scan8_kernel ms | same bits | share of the i8 MFMA rate (any) |", "|---|---|---|---|---|"]
+    for r in rows:
+        if "any_ms" in r:
+            out.append(f"| {r['workload']} | {r['any_ms']} | {r['narrow_ms'] if r['narrow_ms'] is not None else '-'} | {r['same_bits']} | {r['i8_mfma_share']} |")
+    return "\n".join(out) + "\n"
+
+
 def markdown(rows, commit):
     out = [f"# Exact scan (tools/scan_sweep.py)", "",
            f"Commit {commit}, {datetime.date.today().isoformat()}, one MI355X, one process, contenders alternated, one warm-up and the median of {RUNS} runs.  "
@@ -180,7 +279,8 @@ def markdown(rows, commit):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--workloads", default="sift1m,deep1m")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scan.md"))
+    ap.add_argument("--any", action="store_true", help="the layouts of option scan_any, through the kernel entry (default --out: profiles/scan_any.md)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--json", default=None)
     ap.add_argument("--commit", default=None, help="the commit the tables are headed with (default: git rev-parse of this tree)")
     a = ap.parse_args()
@@ -191,6 +291,16 @@ def main():
         commit = a.commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or "(no git)"
     except OSError:
         commit = "(no git)"
+    a.out = a.out or os.path.join(ROOT, "profiles", "scan_any.md" if a.any else "scan.md")
+    if a.any:
+        rows = any_rows(log)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        with open(a.out, "w") as f:
+            f.write(markdown_any(rows, commit))
+        log(f"wrote {a.out}")
+        return
     rows = []
     for name in a.workloads.split(","):                   # the files are rewritten behind every workload: a run cut short keeps what it has
         rows += one(name, log)
