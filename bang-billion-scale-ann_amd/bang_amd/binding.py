@@ -154,6 +154,15 @@ class ScanParams(C.Structure):
                 ("scratch_bytes", C.c_uint64), ("d_ids_out", C.c_void_p), ("d_dists_out", C.c_void_p), ("d_matched", C.c_void_p)]
 
 
+class ScanRangeParams(C.Structure):
+    """bang_scan_range_params (include/bang_c.h): device addresses."""
+    _fields_ = [("d_vec_base", C.c_void_p), ("vec_stride", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("n_nodes", C.c_uint32),
+                ("d_queries", C.c_void_p), ("nq", C.c_uint32), ("d_radius", C.c_void_p), ("d_excluded", C.c_void_p), ("d_removed", C.c_void_p),
+                ("d_labels", C.c_void_p), ("d_filters", C.c_void_p), ("max_hits", C.c_uint32), ("runs", C.c_uint32), ("d_scratch", C.c_void_p),
+                ("scratch_bytes", C.c_uint64), ("d_hit_ids", C.c_void_p), ("d_hit_dists", C.c_void_p), ("d_offered", C.c_void_p),
+                ("d_count", C.c_void_p), ("d_matched", C.c_void_p)]
+
+
 class PruneParams(C.Structure):
     """bang_prune_params (include/bang_c.h): device addresses."""
     _fields_ = [("d_graph", C.c_void_p), ("entry_len", C.c_uint64), ("dtype", C.c_uint32), ("D", C.c_uint32), ("n_nodes", C.c_uint32),
@@ -727,6 +736,54 @@ class Engine:
                   None if words[1] is None else _vp(words[1]), _vp(ids) if ids.size else _vp(spare), _vp(dists) if dists.size else _vp(spare),
                   _vp(matched) if Q else None), "bang_scan")
         return ids, dists, matched
+
+    def scan_range(self, queries: np.ndarray, radii, max_hits: int = 1024, any=None, all=None):
+        """bang_scan_range_e: EVERY candidate of the exact scan (not excluded, not removed, matching the query's {any, all} filter) whose exact squared
+        L2 distance is <= the query's radius -- a scalar radius is broadcast; NaN or a negative radius admits nothing, +inf everything.  The first
+        max_hits (<= 4096) hits in id order are kept and sorted by distance, then id.  Returns (lims [Q + 1] u64, ids u64, dists f32, offered [Q]
+        u32, matched [Q] u32): query q's hits at [lims[q], lims[q + 1]), as range_results packs them; offered[q] > max_hits says the answer was
+        truncated, matched[q] is the number of candidates.  With or without a live allocation."""
+        q = np.ascontiguousarray(queries, dtype=NP_DTYPE[self.dtype])
+        if q.ndim != 2:
+            raise BangError(f"scan_range: queries must be [Q][D] (got shape {q.shape})")
+        Q = q.shape[0]
+        r = np.asarray(radii, dtype=np.float32)
+        r = np.full(Q, r, np.float32) if r.ndim == 0 else np.ascontiguousarray(r.reshape(-1))
+        if r.size != Q:
+            raise BangError(f"scan_range: {r.size} radii for {Q} queries")
+        words = []
+        for name, w in (("any", any), ("all", all)):
+            if w is None:
+                words.append(None)
+                continue
+            w = np.asarray(w).reshape(-1)
+            if w.dtype.kind not in "iu" or (w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF)):
+                raise BangError(f"scan_range: `{name}` must be 32-bit integer words")
+            if w.size != Q:
+                raise BangError(f"scan_range: {w.size} `{name}` words for {Q} queries")
+            words.append(np.ascontiguousarray(w, dtype=np.uint32))
+        H = max(int(max_hits), 0)
+        room = H if Q * H <= (1 << 28) else 0             # (the library refuses such a call before it writes: no buffer is needed)
+        ids, dists = np.empty((Q, room), np.uint64), np.empty((Q, room), np.float32)
+        count, offered, matched = (np.zeros(Q, np.uint32) for _ in range(3))
+        fn = lib().bang_scan_range_e
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
+        spare = np.zeros(2, dtype=np.uint64)              # an empty array still hands over an address: the library names what is wrong
+        vp = lambda a: _vp(a) if a.size else _vp(spare)   # noqa: E731
+        _check(fn(self._h, vp(q), Q, vp(r), H, None if words[0] is None else _vp(words[0]), None if words[1] is None else _vp(words[1]),
+                  vp(ids), vp(dists), vp(count), vp(offered), vp(matched)), "bang_scan_range")
+        lims = np.zeros(Q + 1, np.uint64)
+        np.cumsum(count, dtype=np.uint64, out=lims[1:])
+        keep = np.arange(H, dtype=np.uint32)[None, :] < count[:, None]
+        return lims, ids[keep], dists[keep], offered, matched
+
+    def scan_range_times(self) -> dict:
+        """milliseconds of GPU time of the last scan_range: the count pass with the prefix, the emit pass (scan_times: their sum, the sort, the call)."""
+        ms = (C.c_double * 2)()
+        fn = lib().bang_get_scan_range_times
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        _check(fn(self._h, ms), "bang_get_scan_range_times")
+        return dict(zip(("count", "emit"), ms))
 
     def scan_times(self) -> dict:
         """bang_get_scan_times: milliseconds of the last scan -- the scan launches and the merge of the stripes' lists (GPU time), the whole call."""

@@ -359,6 +359,7 @@ struct bang_engine {
                                        // bang_get_removed_e / bang_set_removed_e; NULL = nothing is removed
   uint64_t stat_reused = 0;            // bang_get_free_slots_e: removed ids that bang_insert_reuse_e handed out again, since the load
   double scan_ms[3] = {0, 0, 0};       // the last bang_scan_e: {scan launches, merge} GPU time, the whole call (host)
+  double scan_range_ms[2] = {0, 0};    // the last bang_scan_range_e: {count + prefix, emit} GPU time; scan_ms holds their sum, the sort, the call
   double consolidate_ms[4] = {0, 0, 0, 0};    // the last bang_consolidate_e: {scan + list, gather / sort / prune, clear + seed, the whole call}, host wall time
 };
 

@@ -1061,6 +1061,67 @@ int bang_scan_check(const bang_scan_params* p);
 int bang_k_scan_any(const bang_scan_params* p, uint32_t qdim, void* stream);
 int bang_scan_any_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes);
 int bang_scan_any_check(const bang_scan_params* p, uint32_t qdim);
+/* EXACT RANGE SCAN (csrc/bang_scan_range.hip, bang_scan_range_host.cpp, bang_scan_range_engine.cpp; DESIGN.md section 2 CANON 26, section 4.20):
+ * EVERY candidate within a per-query radius, by brute force.  Candidates are the exact scan's (CANON 23): ids x < N that are not excluded, were not
+ * removed by a consolidation and match the query's {any, all} filter; matched[q] is their number.  The distance is what bang_scan_e returns for
+ * the same layout (float: the ascending fmaf chain; 8-bit: the integer sum as a float up to 2^24, that chain's value beyond).  A HIT is a candidate
+ * with dist <= radius[q], a plain float compare: a NaN or negative radius admits nothing, +inf every candidate, 0.0f exact copies of the query.
+ * offered[q] counts all hits; the answer keeps the first max_hits of them IN ID ORDER and sorts those ascending by (distance bits << 32) | id;
+ * count[q] = min(offered[q], max_hits).  The answer is a function of the tables, the queries and the radii alone: no atomic decides a position.
+ * L2 only.  Served whatever option scan_any says: uint8 / int8 with D % 4 == 0, 4 <= D <= 1024; float with 1 <= D <= 1024; vec_stride % 4 == 0
+ * holding the vector; vectors from the graph entries in HBM or the packed table of the host placement.
+ * bang_scan_range_e: h_radii [nq]; ids_out [nq][max_hits] u64 and dists_out [nq][max_hits] f32, each row padded behind count_out[q] with
+ * UINT64_MAX / 3.402823E+38f; count_out, offered_out [nq]; matched_out [nq] may be NULL.  State rules, scratch and chunking as bang_scan_e's;
+ * bang_get_scan_times reports the call as a scan (count + prefix + emit launches, the sort, the whole call).  Refused before any HIP call, nothing
+ * written: a null engine, nothing loaded, null queries / radii / outputs, nq = 0 or > BANG_SCAN_MAX_QUERIES, max_hits = 0 or > BANG_RANGE_MAX_HITS,
+ * nq x max_hits > BANG_SCAN_RANGE_MAX_OUT, exactly one of any / all, filters without a label table, float queries that bang_check_floats refuses
+ * (BANG_ERR_ARG); MIPS search parameters, the fp16 vector table, D > 1024, 8-bit D % 4 != 0, no resident vectors (BANG_ERR_UNSUPPORTED). */
+#define BANG_SCAN_RANGE_MAX_OUT (1u << 28)
+#define BANG_SCAN_RANGE_MAX_RUNS 4096u
+int bang_scan_range_e(bang_engine_t* e, const void* h_queries, uint32_t nq, const float* h_radii, uint32_t max_hits, const uint32_t* any,
+                      const uint32_t* all, uint64_t* ids_out, float* dists_out, uint32_t* count_out, uint32_t* offered_out, uint32_t* matched_out);
+/* the last bang_scan_range_e, GPU time from event stamps: ms2[0] the count pass with the prefix, ms2[1] the emit pass */
+int bang_get_scan_range_times(bang_engine_t* e, double* ms2);
+/* Kernel level: device pointers only, every argument checked before any HIP call with the member named.  The points [0, n_nodes) are cut into
+ * `runs` contiguous RUNS of whole 32-point tiles, a run is one wave's share and is walked in ascending id order; a workgroup is four runs of one
+ * tile of queries (32 for 8-bit vectors, on the i8 MFMA; 16 for float vectors).  Four launches in stream order:
+ *   count   counts[q][run] = the hits of query q in the run; matched[q] += the candidates (a workgroup sum and one atomic add: a sum is order-free)
+ *   prefix  one wave per query: the exclusive scan of counts[q][.] in place, offered[q] = the total
+ *   emit    the count pass again; a hit's position is counts[q][run] + its rank among the run's hits in id order (ballot, mbcnt, a running count
+ *           per query carried from tile to tile); positions < max_hits are written to d_hit_ids / d_hit_dists [q][max_hits], nothing at or behind
+ *           min(offered, max_hits)
+ *   sort    bang_k_range_sort on those rows with cap = max_hits: d_count[q] = min(offered[q], max_hits)
+ * runs = 0: bang_scan_range_geometry's choice; else 1 <= runs <= its max_runs.  d_scratch: bang_scan_range_scratch_bytes(nq, runs) bytes, 8-byte
+ * aligned.  Codes as bang_k_scan_any's: a layout outside the ones above is BANG_ERR_UNSUPPORTED, everything else BANG_ERR_ARG. */
+typedef struct {
+  const uint8_t* d_vec_base;   /* vector of node x at d_vec_base + x * vec_stride */
+  uint64_t vec_stride;
+  uint32_t dtype, D, n_nodes;
+  const void* d_queries;       /* [nq][D] */
+  uint32_t nq;
+  const float* d_radius;       /* [nq] */
+  const uint32_t* d_excluded;  /* bitmaps of ceil(n_nodes / 32) words, or NULL */
+  const uint32_t* d_removed;
+  const uint32_t* d_labels;    /* [n_nodes] with d_filters [nq][2] {any, all}, or both NULL */
+  const uint32_t* d_filters;
+  uint32_t max_hits;           /* 1 .. BANG_RANGE_MAX_HITS */
+  uint32_t runs;
+  void* d_scratch;
+  uint64_t scratch_bytes;
+  uint32_t* d_hit_ids;         /* [nq][max_hits] */
+  float* d_hit_dists;          /* [nq][max_hits] */
+  uint32_t* d_offered;         /* [nq] */
+  uint32_t* d_count;           /* [nq] */
+  uint32_t* d_matched;         /* [nq] */
+} bang_scan_range_params;
+int bang_k_scan_range(const bang_scan_range_params* p, void* stream);
+/* Host side, no HIP call in it (csrc/bang_scan_range_host.cpp).  The geometry: tiles = ceil(nq / queries per tile); max_runs = min(ceil(n_nodes /
+ * 32), BANG_SCAN_RANGE_MAX_RUNS, max(1, 2^24 / nq)) -- never more runs than 32-point tiles, and nq x runs x 4 bytes of counts stay within 64 MB;
+ * runs = enough for eight waves per CU of a 256-CU device, ceil(2048 / tiles) rounded up to whole workgroups of four, no run shorter than 256
+ * points, clamped to [1, max_runs].  max_runs may be NULL.  BANG_ERR_ARG on a zero or null argument, BANG_ERR_UNSUPPORTED on another layout. */
+int bang_scan_range_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t* tiles, uint32_t* runs, uint32_t* max_runs);
+uint64_t bang_scan_range_scratch_bytes(uint32_t nq, uint32_t runs);      /* counts u32 [nq][runs] */
+int bang_scan_range_check(const bang_scan_range_params* p);
 /* dst[w] |= src[w] for w < words, except the bits skip_mask of word skip_word (bang_consolidate_e: the removed set, without the medoid) */
 int bang_k_bitmap_or(uint32_t* d_dst, const uint32_t* d_src, uint64_t words, uint64_t skip_word, uint32_t skip_mask, void* stream);
 
