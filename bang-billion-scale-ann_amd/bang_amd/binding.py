@@ -793,6 +793,15 @@ class Engine:
         _check(fn(self._h, ms), "bang_get_scan_times")
         return dict(zip(("scan", "merge", "total"), ms))
 
+    def scan_counters(self) -> dict:
+        """bang_get_scan_counters_e: the last scan's (query, candidate point) pairs that met the MFMA bound and those refined with the exact chain
+        (engine option scan_mfma = 1 on a float index); zeros when the scan ran on the other kernels."""
+        out = (C.c_uint64 * 2)()
+        fn = lib().bang_get_scan_counters_e
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        _check(fn(self._h, out), "bang_get_scan_counters")
+        return dict(tested=int(out[0]), refined=int(out[1]))
+
     def query_counters(self, Q: int) -> np.ndarray:
         """[Q][4] per-query {iterations (search kernel only, else 0), candidates, dist_evals, fetched} of the last query -- the
         column order of the oracle's per-query statistics."""

@@ -338,6 +338,7 @@ struct bang_engine {
   int range_hits = 0;                  // option "range_hits": capacity of a query's hit log, 0 = off
   int any_dim = 0;                     // option "any_dim": 1 = distance = 1 also takes float vectors of any D, 8-bit vectors with D % 4 == 0 and MIPS parameters
   int scan_any = 0;                    // option "scan_any": 1 = bang_scan_e also serves float vectors of any D, 8-bit vectors with D % 4 == 0 (D <= 1024) and MIPS parameters
+  int scan_mfma = 0;                   // option "scan_mfma": 1 = bang_scan_e runs float indexes on the fp32 MFMA prefilter + exact refine (bang_k_scan_f32_mfma)
   uint32_t* d_hit_ids = nullptr;       // [Qcap][range_hits] the hit log's ids; sorted and de-duplicated in place by bang_k_range_sort
   float* d_hit_dists = nullptr;        // [Qcap][range_hits] ... and distances
   float* d_radius = nullptr;           // [Qcap] the batch's radii
@@ -359,6 +360,7 @@ struct bang_engine {
                                        // bang_get_removed_e / bang_set_removed_e; NULL = nothing is removed
   uint64_t stat_reused = 0;            // bang_get_free_slots_e: removed ids that bang_insert_reuse_e handed out again, since the load
   double scan_ms[3] = {0, 0, 0};       // the last bang_scan_e: {scan launches, merge} GPU time, the whole call (host)
+  uint64_t scan_counters[2] = {0, 0};  // the last bang_scan_e on bang_k_scan_f32_mfma: pairs tested, pairs refined, summed over its launches; else zeros
   double scan_range_ms[2] = {0, 0};    // the last bang_scan_range_e: {count + prefix, emit} GPU time; scan_ms holds their sum, the sort, the call
   double consolidate_ms[4] = {0, 0, 0, 0};    // the last bang_consolidate_e: {scan + list, gather / sort / prune, clear + seed, the whole call}, host wall time
 };

@@ -116,6 +116,7 @@ int bang_apply_query_filter_file_e(bang_engine_t* e, int num_queries);
 // bang_k_scan with a HIP event (hipEvent_t, or NULL) recorded between the scan launch and the merge of the stripes' lists (bang_scan_e's times)
 int bang_k_scan_marked(const bang_scan_params* p, void* stream, void* ev_merge);
 int bang_k_scan_any_marked(const bang_scan_params* p, uint32_t qdim, void* stream, void* ev_merge);     // the same for bang_k_scan_any
+int bang_k_scan_f32_mfma_marked(const bang_scan_params* p, uint32_t qdim, uint64_t* d_counters, void* stream, void* ev_merge);     // and for bang_k_scan_f32_mfma
 // bang_k_scan_range with HIP events (or NULL) recorded in front of the emit pass and in front of the sort (bang_scan_range_e's times)
 int bang_k_scan_range_marked(const bang_scan_range_params* p, void* stream, void* ev_emit, void* ev_sort);
 

@@ -92,6 +92,11 @@ static const OptionDef kOptions[] = {
      "search parameters (queries of D - 1 elements, the last coordinate read as 0), with any_dim = 1 or not; every distance is the ascending fmaf chain of "
      "(vector - query).  A layout that 0 serves, under L2, keeps today's kernels bit for bit.  Still refused, by name: an fp16 vector table, D > 1024, 8-bit "
      "D % 4 != 0, no resident vectors, k > 128, a distance function that is neither L2 nor MIPS.  0 = today's layouts and refusals (default)"},
+    {"scan_mfma", "BANG_SCAN_MFMA", &bang_engine::scan_mfma, 0, 1, INT, ANY,
+     "the exact scan (bang_scan_e) of a float index: 1 = every launch runs on bang_k_scan_f32_mfma -- an fp32 MFMA product with a proven error bound discards "
+     "the pairs that cannot enter the answer, the ascending fmaf chain refines the rest -- for the layouts 0 serves and, with scan_any = 1, the any-dimension "
+     "layouts and MIPS; same answer bit for bit, same refusals and messages; bang_get_scan_counters_e tells pairs tested and refined.  No effect on 8-bit "
+     "indexes.  0 = the float chain kernels (default)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

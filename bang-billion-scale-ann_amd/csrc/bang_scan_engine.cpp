@@ -2,7 +2,8 @@
 // -- the graph entries in HBM or the packed vector table, the exclusion bitmap, the removed bitmap, the label table -- and writes none of them; its
 // device temporaries live for the call.  Per chunk of <= 4096 queries, in stream order: the queries (and filters) up, bang_k_scan (the scan launch,
 // bang_k_range_sort over the stripes' lists, the output kernel), the results down.  With option scan_any = 1 (CANON 25) a launch that bang_scan_check
-// refuses, or MIPS search parameters (queries of D - 1 elements), go to bang_k_scan_any instead; everything around the launch is the same.
+// refuses, or MIPS search parameters (queries of D - 1 elements), go to bang_k_scan_any instead; everything around the launch is the same.  With
+// option scan_mfma = 1 every launch of a float index goes to bang_k_scan_f32_mfma, whose counters the call sums (bang_get_scan_counters_e).
 #include "bang_engine.h"
 
 using namespace bang;
@@ -25,8 +26,10 @@ struct Scratch {                            // device temporaries of one call, f
   }
 };
 
-// any_entry: the launches go to bang_k_scan_any with queries of qdim elements (else qdim = D)
-int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, bool any_entry, uint32_t qdim, const void* h_queries, uint32_t nq, uint32_t k,
+enum Entry { NARROW = 0, ANY = 1, MFMA = 2 };
+
+// entry: ANY / MFMA: the launches go to bang_k_scan_any / bang_k_scan_f32_mfma with queries of qdim elements (NARROW: qdim = D)
+int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, Entry entry, uint32_t qdim, const void* h_queries, uint32_t nq, uint32_t k,
          const uint32_t* any, const uint32_t* all, uint64_t* ids_out, float* dists_out, uint32_t* matched_out) {
   const Clock::time_point t_call = Clock::now();
   const size_t qbytes = (size_t)qdim * e->tsize;
@@ -35,14 +38,19 @@ int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, bool any_
   const uint32_t chunk = (uint32_t)std::min((long)QUERY_CHUNK, std::max(1L, env_long("BANG_SCAN_QUERY_CHUNK", QUERY_CHUNK)));   // test hook, clamped
   const uint32_t QC = std::min(nq, chunk);
   uint32_t tiles = 0, stripes = 0;
-  if ((any_entry ? bang_scan_any_geometry : bang_scan_geometry)(e->dtype, e->D, QC, e->N, k, &tiles, &stripes) != BANG_OK) { bang_set_error("bang_scan: no launch geometry"); return BANG_ERR_ARG; }
+  const int geo = entry == MFMA ? bang_scan_f32_mfma_geometry(e->D, QC, e->N, k, &tiles, &stripes)
+                               : (entry == ANY ? bang_scan_any_geometry : bang_scan_geometry)(e->dtype, e->D, QC, e->N, k, &tiles, &stripes);
+  if (geo != BANG_OK) { bang_set_error("bang_scan: no launch geometry"); return BANG_ERR_ARG; }
   const long want = env_long("BANG_SCAN_STRIPES", 0);                      // test hook, clamped
-  if (want > 0) stripes = (uint32_t)std::min<long>(want, std::max<uint32_t>(1u, bang_scan_max_stripes(e->dtype, e->N, k)));
+  const uint32_t most = entry == MFMA ? bang_scan_f32_mfma_max_stripes(e->N, k) : bang_scan_max_stripes(e->dtype, e->N, k);
+  if (want > 0) stripes = (uint32_t)std::min<long>(want, std::max<uint32_t>(1u, most));
   const uint64_t scratch_bytes = bang_scan_scratch_bytes(QC, k, stripes);
   uint8_t *d_q = nullptr, *d_scratch = nullptr;
   uint32_t *d_flt = nullptr, *d_matched = nullptr;
   uint64_t* d_ids = nullptr;
   float* d_dists = nullptr;
+  uint64_t* d_counters = nullptr;
+  if (entry == MFMA) BANG_TRY(sc.get(&d_counters, 2));
   BANG_TRY(sc.get(&d_q, (size_t)QC * qbytes));
   BANG_TRY(sc.get(&d_scratch, (size_t)scratch_bytes));
   BANG_TRY(sc.get(&d_ids, (size_t)QC * k));
@@ -70,18 +78,22 @@ int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, bool any_
     p.stripes = stripes; p.d_scratch = d_scratch; p.scratch_bytes = scratch_bytes;
     p.d_ids_out = d_ids; p.d_dists_out = d_dists; p.d_matched = d_matched;
     HIP_TRY(hipEventRecord(sc.ev[0], s));
-    if (any_entry) BANG_TRY(bang_k_scan_any_marked(&p, qdim, s, sc.ev[1]));
+    if (entry == MFMA) BANG_TRY(bang_k_scan_f32_mfma_marked(&p, qdim, d_counters, s, sc.ev[1]));
+    else if (entry == ANY) BANG_TRY(bang_k_scan_any_marked(&p, qdim, s, sc.ev[1]));
     else BANG_TRY(bang_k_scan_marked(&p, s, sc.ev[1]));
     HIP_TRY(hipEventRecord(sc.ev[2], s));
     // the results of this chunk: ids [n][k] are a contiguous piece of the caller's rows, distances [k][n] one piece per rank
     HIP_TRY(hipMemcpyAsync(ids_out + (size_t)q0 * k, d_ids, (size_t)n * k * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpy2DAsync(dists_out + q0, (size_t)nq * 4, d_dists, (size_t)n * 4, (size_t)n * 4, k, hipMemcpyDeviceToHost, s));
     if (matched_out) HIP_TRY(hipMemcpyAsync(matched_out + q0, d_matched, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    uint64_t counters[2] = {0, 0};
+    if (d_counters) HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     float a = 0, b = 0;
     HIP_TRY(hipEventElapsedTime(&a, sc.ev[0], sc.ev[1]));
     HIP_TRY(hipEventElapsedTime(&b, sc.ev[1], sc.ev[2]));
     ms_scan += a; ms_merge += b;
+    e->scan_counters[0] += counters[0]; e->scan_counters[1] += counters[1];
   }
   e->scan_ms[0] = ms_scan; e->scan_ms[1] = ms_merge; e->scan_ms[2] = ms_since(t_call);
   return BANG_OK;
@@ -140,7 +152,9 @@ extern "C" int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq,
   }
   BANG_TRY(ensure_device(e));
   for (double& x : e->scan_ms) x = 0;
-  const int rc = scan(e, vec_base, vec_stride, any_entry, qdim, h_queries, nq, k, any, all, ids_out, dists_out, matched_out);
+  e->scan_counters[0] = e->scan_counters[1] = 0;
+  const Entry entry = (e->scan_mfma == 1 && e->dtype == BANG_F32) ? MFMA : any_entry ? ANY : NARROW;
+  const int rc = scan(e, vec_base, vec_stride, entry, qdim, h_queries, nq, k, any, all, ids_out, dists_out, matched_out);
   if (rc != BANG_OK) (void)hipDeviceSynchronize();
   return rc;
 }
@@ -148,5 +162,11 @@ extern "C" int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq,
 extern "C" int bang_get_scan_times(bang_engine_t* e, double* ms3) {
   if (!e || !ms3) return BANG_ERR_ARG;
   memcpy(ms3, e->scan_ms, sizeof(e->scan_ms));
+  return BANG_OK;
+}
+
+extern "C" int bang_get_scan_counters_e(bang_engine_t* e, uint64_t out[2]) {
+  if (!e || !out) return BANG_ERR_ARG;
+  out[0] = e->scan_counters[0]; out[1] = e->scan_counters[1];
   return BANG_OK;
 }

@@ -1061,6 +1061,22 @@ int bang_scan_check(const bang_scan_params* p);
 int bang_k_scan_any(const bang_scan_params* p, uint32_t qdim, void* stream);
 int bang_scan_any_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes);
 int bang_scan_any_check(const bang_scan_params* p, uint32_t qdim);
+/* OPTION scan_mfma (csrc/bang_scan_mfma.hip, bang_scan_mfma_host.cpp): the float side of the scan on the fp32 MFMA.  Float
+ * vectors with 1 <= D <= BANG_SCAN_ANY_MAX_D, vec_stride % 4 == 0 holding the vector, queries [nq][qdim] with qdim = D or D - 1 (MIPS).  A matrix
+ * product d~ = |q|^2 + |p|^2 - 2 q.p with a proven error bound E discards the pairs whose d~ - E is above the query's threshold distance; every other
+ * pair is refined with the ascending fmaf chain of (vector - query), and only those keys are offered: the answer is bang_k_scan's / bang_k_scan_any's
+ * bit for bit.  Workgroups take 32 queries and rounds of 128 points: stripes <= bang_scan_f32_mfma_max_stripes(n_nodes, k) = min(ceil(n_nodes / 128),
+ * BANG_SCAN_MAX_KEYS / k); scratch as bang_scan_scratch_bytes.  d_counters (may be NULL; 8-byte aligned): two 64-bit sums of the launch, written in
+ * stream order -- {pairs tested: (query, candidate point) pairs that met the bound; pairs refined}.  Refused before any HIP call with the cause
+ * named: what bang_k_scan_any refuses, and a dtype that is not float (BANG_ERR_UNSUPPORTED).  bang_scan_f32_mfma_geometry / _check / _max_stripes:
+ * the host side, no HIP call in it. */
+int bang_k_scan_f32_mfma(const bang_scan_params* p, uint32_t qdim, uint64_t* d_counters, void* stream);
+int bang_scan_f32_mfma_geometry(uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* stripes);
+uint32_t bang_scan_f32_mfma_max_stripes(uint32_t n_nodes, uint32_t k);
+int bang_scan_f32_mfma_check(const bang_scan_params* p, uint32_t qdim);
+/* the counters of the last bang_scan_e, summed over its launches: out[0] pairs tested, out[1] pairs refined; zeros when it ran on the other kernels
+ * (option scan_mfma = 0, or an 8-bit index) */
+int bang_get_scan_counters_e(bang_engine_t* e, uint64_t out[2]);
 /* EXACT RANGE SCAN (csrc/bang_scan_range.hip, bang_scan_range_host.cpp, bang_scan_range_engine.cpp; DESIGN.md section 2 CANON 26, section 4.20):
  * EVERY candidate within a per-query radius, by brute force.  Candidates are the exact scan's (CANON 23): ids x < N that are not excluded, were not
  * removed by a consolidation and match the query's {any, all} filter; matched[q] is their number.  The distance is what bang_scan_e returns for

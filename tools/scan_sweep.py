@@ -13,6 +13,9 @@ alternately, one warm-up and five timed runs each, medians recorded:
 --any [--out profiles/scan_any.md]: the layouts of option scan_any instead, through the kernel entry bang_k_scan_any on a packed table of 10^6
 structured vectors (synth.make_vectors / make_queries; no graph is built, so no engine is loaded: the times are the launches' -- scan, merge, outputs --
 without the engine's copies of queries and results), against synth.knn on the same GPU; and uint8 D = 256 on scan8_any_kernel beside scan8_kernel.
+
+--mfma [--out profiles/scan_mfma.md]: option scan_mfma's kernel entry bang_k_scan_f32_mfma beside the float chain kernel (bang_k_scan_any) and synth.knn
+on float D = 74, 201 (MIPS) and 960, the three alternating, with the share of the tested pairs that the exact refine took.
 """
 import argparse
 import datetime
@@ -167,15 +170,21 @@ def k_scan(entry, vec, stride, dtype, D, q, qdim, k):
     import torch
     from bang_amd import binding as B
     lib, Q, N = B.lib(), q.shape[0], vec.shape[0]
+    mfma = entry == "bang_k_scan_f32_mfma"
     lib.bang_scan_any_geometry.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.bang_scan_f32_mfma_geometry.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.bang_scan_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     lib.bang_scan_scratch_bytes.restype = C.c_uint64
     t, st = C.c_uint32(0), C.c_uint32(0)
-    assert lib.bang_scan_any_geometry(B.DTYPE_CODE[dtype], D, Q, N, k, C.byref(t), C.byref(st)) == 0
+    if mfma:
+        assert lib.bang_scan_f32_mfma_geometry(D, Q, N, k, C.byref(t), C.byref(st)) == 0
+    else:
+        assert lib.bang_scan_any_geometry(B.DTYPE_CODE[dtype], D, Q, N, k, C.byref(t), C.byref(st)) == 0
     nbytes = int(lib.bang_scan_scratch_bytes(Q, k, st.value))
     scratch = torch.empty(nbytes // 8, dtype=torch.int64, device="cuda")
     ids, dists = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((k, Q), dtype=torch.float32, device="cuda")
     matched = torch.empty(Q, dtype=torch.int32, device="cuda")
+    counters = torch.zeros(2, dtype=torch.int64, device="cuda")          # bang_k_scan_f32_mfma: pairs tested, pairs refined
     p = B.ScanParams()
     p.d_vec_base, p.vec_stride, p.dtype, p.D, p.n_nodes = vec.data_ptr(), stride, B.DTYPE_CODE[dtype], D, N
     p.d_queries, p.nq, p.k, p.stripes = q.data_ptr(), Q, k, st.value
@@ -183,11 +192,13 @@ def k_scan(entry, vec, stride, dtype, D, q, qdim, k):
     fn = getattr(lib, entry)
     fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p] if entry == "bang_k_scan_any" else [C.c_void_p, C.c_void_p]
     args = (C.byref(p), qdim, None) if entry == "bang_k_scan_any" else (C.byref(p), None)
+    if mfma:
+        fn.argtypes, args = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], (C.byref(p), qdim, C.c_void_p(counters.data_ptr()), None)
 
     def run():
         assert fn(*args) == 0, lib.bang_last_error().decode()
         torch.cuda.synchronize()
-    return run, (ids, dists), (p, scratch, matched)
+    return run, (ids, dists), (p, scratch, matched, counters)
 
 
 def any_rows(log):
@@ -236,6 +247,52 @@ def any_rows(log):
     return rows
 
 
+MFMA_LAYOUTS = (("f32_74", 74, 0), ("f32_201_mips", 201, 1), ("f32_960", 960, 0))
+
+
+def mfma_rows(log):
+    import torch
+    rows = []
+    for name, D, drop in MFMA_LAYOUTS:
+        x = synth.make_vectors(1_000_000, D, "float", n_clusters=256, seed=77, device="cuda").contiguous()
+        q_all = synth.make_queries(x, 10000, "float", seed=77)
+        for Q in (100, 10000):
+            qk = q_all[:Q].clone()
+            if drop:
+                qk[:, D - 1] = 0                          # the MIPS coordinate: synth.knn sees the 0 the scan reads
+            q = qk[:, :D - drop].contiguous()
+            for k in (10, 100):
+                chain, out_c, keep_c = k_scan("bang_k_scan_any", x, 4 * D, "float", D, q, D - drop, k)
+                mfma, out_m, keep_m = k_scan("bang_k_scan_f32_mfma", x, 4 * D, "float", D, q, D - drop, k)
+                res = {}
+
+                def knn():
+                    res["knn"] = synth.knn(x, qk, k)[0].cpu().numpy()
+                ms_chain, ms_mfma, ms_knn = alternate_ms([chain, mfma, knn])
+                tested, refined = (int(v) for v in keep_m[3].cpu())
+                row = dict(workload=name, Q=Q, k=k, chain_ms=round(ms_chain, 3), mfma_ms=round(ms_mfma, 3), knn_ms=round(ms_knn, 3),
+                           same_bits=bool(torch.equal(out_c[0], out_m[0]) and torch.equal(out_c[1].view(torch.int32), out_m[1].view(torch.int32))),
+                           tested=tested, refined_share=round(refined / max(tested, 1), 5), stripes=int(keep_m[0].stripes))
+                log(json.dumps(row))
+                rows.append(row)
+                del chain, mfma, out_c, out_m, keep_c, keep_m
+        del x, q_all
+        torch.cuda.empty_cache()
+    return rows
+
+
+def markdown_mfma(rows, commit):
+    out = ["# Exact scan, option scan_mfma (tools/scan_sweep.py --mfma)", "",
+           f"Commit {commit}, {datetime.date.today().isoformat()}, one MI355X, one process, the three contenders alternated, one warm-up and the median of {RUNS} runs.  "
+           "10^6 structured float vectors in a packed table, through the kernel entries: host wall time in ms of the launches (scan, merge, outputs) up to "
+           "their completion, queries and results staying on the device.  chain: bang_k_scan_any (scan_f32_any_kernel); mfma: bang_k_scan_f32_mfma; "
+           "refined share: pairs the exact chain ran for over pairs tested.", "",
+           "| layout | Q | k | chain ms | mfma ms | synth.knn ms | same bits | refined share | stripes (mfma) |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        out.append(f"| {r['workload']} | {r['Q']} | {r['k']} | {r['chain_ms']} | {r['mfma_ms']} | {r['knn_ms']} | {r['same_bits']} | {r['refined_share']} | {r['stripes']} |")
+    return "\n".join(out) + "\n"
+
+
 def markdown_any(rows, commit):
     out = ["# Exact scan, option scan_any (tools/scan_sweep.py --any)", "",
            f"Commit {commit}, {datetime.date.today().isoformat()}, one MI355X, one process, contenders alternated, one warm-up and the median of {RUNS} runs.  "
@@ -280,6 +337,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--workloads", default="sift1m,deep1m")
     ap.add_argument("--any", action="store_true", help="the layouts of option scan_any, through the kernel entry (default --out: profiles/scan_any.md)")
+    ap.add_argument("--mfma", action="store_true", help="option scan_mfma's kernel entry beside the float chain kernel and synth.knn (default --out: profiles/scan_mfma.md)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--json", default=None)
     ap.add_argument("--commit", default=None, help="the commit the tables are headed with (default: git rev-parse of this tree)")
@@ -291,14 +349,14 @@ def main():
         commit = a.commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or "(no git)"
     except OSError:
         commit = "(no git)"
-    a.out = a.out or os.path.join(ROOT, "profiles", "scan_any.md" if a.any else "scan.md")
-    if a.any:
-        rows = any_rows(log)
+    a.out = a.out or os.path.join(ROOT, "profiles", "scan_mfma.md" if a.mfma else "scan_any.md" if a.any else "scan.md")
+    if a.any or a.mfma:
+        rows = mfma_rows(log) if a.mfma else any_rows(log)
         if a.json:
             with open(a.json, "w") as f:
                 json.dump(rows, f, indent=1)
         with open(a.out, "w") as f:
-            f.write(markdown_any(rows, commit))
+            f.write((markdown_mfma if a.mfma else markdown_any)(rows, commit))
         log(f"wrote {a.out}")
         return
     rows = []
