@@ -709,7 +709,8 @@ class Engine:
         {any, all} filter if filters are given -- by brute force, in the distance bits the search returns; equal distances in id order.
         Returns (ids [Q][k] u64, dists [k][Q] f32, matched [Q] u32: the candidates of each query); short answers are padded with
         UINT64_MAX / 3.402823E+38.  With or without a live allocation.  Engine option scan_any = 1: float vectors of any D, 8-bit vectors with
-        D % 4 == 0 (D <= 1024) and, under MIPS search parameters, queries [Q][D - 1] (the last coordinate is read as 0)."""
+        D % 4 == 0 (D <= 1024) and, under MIPS search parameters, queries [Q][D - 1] (the last coordinate is read as 0).  Engine option
+        scan_radix = 1: k up to 4096 (k > 128 by radix select over the keys, the same bits) on those layouts; 2: every k on those kernels."""
         q = np.ascontiguousarray(queries, dtype=NP_DTYPE[self.dtype])
         if q.ndim != 2:
             raise BangError(f"scan: queries must be [Q][D] (got shape {q.shape})")

@@ -1,4 +1,4 @@
-"""Ground truth from the engine itself: python -m bang_amd.truth [--scan-any] <index prefix> <query.bin> <K> <out.bin>
+"""Ground truth from the engine itself: python -m bang_amd.truth [--scan-any] [--scan-radix] <index prefix> <query.bin> <K> <out.bin>
 
 Loads the index (graph in HBM; BANG_EXCLUDE_FILE / BANG_LABEL_FILE are read as by every load), runs the exact scan WITHOUT filters (Engine.scan:
 every live point, the distance bits the search returns, equal distances in id order) and writes the harness's ground-truth file (formats.write_truthset:
@@ -6,7 +6,8 @@ i32 Q, i32 K, ids u32 [Q][K], distances f32 [Q][K]).  K <= 128; an answer shorte
 0xFFFFFFFF at distance 3.402823E+38.  The vector type is read from <prefix>_disk_metadata.bin.  The ids of BANG_EXCLUDE_FILE are left out of the
 truth; a label table is loaded and changes nothing, since the tool applies no filter (filtered truth: compute(..., any=, all=)).
 --scan-any sets the engine option scan_any = 1: float vectors of any D, 8-bit vectors with D % 4 == 0, D <= 1024 (MIPS truth: compute(..., scan_any=1,
-mips=True) with queries of D - 1 elements).  Without the flag the tool is what it was.
+mips=True) with queries of D - 1 elements).  --scan-radix sets the engine option scan_radix = 1: K up to 4096 (a recall@1000 truth set), K > 128 on the
+radix-select kernels, and the layouts of --scan-any.  Without the flags the tool is what it was.
 """
 from __future__ import annotations
 
@@ -43,6 +44,9 @@ def main(argv=None) -> int:
     if "--scan-any" in argv:
         argv.remove("--scan-any")
         options["scan_any"] = 1
+    if "--scan-radix" in argv:
+        argv.remove("--scan-radix")
+        options["scan_radix"] = 1
     if len(argv) != 4:
         print(__doc__.strip().splitlines()[0], file=sys.stderr)
         return 2

@@ -338,6 +338,7 @@ struct bang_engine {
   int range_hits = 0;                  // option "range_hits": capacity of a query's hit log, 0 = off
   int any_dim = 0;                     // option "any_dim": 1 = distance = 1 also takes float vectors of any D, 8-bit vectors with D % 4 == 0 and MIPS parameters
   int scan_any = 0;                    // option "scan_any": 1 = bang_scan_e also serves float vectors of any D, 8-bit vectors with D % 4 == 0 (D <= 1024) and MIPS parameters
+  int scan_radix = 0;                  // option "scan_radix": 1 = bang_scan_e takes k <= 4096, k > 128 on the radix-select kernels (bang_k_scan_radix); 2 = every k on them
   int scan_mfma = 0;                   // option "scan_mfma": 1 = bang_scan_e runs float indexes on the fp32 MFMA prefilter + exact refine (bang_k_scan_f32_mfma)
   uint32_t* d_hit_ids = nullptr;       // [Qcap][range_hits] the hit log's ids; sorted and de-duplicated in place by bang_k_range_sort
   float* d_hit_dists = nullptr;        // [Qcap][range_hits] ... and distances

@@ -119,6 +119,8 @@ int bang_k_scan_any_marked(const bang_scan_params* p, uint32_t qdim, void* strea
 int bang_k_scan_f32_mfma_marked(const bang_scan_params* p, uint32_t qdim, uint64_t* d_counters, void* stream, void* ev_merge);     // and for bang_k_scan_f32_mfma
 // bang_k_scan_range with HIP events (or NULL) recorded in front of the emit pass and in front of the sort (bang_scan_range_e's times)
 int bang_k_scan_range_marked(const bang_scan_range_params* p, void* stream, void* ev_emit, void* ev_sort);
+// bang_k_scan_radix with a HIP event (or NULL) recorded between the last pick pass and the emit pass (bang_scan_e's times)
+int bang_k_scan_radix_marked(const bang_scan_params* p, uint32_t qdim, void* stream, void* ev_merge);
 
 #ifdef __cplusplus
 }

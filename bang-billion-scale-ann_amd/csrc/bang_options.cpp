@@ -97,6 +97,13 @@ static const OptionDef kOptions[] = {
      "the pairs that cannot enter the answer, the ascending fmaf chain refines the rest -- for the layouts 0 serves and, with scan_any = 1, the any-dimension "
      "layouts and MIPS; same answer bit for bit, same refusals and messages; bang_get_scan_counters_e tells pairs tested and refined.  No effect on 8-bit "
      "indexes.  0 = the float chain kernels (default)"},
+    {"scan_radix", "BANG_SCAN_RADIX", &bang_engine::scan_radix, 0, 2, INT, ANY,
+     "the exact scan (bang_scan_e) by radix select over the distance keys (bang_k_scan_radix): 1 = k up to 4096 is accepted, k > 128 runs on those "
+     "kernels and k <= 128 keeps today's kernels and bits; 2 = every k runs on them (parity tests, measurements).  With 1 or 2 the scan serves uint8 / "
+     "int8 vectors with D % 4 == 0, float vectors of any D (1 <= D <= 1024), both placements, and MIPS search parameters (queries of D - 1 elements), "
+     "whatever scan_any says -- what the other kernels refuse runs on the radix kernels --, and scan_mfma does not apply to such a launch.  Same "
+     "answer bit for bit.  Still refused, by name: an fp16 vector table, D > 1024, 8-bit D % 4 != 0, no resident vectors, k > 4096.  0 = today's "
+     "kernels and refusals (default)"},
     {"semantics", "BANG_SEMANTICS", &bang_engine::semantics, 0, 1, INT, BEFORE_ALLOC,
      "0 = the walk of the reference's BANG_Base (default), 1 = that of its BANG_Inmemory: the parent is the first unvisited worklist entry after the "
      "merge, the loop stops at iteration L + 119 (candidate log L + 120).  1 needs graph = device, search != 0, persistent != 0, the LDS pivot table "

@@ -3,7 +3,9 @@
 // device temporaries live for the call.  Per chunk of <= 4096 queries, in stream order: the queries (and filters) up, bang_k_scan (the scan launch,
 // bang_k_range_sort over the stripes' lists, the output kernel), the results down.  With option scan_any = 1 (CANON 25) a launch that bang_scan_check
 // refuses, or MIPS search parameters (queries of D - 1 elements), go to bang_k_scan_any instead; everything around the launch is the same.  With
-// option scan_mfma = 1 every launch of a float index goes to bang_k_scan_f32_mfma, whose counters the call sums (bang_get_scan_counters_e).
+// option scan_mfma = 1 every launch of a float index goes to bang_k_scan_f32_mfma, whose counters the call sums (bang_get_scan_counters_e).  With
+// option scan_radix >= 1 the call takes k <= 4096 and the layouts of scan_any; k > 128 (2: every k), and what the other entries refuse, go to
+// bang_k_scan_radix, whose `stripes` are runs and whose scratch does not depend on them.
 #include "bang_engine.h"
 
 using namespace bang;
@@ -26,9 +28,9 @@ struct Scratch {                            // device temporaries of one call, f
   }
 };
 
-enum Entry { NARROW = 0, ANY = 1, MFMA = 2 };
+enum Entry { NARROW = 0, ANY = 1, MFMA = 2, RADIX = 3 };
 
-// entry: ANY / MFMA: the launches go to bang_k_scan_any / bang_k_scan_f32_mfma with queries of qdim elements (NARROW: qdim = D)
+// entry: ANY / MFMA / RADIX: the launches go to bang_k_scan_any / bang_k_scan_f32_mfma / bang_k_scan_radix with queries of qdim elements (NARROW: qdim = D)
 int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, Entry entry, uint32_t qdim, const void* h_queries, uint32_t nq, uint32_t k,
          const uint32_t* any, const uint32_t* all, uint64_t* ids_out, float* dists_out, uint32_t* matched_out) {
   const Clock::time_point t_call = Clock::now();
@@ -37,14 +39,15 @@ int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, Entry ent
   Scratch sc;
   const uint32_t chunk = (uint32_t)std::min((long)QUERY_CHUNK, std::max(1L, env_long("BANG_SCAN_QUERY_CHUNK", QUERY_CHUNK)));   // test hook, clamped
   const uint32_t QC = std::min(nq, chunk);
-  uint32_t tiles = 0, stripes = 0;
-  const int geo = entry == MFMA ? bang_scan_f32_mfma_geometry(e->D, QC, e->N, k, &tiles, &stripes)
+  uint32_t tiles = 0, stripes = 0, max_runs = 0;
+  const int geo = entry == RADIX ? bang_scan_radix_geometry(e->dtype, e->D, QC, e->N, k, &tiles, &stripes, &max_runs)
+                  : entry == MFMA ? bang_scan_f32_mfma_geometry(e->D, QC, e->N, k, &tiles, &stripes)
                                : (entry == ANY ? bang_scan_any_geometry : bang_scan_geometry)(e->dtype, e->D, QC, e->N, k, &tiles, &stripes);
   if (geo != BANG_OK) { bang_set_error("bang_scan: no launch geometry"); return BANG_ERR_ARG; }
   const long want = env_long("BANG_SCAN_STRIPES", 0);                      // test hook, clamped
-  const uint32_t most = entry == MFMA ? bang_scan_f32_mfma_max_stripes(e->N, k) : bang_scan_max_stripes(e->dtype, e->N, k);
+  const uint32_t most = entry == RADIX ? max_runs : entry == MFMA ? bang_scan_f32_mfma_max_stripes(e->N, k) : bang_scan_max_stripes(e->dtype, e->N, k);
   if (want > 0) stripes = (uint32_t)std::min<long>(want, std::max<uint32_t>(1u, most));
-  const uint64_t scratch_bytes = bang_scan_scratch_bytes(QC, k, stripes);
+  const uint64_t scratch_bytes = entry == RADIX ? bang_scan_radix_scratch_bytes(QC, k, stripes) : bang_scan_scratch_bytes(QC, k, stripes);
   uint8_t *d_q = nullptr, *d_scratch = nullptr;
   uint32_t *d_flt = nullptr, *d_matched = nullptr;
   uint64_t* d_ids = nullptr;
@@ -78,7 +81,8 @@ int scan(bang_engine* e, const uint8_t* vec_base, uint64_t vec_stride, Entry ent
     p.stripes = stripes; p.d_scratch = d_scratch; p.scratch_bytes = scratch_bytes;
     p.d_ids_out = d_ids; p.d_dists_out = d_dists; p.d_matched = d_matched;
     HIP_TRY(hipEventRecord(sc.ev[0], s));
-    if (entry == MFMA) BANG_TRY(bang_k_scan_f32_mfma_marked(&p, qdim, d_counters, s, sc.ev[1]));
+    if (entry == RADIX) BANG_TRY(bang_k_scan_radix_marked(&p, qdim, s, sc.ev[1]));
+    else if (entry == MFMA) BANG_TRY(bang_k_scan_f32_mfma_marked(&p, qdim, d_counters, s, sc.ev[1]));
     else if (entry == ANY) BANG_TRY(bang_k_scan_any_marked(&p, qdim, s, sc.ev[1]));
     else BANG_TRY(bang_k_scan_marked(&p, s, sc.ev[1]));
     HIP_TRY(hipEventRecord(sc.ev[2], s));
@@ -105,12 +109,15 @@ extern "C" int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq,
                            float* dists_out, uint32_t* matched_out) {
   if (!e) { bang_set_error("bang_scan: the engine is null"); return BANG_ERR_ARG; }
   if (!e->loaded) { bang_set_error("bang_scan: no index is loaded"); return BANG_ERR_ARG; }
-  const bool scan_any = e->scan_any == 1;                                  // CANON 25; 0: every refusal below is what it was
+  const int radix = e->scan_radix;                                         // 1: k > 128 on the radix kernels, 2: every k; 0: nothing below changes
+  const bool scan_any = e->scan_any == 1 || radix >= 1;                    // CANON 25; neither option: every refusal below is what it was
+  const char* const wide_opt = e->scan_any == 1 ? "scan_any" : "scan_radix";
+  const uint32_t max_k = radix >= 1 ? BANG_SCAN_RADIX_MAX_K : BANG_SCAN_MAX_K;
   if (!scan_any) BANG_TRY(refuse_on_anydim(e, "bang_scan"));
   if (!h_queries) { bang_set_error("bang_scan: the queries are null"); return BANG_ERR_ARG; }
   if (!ids_out || !dists_out) { bang_set_error("bang_scan: an output buffer (ids, dists) is null"); return BANG_ERR_ARG; }
   if (nq == 0 || nq > BANG_SCAN_MAX_QUERIES) { bang_set_error("bang_scan: nq = %u is outside [1, %u]", nq, BANG_SCAN_MAX_QUERIES); return BANG_ERR_ARG; }
-  if (k == 0 || k > BANG_SCAN_MAX_K) { bang_set_error("bang_scan: k = %u is outside [1, %u]", k, BANG_SCAN_MAX_K); return BANG_ERR_ARG; }
+  if (k == 0 || k > max_k) { bang_set_error("bang_scan: k = %u is outside [1, %u]", k, max_k); return BANG_ERR_ARG; }
   if ((any == nullptr) != (all == nullptr)) { bang_set_error("bang_scan: exactly one of any / all is given: a filter batch is both arrays, or neither"); return BANG_ERR_ARG; }
   if (any && !e->d_labels) { bang_set_error("bang_scan: filters without labels: the index has no label table (bang_set_labels_e)"); return BANG_ERR_ARG; }
   if (scan_any && e->params_set && e->distfn != BANG_DIST_L2 && e->distfn != BANG_DIST_MIPS) {
@@ -123,17 +130,20 @@ extern "C" int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq,
   const uint8_t* vec_base = e->d_graph ? e->d_graph : e->d_vecs;
   const uint64_t vec_stride = e->d_graph ? e->entry_len : (uint64_t)vec_bytes(e);
   if (!vec_base) { bang_set_error("bang_scan: no resident vectors: the graph is in host RAM and the vectors were left there (option vectors = 0)"); return BANG_ERR_UNSUPPORTED; }
-  bool any_entry = false;
+  bool any_entry = false, radix_entry = radix == 2 || (radix == 1 && k > BANG_SCAN_MAX_K);
   const uint32_t qdim = e->D - dim_adjust;
   if (scan_any) {
-    // today's entry where it accepts the launch and the metric is L2 (the same instances, the same bits), else the any-dimension entry
-    any_entry = dim_adjust != 0u || !bang_search_can_rerank(e->dtype, e->D, vec_stride, 0);
-    if (any_entry) {
-      if (e->D > BANG_SCAN_ANY_MAX_D) { bang_set_error("bang_scan: D = %u exceeds %u, the widest vector the scan serves (option scan_any)", e->D, BANG_SCAN_ANY_MAX_D); return BANG_ERR_UNSUPPORTED; }
-      if (e->dtype != BANG_F32 && (e->D & 3u) != 0u) { bang_set_error("bang_scan: D = %u: 8-bit vectors need D %% 4 == 0 (option scan_any)", e->D); return BANG_ERR_UNSUPPORTED; }
+    // today's entry where it accepts the launch and the metric is L2 (the same instances, the same bits), else the any-dimension entry -- or, where
+    // option scan_any is off, the radix entry, which serves the same layouts
+    const bool wide = dim_adjust != 0u || !bang_search_can_rerank(e->dtype, e->D, vec_stride, 0);
+    any_entry = wide && e->scan_any == 1;
+    if (wide && !any_entry) radix_entry = true;
+    if (wide) {
+      if (e->D > BANG_SCAN_ANY_MAX_D) { bang_set_error("bang_scan: D = %u exceeds %u, the widest vector the scan serves (option %s)", e->D, BANG_SCAN_ANY_MAX_D, wide_opt); return BANG_ERR_UNSUPPORTED; }
+      if (e->dtype != BANG_F32 && (e->D & 3u) != 0u) { bang_set_error("bang_scan: D = %u: 8-bit vectors need D %% 4 == 0 (option %s)", e->D, wide_opt); return BANG_ERR_UNSUPPORTED; }
       if (qdim == 0u || (vec_stride & 3u) != 0 || vec_stride < (uint64_t)vec_bytes(e)) {
-        bang_set_error("bang_scan: the vector layout (dtype %d, D = %u, stride %llu, queries of %u elements) is outside option scan_any: a stride divisible by 4 that "
-                       "holds the vector, a query of at least one element", e->dtype, e->D, (unsigned long long)vec_stride, qdim);
+        bang_set_error("bang_scan: the vector layout (dtype %d, D = %u, stride %llu, queries of %u elements) is outside option %s: a stride divisible by 4 that "
+                       "holds the vector, a query of at least one element", e->dtype, e->D, (unsigned long long)vec_stride, qdim, wide_opt);
         return BANG_ERR_UNSUPPORTED;
       }
     }
@@ -153,7 +163,7 @@ extern "C" int bang_scan_e(bang_engine_t* e, const void* h_queries, uint32_t nq,
   BANG_TRY(ensure_device(e));
   for (double& x : e->scan_ms) x = 0;
   e->scan_counters[0] = e->scan_counters[1] = 0;
-  const Entry entry = (e->scan_mfma == 1 && e->dtype == BANG_F32) ? MFMA : any_entry ? ANY : NARROW;
+  const Entry entry = radix_entry ? RADIX : (e->scan_mfma == 1 && e->dtype == BANG_F32) ? MFMA : any_entry ? ANY : NARROW;
   const int rc = scan(e, vec_base, vec_stride, entry, qdim, h_queries, nq, k, any, all, ids_out, dists_out, matched_out);
   if (rc != BANG_OK) (void)hipDeviceSynchronize();
   return rc;

@@ -1077,6 +1077,32 @@ int bang_scan_f32_mfma_check(const bang_scan_params* p, uint32_t qdim);
 /* the counters of the last bang_scan_e, summed over its launches: out[0] pairs tested, out[1] pairs refined; zeros when it ran on the other kernels
  * (option scan_mfma = 0, or an 8-bit index) */
 int bang_get_scan_counters_e(bang_engine_t* e, uint64_t out[2]);
+/* OPTION scan_radix (csrc/bang_scan_radix.hip, bang_scan_radix_host.cpp): the exact scan for 1 <= k <= BANG_SCAN_RADIX_MAX_K
+ * by radix select over the keys (distance bits << 32) | id -- no list per query, so k is not bound by LDS.  Same candidates, distances, keys, outputs
+ * and padding as bang_k_scan / bang_k_scan_any (CANON 23), the same bits for every k <= BANG_SCAN_MAX_K, whatever the grid.  Layouts: uint8 / int8
+ * with D % 4 == 0, float with any D, 1 <= D <= BANG_SCAN_ANY_MAX_D, vec_stride % 4 == 0 holding the vector; d_queries is [nq][qdim] with qdim = D, or
+ * D - 1 (MIPS: the last coordinate read as 0).  p->stripes is read as RUNS, bang_k_scan_range's split: contiguous runs of whole 32-point tiles, one
+ * wave each, four runs and one tile of queries per workgroup; 0: bang_scan_radix_geometry's choice, else 1 <= runs <= its max_runs.  Launches in
+ * stream order, nothing read back: init; per 8-bit digit -- four over the distance bits, then the id digits that n_nodes - 1 reaches -- a HISTOGRAM
+ * pass (the products again; keys under the query's prefix count their digit, per-workgroup LDS histograms flushed with vector atomic adds) and a
+ * PICK pass (the digit where the cumulative count crosses the remaining rank; a query is RESOLVED once the chosen bin is needed whole, and passes
+ * without an unresolved query exit at once); an EMIT pass (keys <= the query's bound appended to its row of k); bang_k_range_sort; the outputs.
+ * d_scratch: bang_scan_radix_scratch_bytes(nq, k, runs) bytes, 8-byte aligned (per-query state, 256 bins and the row: independent of runs).
+ * Refused before any HIP call with the member named, codes as bang_k_scan_any's: k = 0 or > BANG_SCAN_RADIX_MAX_K, a qdim that is neither D nor
+ * D - 1, runs > max_runs, a short scratch, null or misaligned pointers (BANG_ERR_ARG); D = 0 or > 1024, 8-bit D % 4 != 0, another dtype, a stride
+ * that does not hold the vector (BANG_ERR_UNSUPPORTED).  bang_scan_radix_geometry / _scratch_bytes / _check: the host side, no HIP call in it;
+ * max_runs = min(ceil(n_nodes / 32), BANG_SCAN_RANGE_MAX_RUNS) may be NULL.
+ * Engine option scan_radix: 0 = bang_scan_e is what it was; 1 = it accepts k <= BANG_SCAN_RADIX_MAX_K and sends k > BANG_SCAN_MAX_K, and the
+ * layouts and MIPS parameters that the other kernels refuse under the engine's scan_any, to these kernels; 2 = every launch.  With 1 or 2 the
+ * layouts above are served whatever scan_any says and option scan_mfma does not apply to such a launch; bang_get_scan_times reports histogram +
+ * pick passes as the scan and emit + sort + outputs as the merge.  Still refused: the fp16 table, no resident vectors, D > 1024, 8-bit
+ * D % 4 != 0, k > BANG_SCAN_RADIX_MAX_K. */
+#define BANG_SCAN_RADIX_MAX_K 4096u
+#define BANG_SCAN_RADIX_BINS 256u
+int bang_k_scan_radix(const bang_scan_params* p, uint32_t qdim, void* stream);
+int bang_scan_radix_geometry(int dtype, uint32_t D, uint32_t nq, uint32_t n_nodes, uint32_t k, uint32_t* tiles, uint32_t* runs, uint32_t* max_runs);
+uint64_t bang_scan_radix_scratch_bytes(uint32_t nq, uint32_t k, uint32_t runs);
+int bang_scan_radix_check(const bang_scan_params* p, uint32_t qdim);
 /* EXACT RANGE SCAN (csrc/bang_scan_range.hip, bang_scan_range_host.cpp, bang_scan_range_engine.cpp; DESIGN.md section 2 CANON 26, section 4.20):
  * EVERY candidate within a per-query radius, by brute force.  Candidates are the exact scan's (CANON 23): ids x < N that are not excluded, were not
  * removed by a consolidation and match the query's {any, all} filter; matched[q] is their number.  The distance is what bang_scan_e returns for

@@ -16,6 +16,10 @@ without the engine's copies of queries and results), against synth.knn on the sa
 
 --mfma [--out profiles/scan_mfma.md]: option scan_mfma's kernel entry bang_k_scan_f32_mfma beside the float chain kernel (bang_k_scan_any) and synth.knn
 on float D = 74, 201 (MIPS) and 960, the three alternating, with the share of the tested pairs that the exact refine took.
+
+--radix [--out profiles/scan_radix.md]: option scan_radix's kernel entry bang_k_scan_radix on packed tables of uint8 D = 128, float D = 96 and int8
+D = 100: at k = 10 / 100 beside the entry the scan takes today (bang_k_scan, bang_k_scan_any for D = 100), at k = 1000 / 4096 beside synth.knn, with
+the digit passes a launch needed and the share of its queries that went on into id digits (read from the launch's scratch).
 """
 import argparse
 import datetime
@@ -170,17 +174,21 @@ def k_scan(entry, vec, stride, dtype, D, q, qdim, k):
     import torch
     from bang_amd import binding as B
     lib, Q, N = B.lib(), q.shape[0], vec.shape[0]
-    mfma = entry == "bang_k_scan_f32_mfma"
+    mfma, radix = entry == "bang_k_scan_f32_mfma", entry == "bang_k_scan_radix"
+    lib.bang_scan_radix_geometry.argtypes = [C.c_int] + [C.c_uint32] * 4 + [C.c_void_p] * 3
+    lib.bang_scan_radix_scratch_bytes.argtypes, lib.bang_scan_radix_scratch_bytes.restype = [C.c_uint32] * 3, C.c_uint64
     lib.bang_scan_any_geometry.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.bang_scan_f32_mfma_geometry.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.bang_scan_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     lib.bang_scan_scratch_bytes.restype = C.c_uint64
     t, st = C.c_uint32(0), C.c_uint32(0)
-    if mfma:
+    if radix:
+        assert lib.bang_scan_radix_geometry(B.DTYPE_CODE[dtype], D, Q, N, k, C.byref(t), C.byref(st), None) == 0
+    elif mfma:
         assert lib.bang_scan_f32_mfma_geometry(D, Q, N, k, C.byref(t), C.byref(st)) == 0
     else:
         assert lib.bang_scan_any_geometry(B.DTYPE_CODE[dtype], D, Q, N, k, C.byref(t), C.byref(st)) == 0
-    nbytes = int(lib.bang_scan_scratch_bytes(Q, k, st.value))
+    nbytes = int((lib.bang_scan_radix_scratch_bytes if radix else lib.bang_scan_scratch_bytes)(Q, k, st.value))
     scratch = torch.empty(nbytes // 8, dtype=torch.int64, device="cuda")
     ids, dists = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((k, Q), dtype=torch.float32, device="cuda")
     matched = torch.empty(Q, dtype=torch.int32, device="cuda")
@@ -190,8 +198,9 @@ def k_scan(entry, vec, stride, dtype, D, q, qdim, k):
     p.d_queries, p.nq, p.k, p.stripes = q.data_ptr(), Q, k, st.value
     p.d_scratch, p.scratch_bytes, p.d_ids_out, p.d_dists_out, p.d_matched = scratch.data_ptr(), nbytes, ids.data_ptr(), dists.data_ptr(), matched.data_ptr()
     fn = getattr(lib, entry)
-    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p] if entry == "bang_k_scan_any" else [C.c_void_p, C.c_void_p]
-    args = (C.byref(p), qdim, None) if entry == "bang_k_scan_any" else (C.byref(p), None)
+    with_qdim = entry in ("bang_k_scan_any", "bang_k_scan_radix")
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p] if with_qdim else [C.c_void_p, C.c_void_p]
+    args = (C.byref(p), qdim, None) if with_qdim else (C.byref(p), None)
     if mfma:
         fn.argtypes, args = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], (C.byref(p), qdim, C.c_void_p(counters.data_ptr()), None)
 
@@ -245,6 +254,72 @@ def any_rows(log):
         del x, vec, q, runs
         torch.cuda.empty_cache()
     return rows
+
+
+RADIX_LAYOUTS = (("u8_128", 128, "uint8", "bang_k_scan"), ("f32_96", 96, "float", "bang_k_scan"), ("i8_100", 100, "int8", "bang_k_scan_any"))
+
+
+def radix_rows(log):
+    """bang_k_scan_radix beside today's entry (k <= 128) and beside synth.knn (k > 128)"""
+    import torch
+    rows = []
+    for name, D, dtype, today in RADIX_LAYOUTS:
+        x = synth.make_vectors(1_000_000, D, dtype, n_clusters=256, seed=77, device="cuda")
+        q_all = synth.make_queries(x, 10000, dtype, seed=77)
+        vec = x.contiguous() if dtype == "float" else x.to(torch.uint8 if dtype == "uint8" else torch.int8).contiguous()
+        stride = vec.shape[1] * vec.element_size()
+        for Q in (100, 10000):
+            qk = q_all[:Q].clone()
+            q = (qk if dtype == "float" else qk.to(vec.dtype)).contiguous()
+            for k in (10, 100, 1000, 4096):
+                run, out, keep = k_scan("bang_k_scan_radix", vec, stride, dtype, D, q, D, k)
+                res = {}
+                if k <= 128:
+                    other, out_o, keep_o = k_scan(today, vec, stride, dtype, D, q, D, k)
+                else:
+                    def other():
+                        res["knn"] = synth.knn(x, qk, k)[0].cpu().numpy()
+                ms_radix, ms_other = alternate_ms([run, other])
+                fixed = keep[1].view(torch.int32)[(2 + 256 + 1) * Q:(2 + 256 + 2) * Q].cpu().numpy()     # the scratch layout: bang_scan_radix_scratch_bytes
+                skipped = 4 - (int(vec.shape[0] - 1).bit_length() + 7) // 8     # id digits above the width of N - 1: never launched
+                digits = int(fixed.max()) // 8                             # the lowest digit any query of the launch still needed
+                row = dict(workload=name, Q=Q, k=k, radix_ms=round(ms_radix, 3), passes=digits - (skipped if digits > 4 else 0), id_digit_share=round(float((fixed > 32).mean()), 5),
+                           runs=int(keep[0].stripes))
+                if k <= 128:
+                    row.update(today=today, today_ms=round(ms_other, 3),
+                               same_bits=bool(torch.equal(out[0], out_o[0]) and torch.equal(out[1].view(torch.int32), out_o[1].view(torch.int32))))
+                    del other, out_o, keep_o
+                else:
+                    ids, d = out[0].cpu().numpy().astype(np.uint64), out[1].cpu().numpy()
+                    row.update(knn_ms=round(ms_other, 3), knn_ids_missed=missed(ids, d, res["knn"]), results=Q * k)
+                log(json.dumps(row))
+                rows.append(row)
+                del run, out, keep
+                torch.cuda.empty_cache()
+        del x, vec, q_all
+        torch.cuda.empty_cache()
+    return rows
+
+
+def markdown_radix(rows, commit):
+    out = ["# Exact scan, option scan_radix (tools/scan_sweep.py --radix)", "",
+           f"Commit {commit}, {datetime.date.today().isoformat()}, one MI355X, one process, the two contenders alternated, one warm-up and the median of {RUNS} runs.  "
+           "10^6 structured vectors in a packed table, through the kernel entries: host wall time in ms of the launches up to their completion, queries "
+           "and results staying on the device.  passes: the histogram + pick passes that still had an unresolved query (of the 4 distance digits and the "
+           "3 id digits 10^6 points need); id digits: the share of the queries whose rank-k distance was tied beyond the cut.", "",
+           "## k <= 128: beside the entry the scan takes today", "",
+           "| layout | Q | k | radix ms | today ms | today's entry | same bits | passes | id digits | runs |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        if "today_ms" in r:
+            out.append(f"| {r['workload']} | {r['Q']} | {r['k']} | {r['radix_ms']} | {r['today_ms']} | {r['today']} | {r['same_bits']} | {r['passes']} | "
+                       f"{r['id_digit_share']} | {r['runs']} |")
+    out += ["", "## k > 128: beside synth.knn on the same GPU", "",
+            "| layout | Q | k | radix ms | synth.knn ms | knn ids missed (tie-aware) | passes | id digits | runs |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        if "knn_ms" in r:
+            out.append(f"| {r['workload']} | {r['Q']} | {r['k']} | {r['radix_ms']} | {r['knn_ms']} | {r['knn_ids_missed']} of {r['results']} | {r['passes']} | "
+                       f"{r['id_digit_share']} | {r['runs']} |")
+    return "\n".join(out) + "\n"
 
 
 MFMA_LAYOUTS = (("f32_74", 74, 0), ("f32_201_mips", 201, 1), ("f32_960", 960, 0))
@@ -338,6 +413,7 @@ def main():
     ap.add_argument("--workloads", default="sift1m,deep1m")
     ap.add_argument("--any", action="store_true", help="the layouts of option scan_any, through the kernel entry (default --out: profiles/scan_any.md)")
     ap.add_argument("--mfma", action="store_true", help="option scan_mfma's kernel entry beside the float chain kernel and synth.knn (default --out: profiles/scan_mfma.md)")
+    ap.add_argument("--radix", action="store_true", help="option scan_radix's kernel entry beside today's entries and synth.knn (default --out: profiles/scan_radix.md)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--json", default=None)
     ap.add_argument("--commit", default=None, help="the commit the tables are headed with (default: git rev-parse of this tree)")
@@ -349,14 +425,14 @@ def main():
         commit = a.commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or "(no git)"
     except OSError:
         commit = "(no git)"
-    a.out = a.out or os.path.join(ROOT, "profiles", "scan_mfma.md" if a.mfma else "scan_any.md" if a.any else "scan.md")
-    if a.any or a.mfma:
-        rows = mfma_rows(log) if a.mfma else any_rows(log)
+    a.out = a.out or os.path.join(ROOT, "profiles", "scan_radix.md" if a.radix else "scan_mfma.md" if a.mfma else "scan_any.md" if a.any else "scan.md")
+    if a.any or a.mfma or a.radix:
+        rows = radix_rows(log) if a.radix else mfma_rows(log) if a.mfma else any_rows(log)
         if a.json:
             with open(a.json, "w") as f:
                 json.dump(rows, f, indent=1)
         with open(a.out, "w") as f:
-            f.write((markdown_mfma if a.mfma else markdown_any)(rows, commit))
+            f.write((markdown_radix if a.radix else markdown_mfma if a.mfma else markdown_any)(rows, commit))
         log(f"wrote {a.out}")
         return
     rows = []
