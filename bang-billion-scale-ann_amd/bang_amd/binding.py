@@ -497,7 +497,8 @@ class Engine:
 
     def set_filters(self, any, all):
         """bang_set_query_filters_e: the filters of the batches to come, one {any, all} pair per query: node x matches when
-        (any == 0 or labels[x] & any) and labels[x] & all == all.  After alloc; kept until replaced, cleared or free."""
+        (any == 0 or labels[x] & any) and labels[x] & all == all.  After alloc; kept until replaced, cleared or free.  An index of the wide vector
+        layouts (D > 256, 8-bit D / 16 not a power of two) takes filters with Engine(..., labels_wide=1): bang_k_search_exact_labels_wide."""
         words = []
         for name, w in (("any", any), ("all", all)):
             w = np.asarray(w).reshape(-1)

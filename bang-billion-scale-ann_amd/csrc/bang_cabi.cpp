@@ -178,7 +178,8 @@ extern "C" int bang_set_query_filters_e(bang_engine_t* e, const uint32_t* any, c
   }
   if (e->beam > 1) { bang_set_error("%s: filters on labels are not available with option beam = %d: the beam kernel keeps no result list", what, e->beam); return BANG_ERR_UNSUPPORTED; }
   if (e->vecs_f16 && !dev_graph) { bang_set_error("%s: filters on labels are not available with vectors_fp16 = 1: the label-filter kernel reads float / 8-bit rows", what); return BANG_ERR_UNSUPPORTED; }
-  if (!bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e), 0)) {
+  // (option labels_wide = 1: the wide layouts have their label-filter instances, bang_k_search_exact_labels_wide; run_exact routes on the layout)
+  if (e->labels_wide != 1 && !bang_search_can_rerank(e->dtype, e->D, dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e), 0)) {
     bang_set_error("%s: filters on labels are not available on the wide vector layouts (dtype %d, D = %u): 8-bit vectors need D / 16 a power of two, D <= 256",
                    what, e->dtype, e->D);
     return BANG_ERR_UNSUPPORTED;

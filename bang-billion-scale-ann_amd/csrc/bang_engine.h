@@ -336,7 +336,8 @@ struct bang_engine {
   // range search (option range_hits + bang_set_query_radii_e): the hit buffers live from bang_alloc to bang_free, the radii from
   // bang_set_query_radii_e to bang_free
   int range_hits = 0;                  // option "range_hits": capacity of a query's hit log, 0 = off
-  int any_dim = 0;                     // option "any_dim": 1 = distance = 1 also takes float vectors of any D, 8-bit vectors with D % 4 == 0 and MIPS parameters
+  int labels_wide = 0;                 // option "labels_wide": 1 = a filtered batch on a wide vector layout runs on bang_k_search_exact_labels_wide
+  int any_dim = 0;                     // option "any_dim":1 = distance = 1 also takes float vectors of any D, 8-bit vectors with D % 4 == 0 and MIPS parameters
   int scan_any = 0;                    // option "scan_any": 1 = bang_scan_e also serves float vectors of any D, 8-bit vectors with D % 4 == 0 (D <= 1024) and MIPS parameters
   int scan_radix = 0;                  // option "scan_radix": 1 = bang_scan_e takes k <= 4096, k > 128 on the radix-select kernels (bang_k_scan_radix); 2 = every k on them
   int scan_mfma = 0;                   // option "scan_mfma": 1 = bang_scan_e runs float indexes on the fp32 MFMA prefilter + exact refine (bang_k_scan_f32_mfma)

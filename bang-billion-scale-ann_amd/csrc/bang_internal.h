@@ -105,6 +105,10 @@ int bang_k_search_exact_beam_pull(const bang_search_params* p, uint32_t beam, vo
 // BANG_EXACT_PULL, bang_search_exact_labels_pull.o), handed bang_k_search_exact_labels' checked arguments
 int bang_k_search_exact_labels_hbm(const bang_search_params* p, const bang_label_filter* f, void* stream);
 int bang_k_search_exact_labels_pull(const bang_search_params* p, const bang_label_filter* f, void* stream);
+// the label-filter instances of the wide layouts (the same source built with BANG_EXACT_WIDE and BANG_EXACT_LABELS as bang_search_exact_wide_labels.o
+// and, with BANG_EXACT_PULL, bang_search_exact_wide_labels_pull.o), handed bang_k_search_exact_labels_wide's checked arguments
+int bang_k_search_exact_wide_labels(const bang_search_params* p, const bang_label_filter* f, void* stream);
+int bang_k_search_exact_wide_labels_pull(const bang_search_params* p, const bang_label_filter* f, void* stream);
 // the range-search instances (the same source built with BANG_EXACT_RANGE as bang_search_exact_range.o and, with BANG_EXACT_PULL,
 // bang_search_exact_range_pull.o), handed bang_k_search_exact_range's checked arguments
 int bang_k_search_exact_range_hbm(const bang_search_params* p, const bang_range_out* r, void* stream);

@@ -249,7 +249,10 @@ static int run_exact(bang_engine* e, Lane& ln, const RunFacts& r, const bang_ite
   } else if (filtered) {
     bang_label_filter lf;
     lf.d_labels = e->d_labels; lf.d_filters = e->d_qfilters; lf.d_excluded = r.masked ? e->d_excl : nullptr; lf.d_matched = e->d_matched;
-    BANG_TRY(bang_k_search_exact_labels(&sp, &lf, ln.s_main));
+    // option labels_wide = 1: a layout of the wide instances takes their label-filter form; every other launch is what it was
+    const bool wide = e->labels_wide == 1 && !bang_search_can_rerank(e->dtype, e->D, r.dev_graph ? e->entry_len : (uint64_t)vec_table_stride(e), 0);
+    if (wide) BANG_TRY(bang_k_search_exact_labels_wide(&sp, &lf, ln.s_main));
+    else BANG_TRY(bang_k_search_exact_labels(&sp, &lf, ln.s_main));
     ++ln.label_launches;
   } else if (e->beam > 1) BANG_TRY(bang_k_search_exact_beam(&sp, (uint32_t)e->beam, ln.s_main));   // up to beam parents per iteration (bang_search_beam.hip)
   else BANG_TRY(bang_k_search_exact(&sp, ln.s_main));

@@ -82,6 +82,11 @@ static const OptionDef kOptions[] = {
      "the same walk and returns, beside its k results, every evaluated node within the query's radius (squared L2), sorted by distance then id "
      "(bang_get_range_results); the first range_hits hits in evaluation order are kept, bang_get_range_counts tells when there were more.  Refused: "
      "distance = 0, beam > 1, vectors_fp16 = 1 and the wide layouts (D > 256, 8-bit D / 16 not a power of two).  0 = off (default)"},
+    {"labels_wide", "BANG_LABELS_WIDE", &bang_engine::labels_wide, 0, 1, INT, BEFORE_ALLOC,
+     "distance = 1 only: 1 = filters on labels (bang_set_query_filters_e) are also accepted on the wide vector layouts -- D > 256, 8-bit D / 16 not a power of "
+     "two -- with graph = device and with the pulled rows; a filtered batch there runs on bang_k_search_exact_labels_wide (the same walk, result list and matched "
+     "counts).  Still refused, by name: beam > 1, vectors_fp16 = 1, radii with filters, the PQ walks, an any_dim = 1 index of the any-dimension instances.  "
+     "0 = today's refusals, word for word (default)"},
     {"any_dim", "BANG_ANY_DIM", &bang_engine::any_dim, 0, 1, INT, BEFORE_ALLOC,
      "distance = 1 only: 1 = the exact-distance walk also takes float vectors of any D, 8-bit vectors with D % 4 == 0 (D <= 1024; SPACEV's 100 bytes) and MIPS "
      "search parameters (queries of D - 1 elements, the last coordinate read as 0), with graph = device and with the pulled rows; such an index runs on the "

@@ -43,6 +43,13 @@
 //    merged into the worklist, those that match -- and are not in the exclusion bitmap -- are compacted in input order, with the distance bits the
 //    walk computed, and go through the same sort_and_merge into the result list.  The results are the first k entries of that list
 //    (CANON 18).  Everything it adds sits under BANG_EXACT_LABELS.
+//  * LABEL FILTERS ON THE WIDE LAYOUTS (BANG_EXACT_WIDE with BANG_EXACT_LABELS, with and without BANG_EXACT_PULL; entry
+//    bang_k_search_exact_labels_wide; engine option labels_wide).  The wide walk, bit for bit, with the result list of CANON 18.  A wave's LDS is
+//    [worklist][result list][144 words of sort scratch][row tile] (bang_exact_dist.h); the result list lives as long as the query, so it shares
+//    no word with the tile.  The label word of survivor i -- and its word of the exclusion bitmap -- is requested by lane i in front of the first
+//    tile's loads of that survivor's pass (exact_dist_wide), so it is back when the first tile is staged: the match is tested right there and kept
+//    as a 64-bit lane mask in scalar registers -- the chain that follows carries no vector register for it, and the walk gains no wait.  The masks
+//    then drive the compaction and the second sort_and_merge of the narrow form.  Everything it adds sits under the two macros together.
 //  * RANGE SEARCH (BANG_EXACT_RANGE, with and without BANG_EXACT_PULL; the narrow layouts only; entry bang_k_search_exact_range).  The same walk,
 //    bit for bit, and the same results; beside them every query collects a HIT LOG in HBM: in EVERY iteration -- the first with its seed list and the
 //    cap iteration, whose survivors are not merged, included -- the survivors with distance <= d_radius[query] that are not in the exclusion bitmap are
@@ -74,7 +81,7 @@
 #error "BANG_EXACT_F16 builds the narrow pulled-rows instance only"
 #endif
 #if defined(BANG_EXACT_LABELS) && defined(BANG_EXACT_WIDE)
-#error "BANG_EXACT_LABELS builds the narrow instances only"
+#define EXACT_WIDE_LABELS 1         // label filters on the wide layouts: the match is tested inside exact_dist_wide, under the first tile's wait
 #endif
 #if defined(BANG_EXACT_LABELS) && defined(BANG_EXACT_F16)
 #error "BANG_EXACT_LABELS builds the narrow instances on float / 8-bit rows only"
@@ -98,6 +105,10 @@
 #define EXACT_TAG _anydim_pull
 #elif defined(BANG_EXACT_ANYDIM)
 #define EXACT_TAG _anydim
+#elif defined(EXACT_WIDE_LABELS) && defined(BANG_EXACT_PULL)
+#define EXACT_TAG _wide_labels_pull
+#elif defined(EXACT_WIDE_LABELS)
+#define EXACT_TAG _wide_labels
 #elif defined(BANG_EXACT_WIDE) && defined(BANG_EXACT_PULL)
 #define EXACT_TAG _wide_pull
 #elif defined(BANG_EXACT_WIDE)
@@ -311,17 +322,42 @@ __device__ __forceinline__ uint32_t tile_word(uint32_t s, uint32_t c) { return 1
 
 __device__ __forceinline__ int rdlane(int v, uint32_t l) { return __builtin_amdgcn_readlane(v, (int)l); }
 
+#ifdef EXACT_WIDE_LABELS
+// The label test of a wide launch (CANON 18), made inside exact_dist_wide.  In: the label table, the exclusion bitmap (or null) and the query's
+// {any, all}.  Out: mm0 -- bit l set when survivor l of the first 64 matches and is not excluded -- and mm1, bit 0 for the seed list's 65th id.
+// Lane l requests label word and bitmap word of its survivor IN FRONT of the first tile's loads of the pass; loads return in order, so both are
+// back when the first tile is staged (turn(0): the wait the walk makes anyway) and the test runs there, once per pass.  Wave-uniform masks: they
+// sit in scalar registers across the chain.
+struct WideMatch {
+  const uint32_t GAS* labels;
+  const uint32_t GAS* excluded;
+  uint32_t f_any, f_all;
+  uint64_t mm0, mm1;
+};
+#endif
+
 // exact distances of the n survivors (ids in LDS: sid[0, n)) -> dist[0, n) in LDS.  DT == BANG_F32: qr[t] holds query element 64 t + lane.
 // 8-bit: qw = the query's 16-byte piece `lane`, qq the sum of its squares.  Every lane of the wave executes.
 template <int DT>
 __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64_t entry_len, uint32_t vec_bytes, uint32_t D, const uint32_t* sid,
-                                                uint32_t n, float* dist, uint32_t* tile, const float (&qr)[EXACT_QREGS], u32x4a qw, int qq, int lane) {
+                                                uint32_t n, float* dist, uint32_t* tile, const float (&qr)[EXACT_QREGS], u32x4a qw, int qq, int lane
+#ifdef EXACT_WIDE_LABELS
+                                                , WideMatch& wm
+#endif
+                                                ) {
   constexpr bool SG = (DT == BANG_I8);
   const uint32_t T = (vec_bytes + 63u) >> 6;                      // 64-byte tiles per row
   const uint32_t ls = (uint32_t)lane >> 2, lc = (uint32_t)lane & 3u;   // fetch: row ls + 16 u, piece lc
   for (uint32_t i0 = 0; i0 < n; i0 += WAVE) {                     // (uniform; a second pass for the 65th id of the seed list only)
     const uint32_t np = n - i0 < WAVE ? n - i0 : WAVE;
     u32x4a st[4] = {};
+#ifdef EXACT_WIDE_LABELS
+    // survivor i0 + lane's label word and its word of the exclusion bitmap, requested with -- in front of -- its row's first tile below (every id
+    // is < n_nodes: the row check of the walk, and bang_k_search_exact_labels_wide refuses n_nodes == 0)
+    const uint32_t my = sid[i0 + ((uint32_t)lane < np ? (uint32_t)lane : 0u)];
+    uint32_t lab = 0, exw = 0;
+    if ((uint32_t)lane < np) { lab = wm.labels[my]; if (wm.excluded) exw = wm.excluded[my >> 5]; }
+#endif
 #ifdef BANG_EXACT_ANYDIM
     // vec_bytes need not be a multiple of 16: the lane of a row's last piece loads the dwords that exist and stages zeros behind them, a lane
     // behind the row's end stages zeros and loads nothing; the chains below then run over ceil(D / 4) or ceil(D / 16) pieces against a query
@@ -350,6 +386,13 @@ __device__ __forceinline__ void exact_dist_wide(const uint8_t GAS* graph, uint64
       for (int u = 0; u < 4; ++u)
         if (16u * (uint32_t)u < np) *(u32x4t*)(tile + tile_word(16u * (uint32_t)u + ls, lc)) = (u32x4t){st[u].x, st[u].y, st[u].z, st[u].w};
       wave_sync();
+#ifdef EXACT_WIDE_LABELS
+      if (t == 0u) {                                              // (uniform) the pass's label and bitmap words arrived in front of tile 0
+        const bool mt = (uint32_t)lane < np && (wm.f_any == 0u || (lab & wm.f_any) != 0u) && (lab & wm.f_all) == wm.f_all && ((exw >> (my & 31u)) & 1u) == 0u;
+        const uint64_t mm = __ballot(mt);
+        if (i0 == 0u) wm.mm0 = mm; else wm.mm1 = mm;              // (uniform)
+      }
+#endif
       if (t + 1u < T) fetch(t + 1u);
     };
     auto piece = [&](int c) { return *(const u32x4t*)(tile + tile_word((uint32_t)lane, (uint32_t)c)); };   // this lane's row
@@ -573,7 +616,10 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
       const WalkSurvivors sv = walk_filter(bloom, ci, x0, x1, sc, lane);
       const uint32_t n = sv.n, sid0 = sv.sid0, sid1 = sv.sid1;
       evals += n;
-#ifdef BANG_EXACT_LABELS
+#ifdef EXACT_WIDE_LABELS
+      // the label test travels with the cooperative fetch (exact_dist_wide); no survivors, no matches
+      WideMatch wm = {labels, excluded, f_any, f_all, 0ull, 0ull};
+#elif defined(BANG_EXACT_LABELS)
       // the survivors' label words, and their words of the exclusion bitmap: requested here, so that they travel with the vectors (every survivor id
       // is < n_nodes: the check above, and bang_k_search_exact_labels refuses n_nodes == 0)
       uint32_t lab0 = 0, lab1 = 0, ex0 = 0, ex1 = 0;
@@ -596,6 +642,8 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
         if (D > 256u) exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, w.scratch + WAVE_SCRATCH_WORDS, qr, aq.qw, aq.qq, lane);   // (uniform)
         else if (DT == BANG_F32) anydim_dist_f32(graph, entry_len, D, sc, n, sdist, qr, lane);
         else anydim_dist8<DT == BANG_I8>(graph, entry_len, D, aq.G, sc, n, sdist, aq.qw, aq.qq, lane);
+#elif defined(EXACT_WIDE_LABELS)
+        exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, w.scratch + WAVE_SCRATCH_WORDS, qr, qw, qq, lane, wm);
 #elif defined(BANG_EXACT_WIDE)
         exact_dist_wide<DT>(graph, entry_len, p.vec_bytes, D, sc, n, sdist, w.scratch + WAVE_SCRATCH_WORDS, qr, qw, qq, lane);
 #else
@@ -648,9 +696,14 @@ __global__ __launch_bounds__(EXACT_MAX_THREADS(DT)) void EXACT_KERNEL(const Exac
 #ifdef BANG_EXACT_LABELS
       // ---------------- CANON 18: the matching survivors of a merged iteration, in input order, go through the same K3a + K3b into the result list
       if (n > 0 && iter < cap_iter) {
+#ifdef EXACT_WIDE_LABELS
+        const uint64_t mm0 = wm.mm0, mm1 = wm.mm1;                // (tested under the first tile's wait: exact_dist_wide)
+        const bool mt0 = ((mm0 >> (uint32_t)lane) & 1ull) != 0ull, mt1 = lane == 0 && (mm1 & 1ull) != 0ull;
+#else
         const bool mt0 = (uint32_t)lane < n && (f_any == 0u || (lab0 & f_any) != 0u) && (lab0 & f_all) == f_all && ((ex0 >> (sid0 & 31u)) & 1u) == 0u;
         const bool mt1 = lane == 0 && n > 64 && (f_any == 0u || (lab1 & f_any) != 0u) && (lab1 & f_all) == f_all && ((ex1 >> (sid1 & 31u)) & 1u) == 0u;
         const uint64_t mm0 = __ballot(mt0), mm1 = __ballot(mt1);
+#endif
         const uint32_t nm0 = (uint32_t)__popcll(mm0), nm = nm0 + (uint32_t)__popcll(mm1);
         matched += nm;
         if (nm > 0) {                                             // (uniform)
@@ -717,7 +770,8 @@ static const void* exact_instance(int dtype) {
 static WaveKernelAttr exact_attr[3];                               // per instance: its figures, per device
 
 // LDS words per wave: worklist + scratch (+ the row tile of the wide builds); the label-filter builds hold a second list, the result list --
-// 2 (2L + L/4) + 144 words, 16 waves per CU up to L = 512
+// 2 (2L + L/4) + 144 words, 16 waves per CU up to L = 512.  Both together (label filters on the wide layouts): 2 (2L + L/4) + 144 + 1024 words --
+// 5 344 bytes at L = 37, where the registers bound the waves per CU, and 13 888 bytes at L = 512: 11 waves per CU, one workgroup of 11
 #ifdef BANG_EXACT_LABELS
 #define EXACT_LISTS 2u
 #else
@@ -774,6 +828,14 @@ extern "C" int EXACT_ENTRY(const bang_search_params* p, const bang_range_out* r,
   if (!r->d_radius || !r->d_hit_ids || !r->d_hit_dists || !r->d_offered || r->cap == 0u || r->cap > BANG_RANGE_MAX_HITS ||
       (r->d_excluded && p->n_nodes == 0u)) return BANG_ERR_ARG;
   return exact_launch(p, r, stream);
+}
+#elif defined(EXACT_WIDE_LABELS)
+extern "C" int EXACT_ENTRY(const bang_search_params* p, const bang_label_filter* f, void* stream) {      // (bang_k_search_exact_labels_wide's checked arguments)
+  if (!p || !f || p->row_layout != (uint32_t)EXACT_PULL || p->rr_vec_f16 != 0u) return BANG_ERR_ARG;
+  const uint64_t stride = EXACT_PULL ? p->rr_vec_stride : p->entry_len;
+  if (!bang_search_exact_supported((int)p->rr_dtype, p->rr_D, stride) || bang_search_can_rerank((int)p->rr_dtype, p->rr_D, stride, 0)) return BANG_ERR_ARG;
+  if (!f->d_labels || !f->d_filters || p->n_nodes == 0u) return BANG_ERR_ARG;
+  return exact_launch(p, f, stream);
 }
 #elif defined(BANG_EXACT_LABELS)
 extern "C" int EXACT_ENTRY(const bang_search_params* p, const bang_label_filter* f, void* stream) {

@@ -187,6 +187,34 @@ extern "C" int bang_k_search_exact_labels(const bang_search_params* p, const ban
   return bang_k_search_exact_labels_hbm(p, f, stream);
 }
 
+// The same on the layouts bang_k_search_exact sends to its wide instances (engine option labels_wide): the checks above, the
+// layout rule turned round, routed on row_layout to the instances of bang_search_exact_wide_labels.o / bang_search_exact_wide_labels_pull.o
+extern "C" int bang_k_search_exact_labels_wide(const bang_search_params* p, const bang_label_filter* f, void* stream) {
+  if (!p) return BANG_ERR_ARG;
+  if (!f) { bang_set_error("distance = 1, labels_wide: the filter arguments f (bang_label_filter) are null"); return BANG_ERR_ARG; }
+  if (!f->d_labels) { bang_set_error("distance = 1, labels_wide: d_labels (one label word per node) is null"); return BANG_ERR_ARG; }
+  if (!f->d_filters) { bang_set_error("distance = 1, labels_wide: d_filters (the queries' {any, all} words) is null"); return BANG_ERR_ARG; }
+  if (p->n_nodes == 0u) { bang_set_error("distance = 1, labels_wide: n_nodes = 0: d_labels and d_excluded are indexed by node id and need the number of nodes"); return BANG_ERR_ARG; }
+  if (p->Q == 0) return BANG_OK;
+  if (p->any_dim > 1u) { bang_set_error("distance = 1, labels_wide: any_dim = %u (0 or 1)", p->any_dim); return BANG_ERR_ARG; }
+  if (exact_takes_anydim(p)) {
+    bang_set_error("distance = 1, labels_wide: any_dim = 1 with a layout or query length of the any-dimension instances (dtype %u, rr_D = %u, rr_qdim = %u), "
+                   "which have no label-filter form", p->rr_dtype, p->rr_D, p->rr_qdim);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  const int rc = exact_check(p);
+  if (rc != BANG_OK) return rc;
+  if (p->rr_vec_f16 == 1u) { bang_set_error("distance = 1, labels_wide: rr_vec_f16 = 1 (fp16 rows) has no label-filter instance"); return BANG_ERR_UNSUPPORTED; }
+  const uint64_t stride = p->row_layout == 1u ? p->rr_vec_stride : p->entry_len;
+  if (bang_search_can_rerank((int)p->rr_dtype, p->rr_D, stride, 0)) {
+    bang_set_error("distance = 1, labels_wide: the vector layout (dtype %u, rr_D = %u, stride %llu) runs on the narrow instances: bang_k_search_exact_labels "
+                   "serves it", p->rr_dtype, p->rr_D, (unsigned long long)stride);
+    return BANG_ERR_UNSUPPORTED;
+  }
+  if (p->row_layout == 1u) return bang_k_search_exact_wide_labels_pull(p, f, stream);
+  return bang_k_search_exact_wide_labels(p, f, stream);
+}
+
 // The walk of bang_k_search_exact with a per-query radius (CANON 19): the same results, and beside them every evaluated node
 // within the radius in the query's row of the hit log.  The narrow layouts only, routed on row_layout to the instances of
 // bang_search_exact_range.o / bang_search_exact_range_pull.o

@@ -833,6 +833,16 @@ int bang_k_search_exact_labels(const bang_search_params* p, const bang_label_fil
  * register count that of the label-filter instance; the second one for the pulled-rows form (row_layout = 1) */
 int bang_search_exact_labels_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
 int bang_search_exact_labels_pull_geometry(int dtype, uint32_t L, uint32_t Q, uint32_t max_wgs, uint32_t max_waves, uint32_t* workgroups, uint32_t* waves);
+/* LABEL FILTERS ON THE WIDE LAYOUTS (csrc/bang_search_exact.hip built as bang_search_exact_wide_labels.o / bang_search_exact_wide_labels_pull.o;
+ * engine option labels_wide).  The contract of bang_k_search_exact_labels above, word for word -- match rule, result list,
+ * d_matched, an unfiltered query returns what bang_k_search_exact returns, the walk is bang_k_search_exact's bit for bit -- for exactly the layouts
+ * that bang_k_search_exact sends to its wide instances: those of bang_search_exact_supported that bang_search_can_rerank refuses (8-bit vectors with
+ * D / 16 not a power of two or D > 256, float vectors with D > 256; D <= BANG_EXACT_MAX_D).  Routed on row_layout to search_exact_wide_labels_kernel
+ * (0) / search_exact_wide_labels_pull_kernel (1).  LDS per wave: 2 (2L + L/4) + 144 + 1024 words (worklist, result list, sort scratch, row tile).
+ * Every check of bang_k_search_exact is made, before any HIP call; refused in addition, with the member named: f, d_labels or d_filters null and
+ * n_nodes == 0 (BANG_ERR_ARG); a narrow layout -- bang_k_search_exact_labels serves it --, rr_vec_f16 = 1, and any_dim = 1 with a layout or a
+ * query length of the any-dimension instances (BANG_ERR_UNSUPPORTED).  bang_k_search_exact_labels itself is what it was. */
+int bang_k_search_exact_labels_wide(const bang_search_params* p, const bang_label_filter* f, void* stream);
 
 /* RANGE SEARCH on the exact-distance walk (csrc/bang_search_exact.hip built as bang_search_exact_range.o / bang_search_exact_range_pull.o; engine:
  * option range_hits + bang_set_query_radii_e; DESIGN.md section 2, CANON 19).  The walk and the results are bang_k_search_exact's, bit for bit --

@@ -15,7 +15,13 @@ instances are read from the code objects.  There is no threshold: the numbers ar
 
   python tools/labels_sweep.py --workloads sift1m,deep1m --out profiles/labels_sweep.json --md profiles/labels_sweep.md
 
-Not part of bench.py: the measurement behind profiles/labels.md.
+  python tools/labels_sweep.py --wide --Ls 46,94,190 --runs 5 --out profiles/labels_wide.json --md profiles/labels_wide.md
+
+--wide: the same columns on the wide vector layouts (engine option labels_wide = 1, bang_k_search_exact_labels_wide): workloads
+yfcc192 (uint8, D = 192) and gist960 (float, D = 960), the truth of a filtered column from Engine.scan with the same filter (scan_any = 1) instead
+of the torch brute force, registers of the two wide label-filter code objects.
+
+Not part of bench.py: the measurement behind profiles/labels.md and profiles/labels_wide.md.
 """
 import argparse
 import json
@@ -39,6 +45,8 @@ import exact_sweep  # noqa: E402
 import exclude_sweep  # noqa: E402
 
 SEED = 20261
+# --wide: structured 10^6-point indexes of the wide layouts filtered search is asked for most (N, D, dtype, R, m, clusters: exact_sweep.WORKLOADS)
+WIDE_WORKLOADS = {"yfcc192": (1_000_000, 192, "uint8", 64, 48, 256), "gist960": (1_000_000, 960, "float", 64, 120, 256)}
 
 
 def label_table(N, shares):
@@ -50,14 +58,16 @@ def label_table(N, shares):
     return lab
 
 
-def instance_registers():
-    """{kernel: [(dtype code, VGPRs, scratch bytes, waves per CU by registers)]} of the two label-filter code objects, or {} without llvm binutils"""
+def instance_registers(wide=False):
+    """{kernel: [(dtype code, VGPRs, scratch bytes, waves per CU by registers)]} of the two label-filter code objects (wide: those of the wide
+    layouts), or {} without llvm binutils"""
     llvm = "/opt/rocm/lib/llvm/bin"
     tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
     if not all(os.path.exists(t) for t in tools):
         return {}
     out = {}
-    for obj, kernel in (("bang_search_exact_labels.o", "search_exact_labels_kernel"), ("bang_search_exact_labels_pull.o", "search_exact_labels_pull_kernel")):
+    tag = "wide_labels" if wide else "labels"
+    for obj, kernel in ((f"bang_search_exact_{tag}.o", f"search_exact_{tag}_kernel"), (f"bang_search_exact_{tag}_pull.o", f"search_exact_{tag}_pull_kernel")):
         path = os.path.join(ROOT, "bang-billion-scale-ann_amd", "lib", obj)
         if not os.path.exists(path):
             continue
@@ -145,7 +155,8 @@ def markdown(out):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--workloads", default="sift1m,deep1m")
+    ap.add_argument("--wide", action="store_true", help="the wide layouts: option labels_wide = 1, workloads yfcc192,gist960, truth from Engine.scan")
+    ap.add_argument("--workloads", default="")
     ap.add_argument("--placements", default="device")
     ap.add_argument("--batch", type=int, default=10000)
     ap.add_argument("--Ls", default="22,46,94,190")
@@ -160,9 +171,11 @@ def main():
         raise SystemExit("labels_sweep needs a HIP device: nothing here is measured on a CPU")
     import torch
     k = 10
+    exact_sweep.WORKLOADS.update(WIDE_WORKLOADS)
+    a.workloads = a.workloads or ("yfcc192,gist960" if a.wide else "sift1m,deep1m")
     Ls = [int(x) for x in a.Ls.split(",")]
     shares = [float(x) for x in a.shares.split(",") if x]
-    out = {"k": k, "runs": a.runs, "shares": shares, "registers": instance_registers(), "workloads": [], "rows": []}
+    out = {"k": k, "runs": a.runs, "shares": shares, "registers": instance_registers(a.wide), "workloads": [], "rows": []}
 
     def flush():
         for path, text in ((a.out, json.dumps(out, indent=1)), (a.md, markdown(out))):
@@ -180,7 +193,7 @@ def main():
         x = torch.from_numpy(ix.vectors().astype(np.float32)).to(dev)
         qq = torch.from_numpy(q.astype(np.float32)).to(dev)
         truth = {None: (np.ascontiguousarray(gi[:a.batch], dtype=np.uint32), np.ascontiguousarray(gd[:a.batch], dtype=np.float32))}
-        for b in range(len(shares)):
+        for b in range(0 if a.wide else len(shares)):
             truth[b] = exclude_sweep.live_truth(x, qq, np.nonzero((labels >> np.uint32(b)) & 1 == 0)[0].astype(np.uint32), k)
         del x, qq
         torch.cuda.empty_cache()
@@ -189,8 +202,12 @@ def main():
                                  "drawn": [100.0 * float(((labels >> np.uint32(b)) & 1).mean()) for b in range(len(shares))]})
         for placement in a.placements.split(","):
             opts = dict(graph=bang_amd.GRAPH_DEVICE) if placement == "device" else dict(graph=bang_amd.GRAPH_HOST, pull=1, rows_hbm=0)
-            with bang_amd.Engine(ix.dtype, distance=1, **opts) as e:
+            with bang_amd.Engine(ix.dtype, distance=1, labels_wide=int(a.wide), scan_any=int(a.wide), **opts) as e:
                 e.load_index(ix)
+                for b in range(len(shares) if a.wide else 0):          # the brute-force answer under the same filter, in the search's distance bits
+                    e.set_labels(labels)
+                    gi_b, gd_b, _ = e.scan(q, k, any=np.full(q.shape[0], 1 << b, np.uint32), all=np.zeros(q.shape[0], np.uint32))
+                    truth[b] = (gi_b.astype(np.uint32), np.ascontiguousarray(gd_b.T))
                 out["rows"] += measure(e, name, placement, ix, q, labels, shares, truth, Ls, k, a.runs, log)
                 e.unload()
             flush()
